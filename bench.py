@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- edges/s per R-GCN layer (forward + backward) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nodes .. --edges .. --relations .. --width ..]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nodes .. --edges .. --relations .. --width ..] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[3], the configuration the metric is quoted on; fits one GPU):
 synthetic graph, 10M nodes / 100M edges / 32 relations, features 64 -> 64, fp32, inputs of
@@ -16,6 +16,11 @@ reported separately (plan_build_s), as SURVEY.md 8d prescribes.  Inputs are resi
 Timing: W untimed warm-up steps, then exactly K steps between barrier + synchronize pairs (value = E * K / that
 time, max over ranks); every timed step is also bracketed by HIP events on the launch stream, whose MEDIAN is
 reported beside it (20 warm-up + 50 timed iterations, median -- the defaults).
+
+--dump-outputs DIR: what the LAST timed step handed its caller -- the layer output and the gradients of x, weight, root and
+bias (rank 0's tensors) -- as DIR/<name>.npy in float32, written after the clock stops.  Arrays larger than their share of
+DUMP_BYTES are cut to a fixed, seeded sample of rows (the same rows of `out` and `d_x`); the inputs are seeded, so two builds
+can be compared output for output.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU over RCCL): the SAME graph is
 edge-partitioned by destination range (strong scaling); every step includes the per-layer
@@ -45,6 +50,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -67,6 +73,7 @@ LADDER = (("100k/1M", 100_000, 1_000_000, 32, 64, 64, None), ("1M/10M", 1_000_00
           # edges, the first 224 nodes two thirds); the forward takes the edge-parallel path, dX the tile kernel
           ("10M/100M skew", 10_000_000, 100_000_000, 32, 64, 64, None))
 CPU_RUNG = ("1M/10M", 1_000_000, 10_000_000)
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much data (under 64 MB in all with the .npy headers)
 
 
 def algorithmic_bytes(e, n, r, din, dout):
@@ -142,6 +149,23 @@ def cpu_baseline(n, e, r, din, dout):
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every tensor of ``arrays`` as <path>/<name>.npy in float32.  One larger than its equal share of
+    DUMP_BYTES keeps a seeded random sample of its rows (of its elements when one row is too large), in row order; the
+    sample depends only on the row count and the seed, so arrays of one row count keep the same rows."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() * 4 > share:
+            if t.dim() < 2 or t[0].numel() * 4 > share:
+                t = t.reshape(-1)
+            keep = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:share // (t[0].numel() * 4)]
+            t = t[keep.sort().values.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        log(f"wrote {os.path.join(path, name + '.npy')}: {tuple(t.shape)}")
 
 
 def plan_stats(plan):
@@ -344,7 +368,12 @@ def main():
                          "rank_share_ms per pieces / exchange, 0 = skip")
     ap.add_argument("--emulate-rank", type=int, default=None, help="which rank to emulate (default: rank 0 and the heaviest rank of the cut)")
     ap.add_argument("--emulate-only", action="store_true", help="skip the ladder, the CPU baseline and the alt-kernel leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (output, gradients of x / weight / root / bias; seeded row "
+                         "sample of the large ones, %d MiB in all) as DIR/<name>.npy, float32" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import __graft_entry__ as ge
     ge.build()          # before anything touches the GPU or the process group (hipcc is a child process)
@@ -402,6 +431,7 @@ def main():
         conv.weight.grad = conv.root.grad = conv.bias.grad = None
         out = conv(x, ei, et)
         out.backward(dg)
+        return out
 
     def barrier():
         if world > 1:
@@ -424,8 +454,9 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for a, b in evs:
+        y = None        # the previous step's output goes back to the allocator before the next step, as in the warm-up
         a.record()
-        step()
+        y = step()
         b.record()
     barrier()
     dt = time.perf_counter() - t0
@@ -433,6 +464,10 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:      # before the legs below run the layer again
+        dump_outputs(args.dump_outputs, {"out": y, "d_x": x.grad, "d_weight": conv.weight.grad, "d_root": conv.root.grad,
+                                         "d_bias": conv.bias.grad})
+    del y
     step_ms = sorted(a.elapsed_time(b) for a, b in evs)
     log(f"{args.steps} timed steps: {dt / args.steps * 1e3:.2f} ms/step (per-step HIP events: median "
         f"{statistics.median(step_ms):.2f}, min {step_ms[0]:.2f}, max {step_ms[-1]:.2f})")
