@@ -99,10 +99,13 @@ typedef struct rgcn_plan {
                             * 5 (chunk = 64; the plan rgcn_bwd_dw_tiles walks): layout 0 with PAIRS of rows of one (destination, relation,
                             * weight) on one slot in the (tile, relation) groups of at most two chunks, see slot_src2; n_units / rel_order
                             * hold the units that are left (its rgcn_plan_build_finish synchronises the stream to count them);
-                            * rgcn_bwd_dw answers RGCN_ERR_PLAN */
+                            * rgcn_bwd_dw, rgcn_fwd and rgcn_bwd_dx answer RGCN_ERR_PLAN.
+                            * Any other value, and layouts 1 / 3 with 64-slot chunks, is refused by every entry point (RGCN_ERR_PLAN) */
     int32_t chunk_rows;    /* rows a chunk may hold: = chunk, or 112 (chunk = 128: seven row tiles of rows, the eighth free for shadow
                             * rows; built by rgcn_plan_build_begin(chunk = 112)): what rgcn_tile3p_kernel's 42 KiB ring slots hold,
-                            * which leaves its accumulator room for tiles up to 272.  0 is read as `chunk` */
+                            * which leaves its accumulator room for tiles up to 272.  0 is read as `chunk`; any other value is
+                            * refused (RGCN_ERR_PLAN).  max(chunk_cnt) <= chunk_rows is a caller promise like every other array
+                            * content: the entry points check header fields only.  The builders keep it */
     const int32_t* tile_ptr;   /* [n_tiles + 1] tile-major chunk ranges */
     const int32_t* chunk_rel;  /* [n_chunks] relation id, R' for root chunks */
     const int32_t* chunk_cnt;  /* [n_chunks] slots of the chunk's used 16-slot MFMA row tiles (16, 32, ... chunk);

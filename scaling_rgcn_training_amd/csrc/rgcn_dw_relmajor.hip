@@ -883,8 +883,14 @@ extern "C" int rgcn_bwd_dw(const rgcn_plan_t* plan, const float* x, int ldx, int
     int unit_begin = 0, n_units = plan->n_units;
     if (flags & RGCN_FLAG_DW_ROOT_ONLY) {
         if (plan->layout == 2) return RGCN_ERR_PLAN;       // (the root units' position follows from the tile geometry)
-        // (both plan layouts put ceil(rows / 16) row tiles of a group on contiguous tiles of its chunks)
-        auto units_of = [&](long rows) -> long { return ((rows + 15) / 16 + 3) / 4; };
+        // (both plan layouts put ceil(rows / 16) row tiles of a group on contiguous tiles of its chunks; 112-row chunks hold
+        // seven of them, so a group takes 2 units per full chunk and ceil(rest / 4) in its last: rgcn_plan.hip group_sizes_kernel)
+        const long cap = (plan->chunk_rows > 0 ? plan->chunk_rows : plan->chunk) / 16;
+        auto units_of = [&](long rows) -> long {
+            const long nt = (rows + 15) / 16;
+            if (cap * 16 == plan->chunk) return (nt + 3) / 4;
+            return nt / cap * ((cap + 3) / 4) + (nt % cap + 3) / 4;
+        };
         const long last_rows = (long)plan->n_owned - (long)(plan->n_tiles - 1) * plan->tile;
         const long root_units = (long)(plan->n_tiles - 1) * units_of(plan->tile) + units_of(last_rows);
         if (root_units <= 0 || root_units > n_units) return RGCN_ERR_PLAN;

@@ -28,7 +28,7 @@ struct EpArgs {
     const float* wp;       // rgcn_pack_weights: fp32 MFMA fragment order
     float* z;              // [n_units * 64][ldz]
     unsigned x_bytes;      // rows * ldx * 4 when x can be gathered through a buffer descriptor, else 0
-    int n_rows, ldx, din4, ldz, n_units, units_per_wave;
+    int n_rows, ldx, din4, ldz, dout4, n_units, units_per_wave;   // dout4: 16-byte pieces of a z row written (round4(dout))
 };
 
 // KEEP: the relation's KT x NT fragments stay in registers (at most 64 VGPRs) while consecutive units share the relation
@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) rgcn_ep_transform_kernel(const EpArgs a) 
             float* zr = a.z + (slot0 + 16 * t) * (size_t)a.ldz + 4 * kq;
 #pragma unroll
             for (int s = 0; s < NT; ++s)
-                if (16 * s + 4 * kq < a.ldz) *(f32x4*)(zr + 16 * s) = acc[s] * w;
+                if (4 * s + kq < a.dout4) *(f32x4*)(zr + 16 * s) = acc[s] * w;
             if (t + 1 < ntile) {
 #pragma unroll
                 for (int j = 0; j < KT; ++j) cur[j] = nxt[j];
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(256) rgcn_ep_transform3_kernel(const EpArgs a)
 #pragma unroll
                     for (int q = 0; q < 6; ++q)
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[t4][pw[q]][sk], __builtin_bit_cast(bf16x8, xp[px[q]][sk]), acc, 0, 0, 0);
-                if (16 * t4 + 4 * kq < a.ldz) *(f32x4*)(zr + 16 * t4) = acc * w;
+                if (4 * t4 + kq < a.dout4) *(f32x4*)(zr + 16 * t4) = acc * w;
             }
             if (t + 1 < ntile) {
 #pragma unroll
@@ -219,7 +219,7 @@ struct EpSumArgs {
     const float* bias;
     const float* mask;
     float* out;
-    int ldin, ldo, ldm, width, n_out, act, final_level;
+    int ldin, ldo, ldm, width, width4, n_out, act, final_level;   // width4: 16-byte pieces of a row read / written
 };
 
 template <int G>
@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(256) rgcn_ep_segment_sum_kernel(const EpSumArg
     const int piece = lane % G;
     if (seg >= a.n_out) return;
     const int q0 = a.seg_ptr[seg], q1 = a.seg_ptr[seg + 1];
-    const bool col_in = 4 * piece < a.ldin;     // pieces beyond the row stride of `in` (narrow layers): nothing to read
+    const bool col_in = piece < a.width4;       // pieces beyond round4(width) (narrow layers): nothing to read or write
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
     auto rowp = [&](int q) { return a.in + (size_t)(a.seg_idx ? a.seg_idx[q] : q) * a.ldin + 4 * piece; };
     int q = q0;
@@ -253,7 +253,7 @@ __global__ void __launch_bounds__(256) rgcn_ep_segment_sum_kernel(const EpSumArg
     }
     f32x4 v = s0 + s1;
     (void)s2; (void)s3;
-    if (4 * piece >= a.ldo) return;
+    if (!col_in) return;
     if (a.final_level) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -311,6 +311,7 @@ extern "C" int rgcn_ep_transform(const rgcn_edge_units_t* units, const float* x,
     a.ldx = ldx;
     a.din4 = (din + 3) / 4;
     a.ldz = ldz;
+    a.dout4 = (dout + 3) / 4;
     a.n_units = units->n_units;
     // enough waves to fill the chip (256 CUs x 16 waves) before a wave takes several units; consecutive units share a
     // relation, so a longer range reloads the weight fragments less often
@@ -361,7 +362,8 @@ extern "C" int rgcn_ep_segment_sum(const float* in, int ldin, const int32_t* seg
     a.n_out = n_out;
     a.act = act;
     a.final_level = final_level;
-    const int ld4 = (ldo > ldin ? ldo : ldin) / 4;
+    const int ld4 = (width + 3) / 4;
+    a.width4 = ld4;
     const int G = ld4 <= 4 ? 4 : (ld4 <= 8 ? 8 : (ld4 <= 16 ? 16 : 32));
     const long waves = ((long)n_out + 64 / G - 1) / (64 / G);
     const unsigned blocks = (unsigned)((waves + 3) / 4);

@@ -236,7 +236,9 @@ static int tiles_per_workgroup(int n_tiles) {
 
 // (layout 2 -- the edge-parallel path's dense relation-major units handed to rgcn_bwd_dw -- has no tiles to walk: a heavy part
 // of a few units on a graph of several 32768-node pseudo tiles is a valid plan, so the chunks-per-tile bound does not apply to it;
-// layout 5 -- pairs of rows on one slot -- leaves chunks EMPTY: fewer units than chunks)
+// layout 5 -- pairs of rows on one slot -- leaves chunks EMPTY: fewer units than chunks).
+// What is checked: the header fields.  The arrays' contents (max(chunk_cnt) <= chunk_rows among them) are the caller's promise:
+// the builders keep it, and no launch reads them back to verify.
 static int check_plan(const rgcn_plan_t* p) {
     if (p == nullptr) return RGCN_ERR_NULL;
     if (!p->tile_ptr || !p->chunk_rel || !p->chunk_cnt || !p->chunk_tile || !p->chunk_flags || !p->rel_order ||
@@ -247,6 +249,11 @@ static int check_plan(const rgcn_plan_t* p) {
         p->n_tiles <= 0 || (p->layout != 2 && p->n_chunks < p->n_tiles) || p->n_chunks <= 0 || (long)p->n_tiles * p->tile < p->n_owned ||
         (p->chunk != 64 && p->chunk != 128) || (p->layout != 5 && p->n_units < p->n_chunks) || p->n_units > p->n_chunks * (p->chunk / 64))
         return RGCN_ERR_PLAN;
+    // layouts the builder makes, each with the chunk size it makes it with: a kernel never walks slots it cannot read
+    if (p->layout != 0 && p->layout != 1 && p->layout != 2 && p->layout != 3 && p->layout != 5) return RGCN_ERR_PLAN;
+    if ((p->layout == 1 || p->layout == 3) && p->chunk != 128) return RGCN_ERR_PLAN;
+    // chunk_rows picks the ring-slot size of the forward / dX kernel: only the chunk itself or the 112-row form of 128-slot chunks
+    if (p->chunk_rows != 0 && p->chunk_rows != p->chunk && !(p->chunk_rows == 112 && p->chunk == 128)) return RGCN_ERR_PLAN;
     return RGCN_OK;
 }
 

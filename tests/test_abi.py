@@ -83,3 +83,77 @@ def test_binding_constants_match_the_header():
     for name in ("NONE", "RELU", "SIGMOID"):
         assert acts["RGCN_ACT_" + name] == getattr(_lib, "ACT_" + name), name
 
+
+
+# ---- plan refusals: header fields a kernel cannot walk are answered RGCN_ERR_PLAN before anything touches a device ------------
+# Every plan-taking entry point validates the plan before check_device, so these calls stop at an argument check that follows:
+# rgcn_fwd / rgcn_bwd_dx get x = NULL (an accepted plan answers RGCN_ERR_NULL), the weight-gradient entry points a workspace of
+# 0 bytes (RGCN_ERR_WORKSPACE); a refused plan answers RGCN_ERR_PLAN.  Nothing is ever launched, on any machine.
+_DUMMY = (ctypes.c_int32 * 64)()       # plan arrays: host memory the argument checks see as non-NULL and never read
+
+
+def _plan(layout, chunk, chunk_rows, tile=320):
+    p = ctypes.addressof(_DUMMY)
+    n_chunks = 8
+    return _lib.RgcnPlanStruct(1000, 1000, 3, tile, 4, n_chunks, chunk, n_chunks, layout, chunk_rows,
+                               p, p, p, p, p, p, p, p, p, p, p if layout == 5 else None)
+
+
+def _calls(ps):
+    """status of the four plan-taking entry points on plan `ps` (no device memory, no launch)"""
+    lib = _lib.load()
+    b, d = ctypes.byref(ps), ctypes.addressof(_DUMMY)
+    return {
+        "fwd": lib.rgcn_fwd(b, None, 64, 64, d, None, d, 64, 64, 0, 0, None),
+        "bwd_dx": lib.rgcn_bwd_dx(b, None, 64, 64, d, d, 64, 64, None, 0, 0, None),
+        "bwd_dw": lib.rgcn_bwd_dw(b, d, 64, 64, d, 64, 64, d, 0, d, d, d, 0, None),
+        "bwd_dw_tiles": lib.rgcn_bwd_dw_tiles(b, d, d, 64, 64, d, 64, 64, d, 0, d, 0, None),
+    }
+
+
+PLAN, NULL, WS = -4, -1, -6
+# (layout, chunk, chunk_rows) -> status of fwd, bwd_dx, bwd_dw, bwd_dw_tiles (tile 320: the tile-major d_weight geometry);
+# NULL / WS: the plan passed (the call stopped at the argument check after it), PLAN: refused
+ACCEPTED = {
+    (0, 64, 64): (NULL, NULL, WS, WS), (0, 64, 0): (NULL, NULL, WS, WS),
+    (0, 128, 128): (NULL, NULL, WS, PLAN), (0, 128, 112): (NULL, NULL, WS, PLAN), (0, 128, 0): (NULL, NULL, WS, PLAN),
+    (1, 128, 128): (NULL, NULL, WS, PLAN),
+    (2, 64, 64): (PLAN, PLAN, WS, PLAN),
+    (3, 128, 128): (NULL, NULL, PLAN, PLAN), (3, 128, 112): (NULL, NULL, PLAN, PLAN),
+    (5, 64, 64): (PLAN, PLAN, PLAN, WS),
+}
+
+
+@pytest.mark.parametrize("key", sorted(ACCEPTED), ids=lambda k: "layout%d-chunk%d-rows%d" % k)
+def test_plan_layouts_the_entry_points_accept(key):
+    assert tuple(_calls(_plan(*key)).values()) == ACCEPTED[key]
+
+
+@pytest.mark.parametrize("layout,chunk,chunk_rows", [
+    (4, 64, 64), (6, 64, 64), (-1, 64, 64), (7, 128, 128), (4, 128, 128),      # layouts no builder makes
+    (1, 64, 64), (3, 64, 64),                                                  # team / merged-run layouts on 64-slot chunks
+    (0, 64, 112), (0, 128, 96), (0, 128, 64), (0, 64, 128), (0, 128, 256), (0, 128, -1), (3, 128, 111), (1, 128, 64),
+    (5, 64, 112), (2, 64, 32),                                                 # chunk_rows other than 0, chunk, or 112 of 128
+])
+def test_plans_no_kernel_walks_are_refused(layout, chunk, chunk_rows):
+    st = _calls(_plan(layout, chunk, chunk_rows))
+    assert st == dict.fromkeys(st, PLAN), st
+
+
+def test_pair_plan_is_refused_by_forward_and_dx():
+    """layout 5 (rows of a pair on one slot, slot_src2) is rgcn_bwd_dw_tiles' plan: the forward / dX kernels ignore slot_src2
+    and would drop every pair's second row"""
+    for tile in (320, 64):
+        st = _calls(_plan(5, 64, 64, tile=tile))
+        assert st["fwd"] == PLAN and st["bwd_dx"] == PLAN and st["bwd_dw"] == PLAN
+
+
+def test_workspace_one_byte_short_is_refused():
+    lib = _lib.load()
+    d = ctypes.addressof(_DUMMY)
+    ps = _plan(0, 64, 64)
+    need = lib.rgcn_bwd_dw_workspace_bytes(ctypes.byref(ps), 64, 64)
+    assert need > 0
+    assert lib.rgcn_bwd_dw(ctypes.byref(ps), d, 64, 64, d, 64, 64, d, need - 1, d, d, d, 0, None) == -6
+    need_t = lib.rgcn_bwd_dw_tiles_workspace_bytes(3)
+    assert lib.rgcn_bwd_dw_tiles(ctypes.byref(ps), d, d, 64, 64, d, 64, 64, d, need_t - 1, d, 0, None) == -6
