@@ -38,7 +38,7 @@ extern "C" {
 #define RGCN_UNIT 64 /* edge slots per unit of the weight-gradient walk (rel_order); a chunk is 1 or 2 units */
 #define RGCN_CHUNK_MAX 128 /* plan->chunk is 64 or 128 edge slots (rows of one LDS ring slot of the forward / dX kernel) */
 #define RGCN_MAX_WIDTH 128
-#define RGCN_DW_WALKERS 2048 /* waves that walk rel_order side by side (512 workgroups x 4): the interleave of rel_order */
+#define RGCN_DW_WALKERS 2048 /* waves that walk rel_order side by side in the largest relation-major dW launch (512 workgroups x 4) */
 
 /* activation fused into rgcn_fwd's store (reference model/layers.py:22 F.relu, :24 activation = torch.sigmoid) */
 enum rgcn_act { RGCN_ACT_NONE = 0, RGCN_ACT_RELU = 1, RGCN_ACT_SIGMOID = 2 };
@@ -50,7 +50,7 @@ enum rgcn_act { RGCN_ACT_NONE = 0, RGCN_ACT_RELU = 1, RGCN_ACT_SIGMOID = 2 };
 #define RGCN_FLAG_DW_ROOT_ONLY 16u   /* rgcn_bwd_dw: d_root and d_bias only (the relations went to rgcn_bwd_dw_tiles) */
 #define RGCN_FLAG_SPLIT_PRODUCERS 32u /* rgcn_fwd / rgcn_bwd_dx: the bf16 x 3 kernel whose PRODUCER waves split the gathered rows
                                        * (fp32-equivalent: 24 significant bits on both operands, six bf16 products): 64 x 64 layers,
-                                       * 128-slot chunks, tile <= 224 (layout-1 plans: two teams of consumer waves); other shapes take the exact-fp32 kernel.
+                                       * 128-slot chunks, tile <= 224 (layout-1 plans too, walked like layout 0); other shapes take the exact-fp32 kernel.
                                        * rgcn_bwd_dw_tiles: the same walk with both operands split into three bf16 pieces in registers
                                        * (six bf16 products, fp32 accumulation; same fp32-equivalence) */
 #define RGCN_FLAG_EXACT_FP32 8u     /* rgcn_fwd / rgcn_bwd_dx: the exact-fp32 MFMA kernel whatever else the flags ask for */
@@ -85,8 +85,8 @@ typedef struct rgcn_plan {
     int32_t layout;        /* 0: the rows of a (tile, relation) group are dealt over all its row tiles; 1 (chunk = 128): TEAM
                             * placement -- a chunk's rows are cut at a change of destination into part A on its first
                             * ceil(nt / 2) row tiles and part B on the others, so the two parts scatter into disjoint rows
-                            * (chunk_flags bit 8: they do not) and experiment builds of the forward / dX kernel of 64 x 64 layers give
-                            * each part to its own team of consumer waves; same chunks and row-tile counts as layout 0;
+                            * (chunk_flags bit 8: they do not); every kernel that takes layout 0 walks it the same way;
+                            * same chunks and row-tile counts as layout 0;
                             * 2: no tiles -- dense relation-major units for rgcn_bwd_dw only (rgcn_edge_units);
                             * 3 (chunk = 128): layout 0 with the rows of a (destination, relation) run on ONE slot where a chunk is
                             * a whole (tile, relation) group with runs of at most 3 rows: heads on slots 0 .. H-1, second rows on

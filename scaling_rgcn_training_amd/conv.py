@@ -36,15 +36,9 @@ def _rows16(t: Tensor, width: int) -> Tensor:
     return t.contiguous()
 
 
-# experiment overrides of the (tile, chunk) layout: read ONCE at import, never on the forward path
-_ENV_TILE = int(os.environ["RGCN_TILE"]) if "RGCN_TILE" in os.environ else None
-_ENV_CHUNK = int(os.environ["RGCN_CHUNK"]) if "RGCN_CHUNK" in os.environ else None
 # forward / dX on the bf16 x 3 kernel whose PRODUCER waves split the gathered rows (csrc/rgcn_tile3p.hip):
 # fp32-equivalent arithmetic; layers padded to 64 x 64 on graphs dense enough for 128-slot chunks.  "1" / "0" / "auto"
 _SPLIT_PRODUCERS_DEFAULT = os.environ.get("RGCN_SPLIT_PRODUCERS", "1")
-# "1": plans of those layers in the TEAM placement (plan layout 1, plan.team_placement) for experiment builds of the kernel
-# with two teams of consumer waves (csrc/rgcn_tile3p.hip RGCN_P3_TEAMS=2: measured no faster).  Default: layout 0
-_TEAM_LAYOUT_DEFAULT = os.environ.get("RGCN_TEAM_LAYOUT", "0") == "1"
 _MERGE_RUNS_DEFAULT = os.environ.get("RGCN_MERGE_RUNS", "1") == "1"
 _PATH_DEFAULT = os.environ.get("RGCN_PATH", "auto")       # auto | ring | ep
 SPLIT_PRODUCERS_TILE = 224       # the largest tile whose fp32 accumulator fits beside the kernel's two 48 KiB ring slots
@@ -73,13 +67,12 @@ def _side_stream(device) -> "torch.cuda.Stream":
 def layout_for(in_channels: int, out_channels: int, n_nodes: int = 0, n_edges: int = 0,
                num_relations: int = 1) -> Tuple[int, int]:
     """(output nodes per tile, edge slots per chunk) for a layer (plan.choose_layout): bounded by the LDS budget of
-    the wider side, tuned to the graph's density.  ``RGCN_TILE`` / ``RGCN_CHUNK`` in the environment at import time
-    override (experiments)."""
+    the wider side, tuned to the graph's density."""
     if not (1 <= in_channels <= 128 and 1 <= out_channels <= 128):
         raise ValueError(f"RGCNConv widths must be in 1..128, got {in_channels}->{out_channels}")
     from .plan import choose_layout
     tile, chunk = choose_layout(n_nodes, n_edges, num_relations, in_channels, out_channels)
-    return (_ENV_TILE or tile), (_ENV_CHUNK or chunk)
+    return tile, chunk
 
 
 def tile_for(in_channels: int, out_channels: int, n_nodes: int = 0, n_edges: int = 0, num_relations: int = 1) -> int:
@@ -528,7 +521,6 @@ class RGCNConv(nn.Module):
         # expects to be faster on the graph (many relations / few tiles / hubs -> edge-parallel); "ring" / "ep" or a
         # (forward, dX) pair pins it.  RGCN_PATH in the environment at import time sets the default.
         self.path = _PATH_DEFAULT
-        self.team_layout = _TEAM_LAYOUT_DEFAULT     # plans of such layers in the team placement (experiment builds: two consumer teams)
         # forward / dX plans in layout 3 where the producer-split kernel runs them and the tile-major kernel takes d_weight: the rows
         # of a (destination, relation) run on ONE slot, summed by the producers before the cut -- aggregate, then transform, as the
         # reference does; 13 % fewer row tiles at the headline config (plan.compact_runs).  RGCN_MERGE_RUNS=0 / False: layout 0
@@ -587,7 +579,6 @@ class RGCNConv(nn.Module):
         n = x.shape[0]
         e = int(edge_type.shape[0])
         tile, chunk = self.layout(n, e)
-        split = self.team_layout and chunk == 128 and self._use_split_producers(chunk)       # plan layout 1 (team placement)
         # the tile-major weight-gradient kernel: 64 x 64 layers with few relations on graphs large enough to fill it
         # (it gathers through buffer descriptors only: above 2^24 rows / 4 GiB the relation-major kernels run)
         from .plan import padded_width
@@ -597,9 +588,8 @@ class RGCNConv(nn.Module):
                     and _lib.buffer_addressable(n, _round4(self.out_channels)))
         # layout 3 only where nothing but rgcn_tile3p_kernel walks the forward / transposed plans: the split kernels unpinned
         # (no kernel flags), d_weight on its own tile-major plan, d_root / d_bias on the plan-free streaming kernel
-        if (not split and self.merge_runs and dw_tiles and self.kernel_flags == 0 and
-                (self._use_split_producers(chunk) or self._exact_merge(chunk))):
-            split = 3
+        split = 3 if (self.merge_runs and dw_tiles and self.kernel_flags == 0 and
+                      (self._use_split_producers(chunk) or self._exact_merge(chunk))) else False
         if self.dist is None:
             paths = self.path if self.path == "auto" else ((self.path, self.path) if isinstance(self.path, str) else tuple(self.path))
             if not x.is_cuda:
@@ -619,13 +609,13 @@ class RGCNConv(nn.Module):
         """whether a plan of ``self.layout`` with that chunk runs on the bf16 x 3 kernel (layout() returns 128-slot chunks for a
         64 x 64 layer with split_producers only where that kernel is the modelled choice, at a tile it has room for)"""
         from .plan import padded_width
-        return (self.split_producers and chunk in (112, 128) and not _ENV_TILE
+        return (self.split_producers and chunk in (112, 128)
                 and padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64)
 
     def _exact_merge(self, chunk: int) -> bool:
         """the exact-fp32 kernel on layout-3 plans: 64 x 64 layers, 128-slot chunks, where the bf16 x 3 kernel is switched off"""
         from .plan import padded_width
-        return (not self.split_producers and self.merge_runs and chunk == 128 and not _ENV_TILE
+        return (not self.split_producers and self.merge_runs and chunk == 128
                 and padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64)
 
     def layout(self, n_nodes: int, n_edges: int) -> Tuple[int, int]:
@@ -633,7 +623,7 @@ class RGCNConv(nn.Module):
         tile where that kernel will run (dist.attach aligns the ranks' node ranges to the same tile), or at the tile that leaves
         the exact-fp32 kernel's chunks room for their shadow row tiles where it will walk layout-3 plans."""
         tile, chunk = layout_for(self.in_channels, self.out_channels, n_nodes, n_edges, self.num_relations)
-        if self._use_split_producers(128) and not _ENV_CHUNK:
+        if self._use_split_producers(128):
             # 64 x 64 with the bf16 x 3 kernel available: its own layout (128-slot chunks, tiles up to 224, its own cycles per chunk
             # and row tile) against the exact-fp32 kernel's, by modelled launch time -- round 4: on a 100k-node / 1M-edge graph the
             # exact model's (400, 64) kept the layer off the faster kernel: 0.416 ms per step replayed against 0.333 at (208, 128)

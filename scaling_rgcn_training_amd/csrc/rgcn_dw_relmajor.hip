@@ -114,11 +114,7 @@ __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
         int relv_pre = ldc(a.chunk_rel, chunk_pre >> a.ushift);
         int unit_next = ldc(a.rel_order, i0 + (nch > 1 ? 1 : 0));
         wg_barrier();
-#ifdef RGCN_STAMPS
-        unsigned long long st_scal = 0, st_comp = 0, st_bar = 0;
-#endif
         for (int it = 0; it < nch; ++it) {
-            STAMP(t0);
             const int buf = it % NBUF;
             const int cnt = cnt_pre;
             const int rel = relv_pre;
@@ -127,7 +123,6 @@ __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
                 relv_pre = ldc(a.chunk_rel, unit_next >> a.ushift);
             }
             unit_next = ldc(a.rel_order, i0 + (it + 2 < nch ? it + 2 : nch - 1));
-            STAMP(t1);
             if (rel != rel_cur) {
                 if (rel_cur >= 0) flush();
                 zero_acc();
@@ -198,26 +193,15 @@ __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
                     }
                 }
             }
-            STAMP(t2);
             wg_barrier();
-            STAMP(t3);
-            STAMP_ADD(st_scal, t0, t1);
-            STAMP_ADD(st_comp, t1, t2);
-            STAMP_ADD(st_bar, t2, t3);
         }
-#ifdef RGCN_STAMPS
-        if (g_stamps && cwv == 0 && lane == 0) {
-            unsigned long long* o = g_stamps + (size_t)blockIdx.x * 32;
-            o[0] = st_scal; o[1] = st_comp; o[2] = 0; o[3] = st_bar;
-        }
-#endif
         if (rel_cur >= 0) flush();
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see rgcn_tile_kernel
     }
     if (wave < kProducerWaves) {
         // The producers' few instructions must not queue behind the consumer wave's MFMAs on the shared SIMD
-        // (issue is arbitrated by priority, then age; an fp32 MFMA holds the pipe 32 cycles): RGCN_PRIO
-        __builtin_amdgcn_s_setprio(RGCN_PRIO);
+        // (kProducerPrio)
+        __builtin_amdgcn_s_setprio(kProducerPrio);
         // producers: wave (k % 4) owns chunk k of this workgroup's range (see rgcn_tile_kernel)
         const int pw = wave;
         int knext = pw;
@@ -247,30 +231,13 @@ __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
             if (k % kProducerWaves == pw && k < nch) issue(k);
         if (pw == 0) wait_vmcnt<0>();
         wg_barrier();
-#ifdef RGCN_STAMPS
-        unsigned long long sp_issue = 0, sp_wait = 0, sp_bar = 0;
-#endif
         for (int it = 0; it < nch; ++it) {
             const int ki = it + D, kw = it + 1;
-            STAMP(p0);
             if (ki % kProducerWaves == pw && ki < nch) issue(ki);
-            STAMP(p1);
             if (kw % kProducerWaves == pw && kw < nch) wait_vmcnt<0>();
-            STAMP(p2);
             wg_barrier();
-            STAMP(p3);
-            STAMP_ADD(sp_issue, p0, p1);
-            STAMP_ADD(sp_wait, p1, p2);
-            STAMP_ADD(sp_bar, p2, p3);
         }
         wait_vmcnt<0>();
-#ifdef RGCN_STAMPS
-        if (g_stamps && lane == 0) {
-            unsigned long long* o = g_stamps + (size_t)blockIdx.x * 32;
-            if (pw == 0) { o[4] = sp_issue; o[5] = sp_wait; o[6] = sp_bar; }
-            if (pw == 1) o[7] = nch;
-        }
-#endif
     }
 }
 
@@ -364,11 +331,7 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
         int unit_next = ldc(a.rel_order, i0 + (nch > 1 ? 1 : 0));
         wg_barrier();   // producers: index vectors landed
         wg_barrier();   // producers: chunk 0 landed
-#ifdef RGCN_STAMPS
-        unsigned long long st_scal = 0, st_comp = 0, st_bar = 0;
-#endif
         for (int it = 0; it < nch; ++it) {
-            STAMP(t0);
             const int buf = it % NBUF;
             const int cnt = cnt_pre;
             const int rel = relv_pre;
@@ -377,7 +340,6 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
                 relv_pre = ldc(a.chunk_rel, unit_next >> a.ushift);
             }
             unit_next = ldc(a.rel_order, i0 + (it + 2 < nch ? it + 2 : nch - 1));
-            STAMP(t1);
             if (rel != rel_cur) {
                 if (rel_cur >= 0) flush();
                 zero_acc();
@@ -426,10 +388,6 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
                 for (int ia = 0; ia < NA; ++ia)
 #pragma unroll
                     for (int jb = 0; jb < NB; ++jb) {
-                        if (RGCN_ABL & 1) {   // diagnostic build: no MFMA
-                            acc[ia][jb][0] += o.a4[ia >> 2][ia & 3] * bv4[jb >> 2][jb & 3];
-                            continue;
-                        }
                         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0"
                                      : "+v"(acc[ia][jb])
                                      : "v"(o.a4[ia >> 2][ia & 3]), "v"(bv4[jb >> 2][jb & 3]));
@@ -475,26 +433,15 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
                     }
                 }
             }
-            STAMP(t2);
             wg_barrier();
-            STAMP(t3);
-            STAMP_ADD(st_scal, t0, t1);
-            STAMP_ADD(st_comp, t1, t2);
-            STAMP_ADD(st_bar, t2, t3);
         }
-#ifdef RGCN_STAMPS
-        if (g_stamps && cwv == 0 && lane == 0) {
-            unsigned long long* o = g_stamps + (size_t)blockIdx.x * 32;
-            o[0] = st_scal; o[1] = st_comp; o[2] = 0; o[3] = st_bar;
-        }
-#endif
         if (rel_cur >= 0) flush();
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): see rgcn_tile_kernel
     }
     if (wave < kProducerWaves) {
         // The producers' few instructions must not queue behind the consumer wave's MFMAs on the shared SIMD
-        // (issue is arbitrated by priority, then age; an fp32 MFMA holds the pipe 32 cycles): RGCN_PRIO
-        __builtin_amdgcn_s_setprio(RGCN_PRIO);
+        // (kProducerPrio)
+        __builtin_amdgcn_s_setprio(kProducerPrio);
         // producers, wide kernel: EVERY producer wave issues a quarter of every chunk (rows 16*pw..+15 of the H
         // and of the G slot), so the DMA-issue instructions are spread over the four SIMDs instead of landing
         // on one of them per chunk (fp32 MFMAs and these vector instructions share a SIMD's pipe: with one
@@ -549,29 +496,12 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
         for (int k = 0; k < D; ++k) step(k);
         wait_ahead();                                           // chunk 0 landed
         wg_barrier();
-#ifdef RGCN_STAMPS
-        unsigned long long sp_issue = 0, sp_wait = 0, sp_bar = 0;
-#endif
         for (int it = 0; it < nch; ++it) {
-            STAMP(p0);
             step(it + D);
-            STAMP(p1);
             wait_ahead();                                       // chunk it+1 landed
-            STAMP(p2);
             wg_barrier();
-            STAMP(p3);
-            STAMP_ADD(sp_issue, p0, p1);
-            STAMP_ADD(sp_wait, p1, p2);
-            STAMP_ADD(sp_bar, p2, p3);
         }
         wait_vmcnt<0>();
-#ifdef RGCN_STAMPS
-        if (g_stamps && lane == 0) {
-            unsigned long long* o = g_stamps + (size_t)blockIdx.x * 32;
-            if (pw == 0) { o[4] = sp_issue; o[5] = sp_wait; o[6] = sp_bar; }
-            if (pw == 1) o[7] = nch;
-        }
-#endif
     }
 }
 
@@ -660,7 +590,7 @@ __global__ void __launch_bounds__(256, 2) rgcn_dw_direct_kernel(const DwArgs a) 
         }
 #pragma unroll
         for (int s = 0; s < HS; ++s) {
-            o.a4[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(__umul24((unsigned)ih[s], rbx) + colb), 0, RGCN_DW_X_AUX));
+            o.a4[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(__umul24((unsigned)ih[s], rbx) + colb), 0, 0));
             o.g4[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rg, (int)(__umul24((unsigned)ig[s], rbg) + colb), 0, 0));
         }
     };
@@ -684,10 +614,6 @@ __global__ void __launch_bounds__(256, 2) rgcn_dw_direct_kernel(const DwArgs a) 
                     for (int ia = 0; ia < 4; ++ia)
 #pragma unroll
                         for (int jb = 0; jb < 4; ++jb) {
-                            if (RGCN_ABL & 1) {   // diagnostic build: no MFMA (memory rate of the walk)
-                                if (jb == 0) acc[ia][0][0] += o.a4[s][ia] * bv[ia];
-                                continue;
-                            }
                             asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0"
                                          : "+v"(acc[ia][jb])
                                          : "v"(o.a4[s][ia]), "v"(bv[jb]));
@@ -850,11 +776,6 @@ static size_t dw_slab_floats(int num_rel, int KP, int NP) {
 
 using namespace rgcn;
 
-#ifdef RGCN_STAMPS
-extern "C" int rgcn_debug_set_stamps_dw(unsigned long long* p) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(rgcn::g_stamps), &p, sizeof(p));
-}
-#endif
 
 extern "C" size_t rgcn_bwd_dw_workspace_bytes(const rgcn_plan_t* plan, int din, int dout) {
     if (plan == nullptr) return 0;

@@ -22,49 +22,10 @@ namespace rgcn {
 // Traffic: x gathers E * 4 * in + four sweeps of g (4 N * 4 * out) + indices = 37 GB instead of 55; one barrier per tile.
 // The root relation and the bias gradient stay with rgcn_dw_direct_kernel (RGCN_FLAG_DW_ROOT_ONLY): their x rows are
 // the tile's own.
-#ifndef RGCN_DW_ABL_NOBARRIER
-#define RGCN_DW_ABL_NOBARRIER 0
-#endif
-#ifndef RGCN_DW_TRUNC
-#define RGCN_DW_TRUNC 0
-#endif
-#ifndef RGCN_DW_ABL
-#define RGCN_DW_ABL 0      // timing-only ablations of rgcn_dw_tile_kernel<true>: 1 cached gathers, 2 no MFMAs, 4 no split arithmetic
-#endif
-#ifndef RGCN_DW_VECTOR_WALK
-#define RGCN_DW_VECTOR_WALK 0
-#endif
-// wave priority raised around the MFMA block of every output-column group (1) or around its vector work (2); 0: none.  Two waves
-// share a SIMD and alternate between cutting operands and multiplying: 7.00 / 7.01 ms (1), 7.01 / 6.99 (2) against 7.08 / 7.06 (0),
-// A/B on one box -- a per cent, kept at 1.  (The two waves of a SIMD at DIFFERENT priorities for the whole launch, so that they
-// fall out of step: 7.0-7.1 ms against 6.76, worse in all three forms tried.)
-#ifndef RGCN_DW_PRIO
-#define RGCN_DW_PRIO 1
-#endif
-#ifndef RGCN_DW_PIPE
-#define RGCN_DW_PIPE 3     // vector instructions issued behind every MFMA of the split form (0: phases, the round-2 form)
-#endif
-#ifndef RGCN_DW_STAGED
-#define RGCN_DW_STAGED 1   // the A pieces cut four pairs at a time, stage by stage
-#endif
-#ifndef RGCN_DW_XCD_MAP
-#define RGCN_DW_XCD_MAP 1
-#endif
-// Diagnostic build only (-DRGCN_DW_STAMPS, tools/debug/dw_stamps.py): per-phase cycle sums of every wave of the split form,
-// written to a buffer no other code reads.  A stamp is s_memtime + lgkmcnt(0): it also waits for the LDS operations in flight.
-#ifdef RGCN_DW_STAMPS
-__device__ unsigned long long* g_dw_stamps = nullptr;
-__device__ __forceinline__ unsigned dw_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return (unsigned)t;
-}
-#define DWS(i) { const unsigned now_ = dw_stamp(); ph[i] += now_ - last_; last_ = now_; }
-#else
-#define DWS(i)
-#endif
+// The split form raises its wave priority around the MFMA block of the output-column groups.  Two waves share a SIMD and
+// alternate between cutting operands and multiplying: 7.00 / 7.01 ms against 7.01 / 6.99 with the priority raised around the
+// vector work instead and 7.08 / 7.06 with none, A/B on one box -- a per cent.  (The two waves of a SIMD at DIFFERENT
+// priorities for the whole launch, so that they fall out of step: 7.0-7.1 ms against 6.76, worse in all three forms tried.)
 constexpr int kDwTileT = 320;                    // gradient rows per LDS buffer = tile size of the plan this kernel walks
 constexpr int kDwTileWalkers = 64;               // tile ranges; x 4 relation quarters = 256 workgroups, one per CU
 constexpr int kDwTileMaxRel = 32;
@@ -81,18 +42,9 @@ constexpr int kDwTileMaxRel = 32;
 //     64 without the sign flip: 2.2e-2 / -1.7e-2 (the flip is worth two orders of magnitude of bias)
 // 128 units (~7K rows): within 1 % of the launch without folds, worst error 0.15 x and bias ~1 x the exact-fp32 form's.
 // The cost is the fold's read-modify-write draining the wave's prefetch queue (16 x {load 16 B, add, store 16 B} per lane);
-// the same fold as 64 no-return global_atomic_add_f32 per lane (RGCN_DW_FOLD_ATOMIC=1, equally deterministic on a private slab)
-// was SLOWER: 6.95 ms at 64 units, 7.31 at 32, 8.33 at 16.
-#ifndef RGCN_DW_FLUSH_UNITS
-#define RGCN_DW_FLUSH_UNITS 128
-#endif
-#ifndef RGCN_DW_FLUSH_SIGNS
-#define RGCN_DW_FLUSH_SIGNS 1
-#endif
-#ifndef RGCN_DW_FOLD_ATOMIC
-#define RGCN_DW_FOLD_ATOMIC 0
-#endif
-constexpr int kDwFlushUnits = RGCN_DW_FLUSH_UNITS;      // 0: one accumulator for the whole launch (round 2 / 3)
+// the same fold as 64 no-return global_atomic_add_f32 per lane (equally deterministic on a private slab) was SLOWER: 6.95 ms
+// at 64 units, 7.31 at 32, 8.33 at 16.  (Rounds 2 and 3 kept one accumulator for the whole launch.)
+constexpr int kDwFlushUnits = 128;
 
 struct DwTileArgs {
     const int* rel_order;   // of a plan with tile = kDwTileT, 64-slot chunks (unit == chunk), layout 0
@@ -128,12 +80,8 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if RGCN_DW_XCD_MAP
     // the four relation quarters of a tile range on ONE XCD (workgroup b runs on XCD b % 8): they stage the same gradient rows
     const int quarter = (blockIdx.x >> 3) & 3, p = (blockIdx.x & 7) | ((blockIdx.x >> 5) << 3);
-#else
-    const int quarter = blockIdx.x & 3, p = blockIdx.x >> 2;
-#endif
     const int rel = 8 * quarter + wave;
     const bool have = rel < a.num_rel;
     const int t0 = (int)((long)p * a.n_tiles / a.walkers), t1 = (int)((long)(p + 1) * a.n_tiles / a.walkers);
@@ -153,10 +101,6 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
     for (int ia = 0; ia < 4; ++ia)
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) acc[ia][jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifdef RGCN_DW_STAMPS
-    unsigned ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned last_ = dw_stamp();
-#endif
 
     // tile t -> LDS buffer b: DMA instruction i moves rows 4 i .. 4 i + 3 (64 lanes x 16 bytes); rows past the end read zeros
     auto dma_tile = [&](int t, int b) {
@@ -186,15 +130,14 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
         int ih[HS];
 #pragma unroll
         for (int s = 0; s < HS; ++s) ih[s] = __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), ix.h);
-        if (RGCN_DW_ABL & 1)       // (timing only: every gather hits rows 0..63 -- no HBM traffic for x)
-#pragma unroll
-            for (int s = 0; s < HS; ++s) ih[s] &= 63;
 #pragma unroll
         for (int s = 0; s < HS; ++s)
             a4[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(__umul24((unsigned)ih[s], rbx) + colb), 0, 0));
     };
     // half a unit: 8 k-steps of 4 rows; gradient rows from the LDS tile (row ids local to the tile, padding clamped: its
     // weight is 0 and every LDS word is a finite number)
+    // nks (the unit's 4-row k-steps) is not used; dropping the argument reschedules the exact-fp32 kernels slightly, so it goes
+    // in a change that is measured on its own
     auto compute_half = [&](f32x4 (&a4)[HS], const f32x4& pair, const Idx& ix, int h, int ngrp, int nks, const float* gbuf, int tile_row0) {
         if constexpr (PAIRS) a4[0] += pair;
         const unsigned loc = (unsigned)(ix.g - tile_row0);
@@ -214,8 +157,7 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
                 for (int t = 0; t < 4; ++t) {
                     const int s = 4 * gi + t;
                     // (cutting a unit's tail at the 4-row k-step instead of the 16-row group -- ~6 % fewer MFMAs -- measured
-                    // 1 % SLOWER: 8.25 against 8.16 ms; the walk is not bound by its MFMA count.  Knob: RGCN_DW_KSTEP_GATE)
-                    if (RGCN_DW_KSTEP_GATE && HS * h + s >= nks) break;
+                    // 1 % SLOWER: 8.25 against 8.16 ms; the walk is not bound by its MFMA count)
                     f32x4 bv = g4[s] * wv[s];
                     asm volatile("s_nop 4" : "+v"(bv));       // VALU write -> asm MFMA operand (see rgcn_dw_direct_kernel)
 #pragma unroll
@@ -228,26 +170,6 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
         }
     };
 
-    // v0, v1 -> three packed bf16 pairs (low half = v0), round-to-nearest pieces: v = h + m + l to 24 bits
-    auto split_pair = [](float v0, float v1, unsigned& h, unsigned& m, unsigned& l) {
-        if (RGCN_DW_ABL & 4) {      // (timing only: no split arithmetic)
-            h = __float_as_uint(v0);
-            m = __float_as_uint(v1);
-            l = h ^ m;
-            return;
-        }
-#if RGCN_DW_TRUNC      // pieces by truncation (v_perm_b32 packs two upper halves; exact as well): measured, see DESIGN.md 4.3
-        auto pk = [](float lo, float hi) { return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u); };
-        auto top = [](float v) { return __uint_as_float(__float_as_uint(v) & 0xFFFF0000u); };
-        h = pk(v0, v1);
-        v0 -= top(v0); v1 -= top(v1);
-        m = pk(v0, v1);
-        v0 -= top(v0); v1 -= top(v1);
-        l = pk(v0, v1);
-        return;
-#endif
-        split3_pair(v0, v1, h, m, l);
-    };
     // half a unit as ONE 32-row k-step (a half with no valid slot is skipped; padding slots inside one have weight 0)
     auto compute_half3 = [&](f32x4 (&a4)[HS], const f32x4& pair, const Idx& ix, int h, int ngrp, const float* gbuf, int tile_row0) {
         if (2 * h >= ngrp) return;      // (ix.w carries the period's sign, see fold_into_slab)
@@ -262,9 +184,7 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
             const int o = __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), goff);
             g4[s] = *(const f32x4*)((const char*)gbuf + o + colb);
         }
-        DWS(2 + 5 * h)       // weights and gradient rows of the half out of LDS
         u32x4 ap[3][4];      // [piece][ia]: 8 bf16 = k index 8 kq + 0..7 of input channel 4 ml + ia
-#if RGCN_DW_STAGED
         // the four pairs of an input channel cut side by side, stage by stage (split3_pair's arithmetic, same pieces): left
         // alone the scheduler emits one dependent chain after the other with a wait state behind every conversion
 #pragma unroll
@@ -290,38 +210,22 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
                 }
             }
         }
-#else
-#pragma unroll
-        for (int ia = 0; ia < 4; ++ia)
-#pragma unroll
-            for (int jp = 0; jp < 4; ++jp) {
-                unsigned h_, m_, l_;
-                split_pair(a4[2 * jp][ia], a4[2 * jp + 1][ia], h_, m_, l_);
-                ap[0][ia][jp] = h_; ap[1][ia][jp] = m_; ap[2][ia][jp] = l_;
-            }
-#endif
-        DWS(3 + 5 * h)       // the x rows have arrived and are cut
         constexpr int pa[6] = {2, 1, 1, 0, 0, 0}, pb[6] = {0, 1, 0, 2, 1, 0};      // small products first
-#if RGCN_DW_PIPE
         // Software pipeline over the four output-column groups: the B pieces of group jb + 1 are cut in the shadow of group jb's
         // 24 MFMAs.  A 16x16x32 bf16 MFMA holds the matrix pipe for 16 cycles = four issue slots, of which it takes one: the
         // other three go to the SAME wave's vector instructions (the second wave of the SIMD does not fill them: its vector
         // phase and this wave's MFMA phase ran one after the other, MFMA time came on top of everything else -- DESIGN.md 4.3).
-        // The order is forced with sched_group_barrier (one MFMA, then up to RGCN_DW_PIPE vector instructions, 24 times);
-        // left alone the scheduler keeps runs of 24 MFMAs.
+        // The order is forced with sched_group_barrier (one MFMA, then up to 3 vector instructions, 24 times); left alone the
+        // scheduler keeps runs of 24 MFMAs.  (The round-2 form cut a group's pieces, then multiplied them, phase after phase.)
         auto cut_b = [&](int jb, u32x4 (&bp)[3]) {
 #pragma unroll
             for (int jp = 0; jp < 4; ++jp) {
                 unsigned h_, m_, l_;
-                if (RGCN_DW_ABL & 8) {      // (timing only: the B side without its cut -- what pieces staged per tile could save at most)
-                    h_ = __float_as_uint(g4[2 * jp][jb]); m_ = __float_as_uint(g4[2 * jp + 1][jb]); l_ = __float_as_uint(wv[2 * jp]) ^ __float_as_uint(wv[2 * jp + 1]);
-                } else
-                split_pair(g4[2 * jp][jb] * wv[2 * jp], g4[2 * jp + 1][jb] * wv[2 * jp + 1], h_, m_, l_);
+                split3_pair(g4[2 * jp][jb] * wv[2 * jp], g4[2 * jp + 1][jb] * wv[2 * jp + 1], h_, m_, l_);
                 bp[0][jp] = h_; bp[1][jp] = m_; bp[2][jp] = l_;
             }
         };
         u32x4 bpp[2][3];
-#if RGCN_DW_STAGED
         {      // group 0 is cut in the open: staged like the A pieces
             float v0[4], v1[4];
             unsigned pc[4];
@@ -344,12 +248,8 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
                 }
             }
         }
-#else
-        cut_b(0, bpp[0]);
-#endif
         __builtin_amdgcn_sched_barrier(0);
-        DWS(4 + 5 * h)       // column group 0 of B cut
-        if (RGCN_DW_PRIO == 1) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
             if (jb < 3) cut_b(jb + 1, bpp[(jb + 1) & 1]);
@@ -363,41 +263,12 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
 #pragma unroll
                 for (int i = 0; i < 24; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, RGCN_DW_PIPE, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (RGCN_DW_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        DWS(5 + 5 * h)       // 96 MFMAs issued, the cuts of groups 1-3 between them
-        return;
-#endif
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb) {
-            u32x4 bp[3];
-#pragma unroll
-            for (int jp = 0; jp < 4; ++jp) {
-                unsigned h_, m_, l_;
-                split_pair(g4[2 * jp][jb] * wv[2 * jp], g4[2 * jp + 1][jb] * wv[2 * jp + 1], h_, m_, l_);
-                bp[0][jp] = h_; bp[1][jp] = m_; bp[2][jp] = l_;
-            }
-            if (RGCN_DW_ABL & 2) {      // (timing only: no MFMAs; the pieces stay alive)
-#pragma unroll
-                for (int ia = 0; ia < 4; ++ia)
-                    asm volatile("" ::"v"(ap[0][ia]), "v"(ap[1][ia]), "v"(ap[2][ia]), "v"(bp[0]), "v"(bp[1]), "v"(bp[2]));
-                continue;
-            }
-            if (RGCN_DW_PRIO == 1) __builtin_amdgcn_s_setprio(3);
-            if (RGCN_DW_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int ia = 0; ia < 4; ++ia)
-                    acc[ia][jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ap[pa[q]][ia]),
-                                                                          __builtin_bit_cast(bf16x8, bp[pb[q]]), acc[ia][jb], 0, 0, 0);
-            if (RGCN_DW_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-            if (RGCN_DW_PRIO == 2) __builtin_amdgcn_s_setprio(3);
-        }
+        __builtin_amdgcn_s_setprio(0);
     };
 
     // The halves are computed under conditions (a half without valid slots is skipped), and loads whose uses all sit in later
@@ -414,18 +285,6 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
     auto fold_into_slab = [&](float sgn) {
         if (!have) return;
         if constexpr (!SPLIT) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#if RGCN_DW_FOLD_ATOMIC
-#pragma unroll
-        for (int ia = 0; ia < 4; ++ia)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int jb = 0; jb < 4; ++jb) {
-                    unsafeAtomicAdd(slab + (4 * (4 * kq + r) + ia) * NP + 4 * ml + jb, sgn * acc[ia][jb][r]);
-                    acc[ia][jb][r] = 0.f;
-                }
-        return;
-#endif
 #pragma unroll
         for (int ia = 0; ia < 4; ++ia)
 #pragma unroll
@@ -445,55 +304,38 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
     // of its walk (at least 16 units) where it is shorter -- there the folds cost nothing that matters and a chain of ~1K rows
     // instead of ~7K keeps the sums as accurate as ATen's blocked ones (tests/test_gpu_parity.py holds 2 x the CPU loop's error)
     // (the exact-fp32 form has no bias to cancel, only chains to keep short: four times the period)
-    const int fold_period = kDwFlushUnits > 0 ? min(SPLIT ? kDwFlushUnits : 4 * kDwFlushUnits, max(16, nun >> 3)) : 0;
+    const int fold_period = min(SPLIT ? kDwFlushUnits : 4 * kDwFlushUnits, max(16, nun >> 3));
     int fold_left = fold_period;
     dma_tile(t0, 0);
     int k = 0;
     int uid_cur = unit_of(0), uid_nxt = unit_of(1), uid_nn = unit_of(2);
     int cnt_cur = ldc(a.chunk_cnt, uid_cur), tile_cur = nun > 0 ? ldc(a.chunk_tile, uid_cur) : t1;
     int cnt_nxt = ldc(a.chunk_cnt, uid_nxt), tile_nxt = nun > 1 ? ldc(a.chunk_tile, uid_nxt) : t1;
-#if RGCN_DW_VECTOR_WALK
-    // Inside the walk the three per-unit words (unit id, slot count, tile) come by VECTOR loads of a uniform address: scalar
-    // loads return out of order, so the first LDS operation of the next unit -- its wait is lgkmcnt(0) -- would wait for the
-    // scalar loads issued a few instructions earlier, a full L2 round trip per unit; vector loads retire in order and are
-    // waited for by count, a whole unit after they were issued.
-    const __amdgpu_buffer_rsrc_t r_ord = make_rsrc(a.rel_order, 0xFFFFFFFCu), r_cnt = make_rsrc(a.chunk_cnt, 0xFFFFFFFCu),
-                                 r_til = make_rsrc(a.chunk_tile, 0xFFFFFFFCu);
-    auto ldv = [](__amdgpu_buffer_rsrc_t r, int idx) { return __builtin_amdgcn_raw_buffer_load_b32(r, idx * 4, 0, 0); };
-#endif
     Idx ix_cur = load_idx(uid_cur), ix_nxt = load_idx(uid_nxt);
     f32x4 s0[HS], s1[HS];
     f32x4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = {0.f, 0.f, 0.f, 0.f};
     if (nun > 0) issue_half(s0, p0, ix_cur, 0);
-    constexpr int kInFlight = (RGCN_DW_VECTOR_WALK ? 14 : 11) + (PAIRS ? 2 : 0);      // 8 (+ 1) row loads + 3 (+ 1) index loads (+ 3 walk words)
+    constexpr int kInFlight = 11 + (PAIRS ? 2 : 0);      // 8 (+ 1) row loads + 3 (+ 1) index loads
     bool walked = nun > 0;      // at least kInFlight vector-memory operations were issued after the pending tile's DMAs
     for (int t = t0; t < t1; ++t) {
         // The DMAs of tile t were issued a tile ago (or in the prologue).  If the wave has walked a unit since (or issued the
         // prologue's loads), more than kInFlight younger operations exist and at most kInFlight are in flight at a unit boundary (8 row
-        // loads + 3 index loads of the unit after next + the walk words): a counted wait retires the DMAs and leaves the prefetches alone.  A wave
+        // loads + 3 index loads of the unit after next): a counted wait retires the DMAs and leaves the prefetches alone.  A wave
         // without units in between (an empty relation) has nothing younger to count: it waits for everything.
-        DWS(12)
         if (walked) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        DWS(13)              // the tile's DMAs
-#if !RGCN_DW_ABL_NOBARRIER      // (timing only: the waves of a workgroup run free -- what the tile lockstep costs)
         wg_barrier();          // tile t landed for every wave; every wave is done with the buffer tile t + 1 goes to
-#endif
-        DWS(14)              // the barrier
         const int b = (t - t0) & 1;
         if (t + 1 < t1) dma_tile(t + 1, b ^ 1);
         walked = false;
-        DWS(15)              // next tile's DMAs issued
         const float* gbuf = lds + b * T * NP;
         while (k < nun && tile_cur == t) {
             const int ngrp = (cnt_cur + 15) >> 4, nks = (cnt_cur + 3) >> 2;
             walked = true;
-            DWS(0)               // (loop overhead, walk words)
             issue_half(s1, p1, ix_cur, 1);
             pin_loads();
             __builtin_amdgcn_sched_barrier(0);
-            DWS(1)               // second half's rows issued
-            if constexpr (SPLIT && kDwFlushUnits > 0 && RGCN_DW_FLUSH_SIGNS) ix_cur.w *= sgn;
+            if constexpr (SPLIT) ix_cur.w *= sgn;
             if constexpr (SPLIT) compute_half3(s0, p0, ix_cur, 0, ngrp, gbuf, t * T);
             else compute_half(s0, p0, ix_cur, 0, ngrp, nks, gbuf, t * T);
             __builtin_amdgcn_sched_barrier(0);
@@ -501,57 +343,30 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
             issue_half(s0, p0, ix_nxt, 0);
             pin_loads();
             __builtin_amdgcn_sched_barrier(0);
-            DWS(6)               // next unit's indices and first-half rows issued
             if constexpr (SPLIT) compute_half3(s1, p1, ix_cur, 1, ngrp, gbuf, t * T);
             else compute_half(s1, p1, ix_cur, 1, ngrp, nks, gbuf, t * T);
             __builtin_amdgcn_sched_barrier(0);
             ++k;
-            if constexpr (kDwFlushUnits > 0) {
-                if (--fold_left == 0) {      // wave-uniform
-                    fold_left = fold_period;
-                    fold_into_slab(sgn);
-                    if (SPLIT && RGCN_DW_FLUSH_SIGNS) sgn = -sgn;
-                }
+            if (--fold_left == 0) {      // wave-uniform
+                fold_left = fold_period;
+                fold_into_slab(sgn);
+                if (SPLIT) sgn = -sgn;
             }
             ix_cur = ix_nxt;
             ix_nxt = ix_nn;
             uid_cur = uid_nxt;
             uid_nxt = uid_nn;
-#if RGCN_DW_VECTOR_WALK
-            uid_nn = ldv(r_ord, i0 + (k + 2 < nun ? k + 2 : nun - 1));
-            cnt_cur = __builtin_amdgcn_readfirstlane(cnt_nxt);
-            tile_cur = k < nun ? __builtin_amdgcn_readfirstlane(tile_nxt) : t1;
-            cnt_nxt = ldv(r_cnt, uid_nxt);
-            tile_nxt = ldv(r_til, uid_nxt);       // (a clamped unit's tile is never looked at: tile_cur = t1 past the end)
-#else
             uid_nn = unit_of(k + 2);
             cnt_cur = cnt_nxt;
             tile_cur = k < nun ? tile_nxt : t1;
             cnt_nxt = ldc(a.chunk_cnt, uid_nxt);
             tile_nxt = k + 1 < nun ? ldc(a.chunk_tile, uid_nxt) : t1;
-#endif
         }
     }
-#ifdef RGCN_DW_STAMPS
-    ph[11] = (unsigned)k;
-    if (g_dw_stamps && lane == 0)
-        for (int i = 0; i < 16; ++i) g_dw_stamps[((size_t)blockIdx.x * 8 + wave) * 16 + i] = ph[i];
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the accumulators are read by plain stores the compiler schedules: keep them clear of the last asm MFMA
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    if constexpr (kDwFlushUnits > 0) {
-        fold_into_slab(sgn);
-        return;
-    }
-    if (have) {
-#pragma unroll
-        for (int ia = 0; ia < 4; ++ia)
-#pragma unroll
-            for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) slab[(4 * (4 * kq + r) + ia) * NP + 4 * ml + jb] = acc[ia][jb][r];
-    }
+    fold_into_slab(sgn);
 }
 
 // walk_ptr[r][p] = first position in rel_order (sorted by (relation, tile)) of a unit of relation r whose tile is
@@ -591,11 +406,6 @@ __global__ void rgcn_dw_tile_reduce_kernel(const float* __restrict__ slabs, int 
 
 using namespace rgcn;
 
-#ifdef RGCN_DW_STAMPS
-extern "C" int rgcn_debug_set_dw_stamps(unsigned long long* p) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_dw_stamps), &p, sizeof(p));
-}
-#endif
 
 extern "C" int rgcn_dw_tiles_geometry(int* tile, int* walkers, int* max_relations) {
     if (tile) *tile = kDwTileT;

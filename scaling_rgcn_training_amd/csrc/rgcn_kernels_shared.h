@@ -1,5 +1,5 @@
-// rgcn_kernels_shared.h -- what the kernel translation units of librgcn_mi355x.so share besides rgcn_common.h: the diagnostic
-// build knobs, the LDS-DMA row gather of the ring kernels, and the host-side argument checks of the C ABI.
+// rgcn_kernels_shared.h -- what the kernel translation units of librgcn_mi355x.so share besides rgcn_common.h: the producer
+// wave priority, the LDS-DMA row gather of the ring kernels, and the host-side argument checks of the C ABI.
 //   rgcn_tile_fp32.hip   rgcn_fwd / rgcn_bwd_dx; the exact-fp32 forward / dX kernel (every width class) is rgcn_tile_fp32_kernel.h,
 //                        instantiated in rgcn_tile_fp32_narrow.hip / _wide.hip
 //   rgcn_tile3p.hip      forward / dX of 64 x 64 layers on bf16 x 3 MFMAs (the default there)
@@ -17,50 +17,9 @@
 
 namespace rgcn {
 
-// Diagnostic build only (-DRGCN_STAMPS, tools/debug/stamps.py): per-segment cycle sums of consumer wave 4
-// and producer wave 0 of every workgroup, written to a buffer no other code reads.  Never in the product .so.
-#ifdef RGCN_STAMPS
-static __device__ unsigned long long* g_stamps = nullptr;     // one copy per translation unit (diagnostic builds only)
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define STAMP(v) const unsigned long long v = stamp()
-#define STAMP_ADD(acc, a, b) acc += (b) - (a)
-#else
-#define STAMP(v)
-#define STAMP_ADD(acc, a, b)
-#endif
-// compile-time ablations for the diagnostic build: 1 no main MFMA, 2 no run-sum MFMA, 4 no accumulator RMW
-#ifndef RGCN_ABL
-#define RGCN_ABL 0
-#endif
-#ifndef RGCN_PRIO
-#define RGCN_PRIO 3
-#endif
-// 1: the Y^T path's 16 MFMAs of a row tile form ONE dependent chain (back-to-back dependent v_mfma_f32_16x16x4_f32 issue at
-// full rate on gfx950), so the accumulate is 2 packed FMAs per tile; 0: two chains folded by 6 FMAs (measured 0.9 % slower)
-#ifndef RGCN_ONE_CHAIN
-#define RGCN_ONE_CHAIN 1
-#endif
-// tile-major dW: cut a unit's tail at the 4-row k-step instead of the 16-row group
-#ifndef RGCN_DW_KSTEP_GATE
-#define RGCN_DW_KSTEP_GATE 0
-#endif
-// cache policy of the direct dW kernel's x-row gathers (aux bits of buffer_load): 0 default, 2 = nt (streamed once)
-#ifndef RGCN_DW_X_AUX
-#define RGCN_DW_X_AUX 0
-#endif
-// run-time ablations of the tile kernel (1 skip MFMA + accumulate, 2 skip DMA, 4 skip B loads): only in diagnostic
-// builds (-DRGCN_DEBUG_KNOBS, set through rgcn_debug_set_mode); the product library has no such switch
-#ifdef RGCN_DEBUG_KNOBS
-#define RGCN_DBG(a) ((a).dbg)
-#else
-#define RGCN_DBG(a) 0
-#endif
+// wave priority (s_setprio) of the producer waves of the fp32 ring kernels: their few instructions must not queue behind the
+// consumer waves' MFMAs on the shared SIMD (issue is arbitrated by priority, then age; an fp32 MFMA holds the pipe 32 cycles)
+constexpr int kProducerPrio = 3;
 
 // ------------------------------------------------------------------------------------------------
 // producers: gather the 64 rows of a chunk into a ring slot by LDS-DMA -- ONE wave per chunk
@@ -214,7 +173,7 @@ template <int KP, int NP>
 constexpr int dw_nbuf() { return (KP == 128 || NP == 128) ? 2 : 4; }
 
 // Tiles one workgroup of rgcn_tile_kernel walks (1..16).  One workgroup fits a CU, so a launch runs in rounds of 256
-// workgroups, and the round count is what the time follows (tools/debug/tpw_sweep.py, forward launch, 28,410 tiles: 16
+// workgroups, and the round count is what the time follows (a sweep of the count, forward launch, 28,410 tiles: 16
 // tiles -> 1,776 workgroups = 7 rounds x 16 = 112 tile times, 10.36 ms; 12 -> 2,368 = 10 rounds x 12 = 120, 11.48 ms;
 // 1 -> 111 rounds, 10.67 ms: a workgroup's start-up costs ~3-4 % of a tile.  2,841 tiles: 12 -> 1 round, 1.11 ms; 8 ->
 // 2 rounds x 8, 1.46 ms).  Pick the count with the least rounds x (tiles + start-up), the larger one on ties.

@@ -22,68 +22,30 @@
 
 namespace rgcn {
 
-// timing-only ablations of diagnostic builds (wrong results): 1 producers load nothing, 2 consumers skip their MFMAs,
-// 4 consumers skip the accumulator read-modify-write, 8 producers skip the split (planes = raw halves)
-#ifndef RGCN_P3_ABL
-#define RGCN_P3_ABL 0
-#endif
-// Diagnostic build only (-DRGCN_P3_STAMPS, tools/debug/p3_stamps.py): per-phase cycle sums of producer wave 0 and consumer
-// wave 4 of every workgroup, written to a buffer no other code reads.
-#ifdef RGCN_P3_STAMPS
-__device__ unsigned long long* g_p3_stamps = nullptr;
-__device__ __forceinline__ unsigned long long p3_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define P3S(v) const unsigned long long v = p3_stamp()
-#define P3A(acc, a, b) acc += (b) - (a)
-#else
-#define P3S(v)
-#define P3A(acc, a, b)
-#endif
 // row tiles whose operands the consumers read ahead of the one they multiply (LDS round trip under load: 300-450 cycles,
 // 12 bf16 MFMAs: ~200).  Round 2 settled on 2; with the consumer waves at priority 3 (their reads go ahead of the producers')
 // and chunks of 4.3 row tiles (layout 3) one tile ahead is as good or better: forward / dX 8.31 / 8.39 ms against 8.40 / 8.42
 // (and 8.59 / 8.56 at 3), 8.70 / 8.64 against 8.76 / 8.72 on layout-0 plans, A/B on one box, bit-identical results
-#ifndef RGCN_P3_LA
-#define RGCN_P3_LA 1
-#endif
-// 0: round-to-nearest pieces (v_cvt_pk_bf16_f32); 1: the producers split by truncation (v_and / v_sub / v_perm_b32: exact too,
-// but measured 0.25 ms per launch SLOWER: 9.94 against 9.67 ms)
-#ifndef RGCN_P3_TRUNC
-#define RGCN_P3_TRUNC 0
-#endif
+constexpr int kP3Lookahead = 1;
+// The producers split into round-to-nearest pieces (v_cvt_pk_bf16_f32).  A split by truncation (v_and / v_sub / v_perm_b32 to
+// pack two upper halves: exact too, every step a full-rate instruction) measured 0.25 ms per launch SLOWER: 9.94 against 9.67 ms.
 // wave priorities (s_setprio 0..3) of the producer / consumer waves: issue is arbitrated by priority, then age.  The consumers are the
 // critical path of a chunk; with priority 3 their LDS and MFMA issue goes ahead of the producer wave on the same SIMD: forward launch
 // 8.87 / 8.87 ms against 9.11 / 8.96 at equal priorities, A/B on one box (producers 3: 9.05 / 9.04; producers 1 + consumers 2: 8.85)
-#ifndef RGCN_P3_PRIO_PROD
-#define RGCN_P3_PRIO_PROD 0
-#endif
-#ifndef RGCN_P3_PRIO_CONS
-#define RGCN_P3_PRIO_CONS 3
-#endif
-// which waves are consumers: 0 = waves 4 .. (one producer and one consumer per SIMD with the one-team kernel: wave i runs on SIMD i % 4);
-// 1 (one-team kernel only) = waves 0, 1, 4, 5 -- the consumers two per SIMD on SIMDs 0 / 1, the producers on SIMDs 2 / 3
-#ifndef RGCN_P3_ROLEMAP
-#define RGCN_P3_ROLEMAP 0
-#endif
-// 1: the consumers drain their LDS queue (s_waitcnt lgkmcnt(0)) in front of EVERY chunk barrier; 0: only where a tile closes.
+constexpr int kP3PrioProducers = 0, kP3PrioConsumers = 3;
+// Waves 0..3 are the producers, waves 4..7 the consumers: one of each per SIMD (wave i runs on SIMD i % 4).  The consumers two
+// per SIMD on two SIMDs and the producers on the other two measured 9.8 ms: the SIMD's issue port is worth spreading over.
+// The consumers drain their LDS queue (s_waitcnt lgkmcnt(0)) in front of EVERY chunk barrier, not only where a tile closes.
 // Per-wave stamps (round 3, profiles/r03a_*) show every consumer wave waiting ~400 cycles per chunk at that barrier with the
 // producers long there -- the drain of its last accumulator stores; without it the same wait moves to the next chunk's first
-// lgkmcnt(0) (scalar metadata): 9.39 / 9.33 ms with, 9.42 / 9.32 without, A/B on one box.  Kept at 1.
-#ifndef RGCN_P3_DRAIN
-#define RGCN_P3_DRAIN 1
-#endif
+// lgkmcnt(0) (scalar metadata): 9.39 / 9.33 ms with, 9.42 / 9.32 without, A/B on one box.
 
 constexpr int kP3Threads = 512;                          // 4 producer + 4 consumer waves
 constexpr int kP3CH = 128;                               // slots of a plan chunk (stride of the plan's slot arrays)
 // Row tiles a ring slot has room for (template parameter ST of the kernel).  8: any 128-slot chunk (48 KiB slots: tiles up to
 // 224).  7 (round 4): plans whose chunks hold at most 112 rows (rgcn_plan.chunk_rows; the shadow row tiles of a layout-3 chunk
 // never reach LDS) -- 42 KiB slots leave the accumulator room for tiles up to 272: 18 % fewer chunks at the headline config.
-// Timing-only builds with clamped chunks (profiles/r04k_*, r04l_*: -DRGCN_P3_SLOT_TILES_EXPERIMENT=6 / 7) priced it first:
+// Timing-only builds with clamped chunks (profiles/r04k_*, r04l_*) priced it first:
 // 7 tiles at T = 272: 7.80 / 7.89 ms against 8.27 / 8.30; 6 tiles at T = 304 / 320: 7.80 / 7.75.
 template <int ST>
 struct P3Geo {
@@ -176,13 +138,7 @@ __device__ __forceinline__ void p3_producer_loop(const TileArgs& a, char* ring, 
 #pragma unroll
         for (int i = 0; i < 8; ++i) idx[i] = __builtin_amdgcn_ds_bpermute((4 * i + rq) * 4, idxv);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (RGCN_P3_ABL & 1) {
-                r.v[i] = f32x4{(float)idx[i], 1.f, 2.f, 3.f};
-                continue;
-            }
-            p3_load_rows(r.v[i], rsrc, __umul24((unsigned)idx[i], rowb) + coff);
-        }
+        for (int i = 0; i < 8; ++i) p3_load_rows(r.v[i], rsrc, __umul24((unsigned)idx[i], rowb) + coff);
     };
     // the ring's metadata: [2][128] pairs {weight, run metadata} -- one 8-byte read per row tile for the consumers.  A wave moves
     // the two words of its OWN 32 rows (lane & 31 <-> row 16 i + 4 pw + rq as for the indices; lanes 0..31 the weight, 32..63 the
@@ -222,34 +178,10 @@ __device__ __forceinline__ void p3_producer_loop(const TileArgs& a, char* ring, 
             const int row = 16 * i + 4 * pw + rq;
             const f32x4 vi = r.v[i];
             float x0 = vi[0], x1 = vi[1], x2 = vi[2], x3 = vi[3];
-            if (RGCN_P3_ABL & 8) {
-                char* p8 = slot + row * 128 + (((c >> 1) ^ ((row >> 1) & 7)) << 4) + ((c & 1) << 3);
-                *(uint2*)p8 = make_uint2(__float_as_uint(x0), __float_as_uint(x1));
-                *(uint2*)(p8 + kP3PlaneBytes) = make_uint2(__float_as_uint(x2), __float_as_uint(x3));
-                *(uint2*)(p8 + 2 * kP3PlaneBytes) = make_uint2(__float_as_uint(x0), __float_as_uint(x3));
-                continue;
-            }
             unsigned h0, h1, m0, m1, l0, l1;
-            if (RGCN_P3_TRUNC) {
-                // split by TRUNCATION: h = the top 8 significant bits of x, m = those of x - h, l = x - h - m (8 bits at most):
-                // x = h + m + l exactly, every step a full-rate instruction (v_and / v_sub / v_perm to pack two upper halves);
-                // v_cvt_pk_bf16_f32 issues at about a third of that rate
-                auto pk = [](float lo, float hi) { return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u); };
-                auto top = [](float v) { return __uint_as_float(__float_as_uint(v) & 0xFFFF0000u); };
-                h0 = pk(x0, x1); h1 = pk(x2, x3);
-                x0 -= top(x0); x1 -= top(x1); x2 -= top(x2); x3 -= top(x3);
-                m0 = pk(x0, x1); m1 = pk(x2, x3);
-                x0 -= top(x0); x1 -= top(x1); x2 -= top(x2); x3 -= top(x3);
-                l0 = pk(x0, x1); l1 = pk(x2, x3);
-            } else {
-                split3_pair(x0, x1, h0, m0, l0);
-                split3_pair(x2, x3, h1, m1, l1);
-            }
+            split3_pair(x0, x1, h0, m0, l0);
+            split3_pair(x2, x3, h1, m1, l1);
             char* p = slot + row * 128 + (((c >> 1) ^ ((row >> 1) & 7)) << 4) + ((c & 1) << 3);
-            if (RGCN_P3_ABL & 32) {      // timing only: no plane stores
-                asm volatile("" ::"v"(h0), "v"(h1), "v"(m0), "v"(m1), "v"(l0), "v"(l1), "v"(p));
-                continue;
-            }
             *(uint2*)p = make_uint2(h0, h1);
             *(uint2*)(p + kP3PlaneBytes) = make_uint2(m0, m1);
             *(uint2*)(p + 2 * kP3PlaneBytes) = make_uint2(l0, l1);
@@ -294,17 +226,11 @@ __device__ __forceinline__ void p3_producer_loop(const TileArgs& a, char* ring, 
     wg_barrier();                                  // chunk 0 (and the accumulator init) visible
     // (batches are issued for chunks past the end too, from clamped addresses: the count of operations in flight stays what
     // the waits assume; two or three redundant batches per tile)
-#ifdef RGCN_P3_STAMPS
-    unsigned long long sp_wait = 0, sp_issue = 0, sp_split = 0, sp_bar = 0;
-#endif
     auto step = [&](int it, P3Rows& tgt, P3Rows& src) {      // tgt = set it % 3, src = set (it + 1) % 3
-        P3S(q0);
         p3_wait_batch<10>(src);
         __builtin_amdgcn_sched_barrier(0);
-        P3S(q1);
         if (it + 1 < nch) issue_batch(tgt, it + 3, src.idx);
         __builtin_amdgcn_sched_barrier(0);
-        P3S(q2);
         const int wd_now = wd_next;
         wd_next = word_of(it + 2);
         if (it + 1 < nch) {
@@ -312,11 +238,8 @@ __device__ __forceinline__ void p3_producer_loop(const TileArgs& a, char* ring, 
             store_meta(src, it + 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        P3S(q3);
         wg_barrier();
         tile_boundary(it);
-        P3S(q4);
-        P3A(sp_wait, q0, q1); P3A(sp_issue, q1, q2); P3A(sp_split, q2, q3); P3A(sp_bar, q3, q4);
     };
     for (int it = 0; it < nch; it += 3) {
         step(it, r0, r1);
@@ -324,34 +247,15 @@ __device__ __forceinline__ void p3_producer_loop(const TileArgs& a, char* ring, 
         if (it + 2 < nch) step(it + 2, r2, r0);
     }
     wait_vmcnt<0>();
-#ifdef RGCN_P3_STAMPS
-    if (g_p3_stamps && lane == 0) {      // every wave: [workgroup][wave 0..11][wait, issue / compute, split / swap, barrier, chunks]
-        unsigned long long* o = g_p3_stamps + ((size_t)blockIdx.x * 12 + pw) * 8;
-        o[0] = sp_wait; o[1] = sp_issue; o[2] = sp_split; o[3] = sp_bar; o[4] = nch;
-    }
-#endif
 }
 
 // ---- the kernel ---------------------------------------------------------------------------------------------------
-// TEAMS: 1 = every consumer wave sees every row tile of a chunk (any plan layout); 2 = two teams of consumer waves, team A on
-//        the first ceil(nt / 2) row tiles of a chunk and team B on the others -- LAYOUT-1 plans only (plan.team_placement: the
-//        two parts of a chunk hold disjoint destinations, so the teams never touch the same accumulator row).
-// NCT:   16-column tiles a consumer wave owns (1: four column owners per team, 2: two).
-// Consumer waves: TEAMS * 4 / NCT (4 or 8) beside the 4 producer waves.
-template <int TEAMS, int NCT>
-struct P3Cfg {
-    static constexpr int kConsumers = TEAMS * 4 / NCT;
-    static constexpr int kThreads = 64 * (4 + kConsumers);
-    static constexpr int kWavesPerSimd = (4 + kConsumers) / 4;
-};
-
-template <int TEAMS, int NCT, int ST>
-__global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, NCT>::kWavesPerSimd)) rgcn_tile3p_kernel(const TileArgs a) {
+// Every consumer wave sees every row tile of a chunk and owns one 16-column tile of the output (any plan layout; layout-1
+// plans run here too -- their placement of a chunk's rows is valid for any walk).
+template <int ST>
+__global__ void __launch_bounds__(kP3Threads, 2) rgcn_tile3p_kernel(const TileArgs a) {
     constexpr int kP3PlaneBytes = P3Geo<ST>::kPlaneBytes, kP3SlotBytes = P3Geo<ST>::kSlotBytes, kP3SlotTiles = ST;
     constexpr int LDO = kP3LDO;
-    constexpr int kThreadsAll = P3Cfg<TEAMS, NCT>::kThreads;
-    constexpr int kConsumers = P3Cfg<TEAMS, NCT>::kConsumers;
-    constexpr int CG = 4 / NCT;                                    // column groups (consumer waves) per team
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* out_lds = lds;                                          // [tile + 1][LDO]  (row `tile`: dummy)
     char* ring = (char*)(lds + (a.tile + 1) * LDO);                // [2][3][128][128 B]
@@ -368,36 +272,30 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
     const int c0 = ldc(a.tile_ptr, tile0);
     const int nch = ldc(a.tile_ptr, tile1) - c0;
 
-    tile_init<LDO>(a, out_lds, tid, kThreadsAll);
+    tile_init<LDO>(a, out_lds, tid, kP3Threads);
 
-    constexpr bool kRoleMap = RGCN_P3_ROLEMAP && kConsumers == 4;
-    const bool is_consumer = kRoleMap ? (wave & 2) == 0 : wave >= 4;
-    const int role_idx = kRoleMap ? ((wave >> 2) * 2 + (wave & 1)) : (wave >= 4 ? wave - 4 : wave);       // cw or pw
-    if (RGCN_P3_PRIO_PROD != 0 || RGCN_P3_PRIO_CONS != 0) {
-        if (is_consumer) __builtin_amdgcn_s_setprio(RGCN_P3_PRIO_CONS);
-        else __builtin_amdgcn_s_setprio(RGCN_P3_PRIO_PROD);
-    }
+    const bool is_consumer = wave >= 4;
+    const int role_idx = wave >= 4 ? wave - 4 : wave;       // cw or pw
+    if (is_consumer) __builtin_amdgcn_s_setprio(kP3PrioConsumers);
+    else __builtin_amdgcn_s_setprio(kP3PrioProducers);
     if (is_consumer) {
-        // ---- consumers: wave cw = (team, column group cg) owns output columns 16 NCT cg .. + 16 NCT - 1 of its team's rows ----
-        const int cw = role_idx;
-        const int team = cw / CG, cg = cw % CG;
+        // ---- consumers: wave cw owns output columns 16 cg .. 16 cg + 15 (cg = cw) ----
+        const int cw = role_idx, cg = cw % 4;
         const int rowl = lane & 15, kq = lane >> 4;
-        const unsigned col4_bytes = (unsigned)(16 * NCT * cg + 4 * kq) * 4u;     // Y^T layout: four consecutive columns of row rowl
-        const unsigned col1_bytes = (unsigned)(16 * NCT * cg + rowl) * 4u;       // Y layout: column rowl of rows 4 kq + i
+        const unsigned col4_bytes = (unsigned)(16 * cg + 4 * kq) * 4u;     // Y^T layout: four consecutive columns of row rowl
+        const unsigned col1_bytes = (unsigned)(16 * cg + rowl) * 4u;       // Y layout: column rowl of rows 4 kq + i
         // W planes of this wave's column tiles: packed3[((((rel * 2 + c) * 3 + pl) * 2 + ct) * 2 + s) * 64 + lane], column
         // 32 c + 16 ct + (lane & 15): fragment (ct, s) of a plane sits 2048 ct + 1024 s bytes behind the plane's first one
-        const int wc = NCT == 1 ? (cg >> 1) : cg, wct0 = NCT == 1 ? (cg & 1) : 0;
+        const int wc = cg >> 1, wct0 = cg & 1;
         const uint4* wp4 = (const uint4*)a.wp + (size_t)(wc * 3 * 2 * 2 + wct0 * 2) * 64 + lane;
         auto wptr = [&](int rel, int pl) { return (const f32x4*)(wp4 + ((size_t)rel * kP3FragsPerRel + pl * 4) * 64); };
-        f32x4 wcur[NCT][3][2], wnext[NCT][3][2];
+        f32x4 wcur[3][2], wnext[3][2];
         int rel_cur = ldc(a.chunk_rel, c0);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                wcur[ct][pl][0] = wptr(rel_cur, pl)[128 * ct];
-                wcur[ct][pl][1] = wptr(rel_cur, pl)[128 * ct + 64];
-            }
+        for (int pl = 0; pl < 3; ++pl) {
+            wcur[pl][0] = wptr(rel_cur, pl)[0];
+            wcur[pl][1] = wptr(rel_cur, pl)[64];
+        }
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): retire these loads in the compiler's scoreboard
         // Per-chunk metadata, one iteration ahead, through scalar BUFFER loads that share one byte offset (rgcn_common.h
         // sbuf_load): iteration `it` fetches chunk it + 1's slot count and flags and chunk it + 3's relation -- three loads and one
@@ -415,12 +313,8 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
         auto prefetch_rel = [&](int rel) {
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
-                prefetch16<0>(wnext[0][pl][0], wptr(rel, pl));
-                prefetch16<1024>(wnext[0][pl][1], wptr(rel, pl));
-                if constexpr (NCT == 2) {
-                    prefetch16<2048>(wnext[1][pl][0], wptr(rel, pl));
-                    prefetch16<3072>(wnext[1][pl][1], wptr(rel, pl));
-                }
+                prefetch16<0>(wnext[pl][0], wptr(rel, pl));
+                prefetch16<1024>(wnext[pl][1], wptr(rel, pl));
             }
         };
         bool pending = rel_n1 != rel_cur;
@@ -428,11 +322,7 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
         int tile_cur = tile0;
         int tend = ldc(a.tile_ptr, tile0 + 1) - c0;     // first chunk (relative) of the next tile
         wg_barrier();
-#ifdef RGCN_P3_STAMPS
-        unsigned long long sc_meta = 0, sc_comp = 0, sc_swap = 0, sc_bar = 0;
-#endif
         for (int it = 0; it < nch; ++it) {
-            P3S(t0s);
             const int chunk = c0 + it;
             const int buf = it & 1;
             const int cnt = ld_cnt;                   // (fetched an iteration ago, waited for behind that iteration's barrier)
@@ -447,30 +337,13 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
             (void)chunk;
             const bool swap_b = pending;
             const int nrt = min(kP3SlotTiles, (cnt + 15) >> 4);
-            // this wave's row tiles of the chunk: [t0, t0 + n)
-            int t0 = 0, n = nrt;
-            bool serial = false;                // a chunk whose parts share a destination: team A takes all of it, tile by tile
-            if constexpr (TEAMS == 2) {
-                const int na = (nrt + 1) >> 1;
-                serial = (flags_all & 256) != 0;
-                if (serial) {
-                    n = team == 0 ? nrt : 0;
-                } else {
-                    t0 = team == 0 ? 0 : na;
-                    n = team == 0 ? na : nrt - na;
-                }
-            }
-            const int flags = (flags_all >> t0) & ((1 << n) - 1);
-#ifdef RGCN_P3_STAMPS
-            asm volatile("" ::"s"(cnt), "s"(rel_next), "s"(flags));
-#endif
-            P3S(t1s);
-            // this lane's operand addresses of its first row tile: plane pl at + pl * 16 KiB, row tile t at + t * 2 KiB (immediates)
+            const int flags = flags_all & ((1 << nrt) - 1);
+            // this lane's operand addresses of row tile 0: plane pl at + pl * 16 KiB, row tile t at + t * 2 KiB (immediates)
             const char* xrow[2];
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                xrow[s] = ring + buf * kP3SlotBytes + t0 * 2048 + rowl * 128 + (((4 * s + kq) ^ ((rowl >> 1) & 7)) << 4);
-            const int2* mb = (const int2*)wring + buf * kP3CH + t0 * 16;          // {weight bits, run metadata} per slot
+                xrow[s] = ring + buf * kP3SlotBytes + rowl * 128 + (((4 * s + kq) ^ ((rowl >> 1) & 7)) << 4);
+            const int2* mb = (const int2*)wring + buf * kP3CH;          // {weight bits, run metadata} per slot
             struct Ops {
                 bf16x8 pl[3][2];    // [plane][k-step]: 8 bf16 of row rowl, k = 32 s + 8 kq + (0..7)
                 float w1;
@@ -483,29 +356,17 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        if (RGCN_P3_ABL & 16) {      // timing only: no operand reads
-                            o.pl[pl][s] = __builtin_bit_cast(bf16x8, f32x4{o.w1, 1.f, 2.f, 3.f});
-                            continue;
-                        }
-                        o.pl[pl][s] = *(const bf16x8*)(xrow[s] + pl * kP3PlaneBytes + t * 2048);
-                    }
+                    for (int s = 0; s < 2; ++s) o.pl[pl][s] = *(const bf16x8*)(xrow[s] + pl * kP3PlaneBytes + t * 2048);
             };
             auto acc_ptr = [&](int d, unsigned col_bytes) -> float* {
                 return (float*)((char*)out_lds + (__umul24((unsigned)d, (unsigned)(LDO * 4)) + col_bytes));
             };
             constexpr int px[6] = {0, 0, 1, 0, 2, 1}, pwl[6] = {0, 1, 0, 2, 0, 1};      // x plane, W plane: hh hm mh hl lh mm
-            // six products of one half (k-step s) of a row tile and column tile ct, Y^T orientation: a lane ends with 4
-            // consecutive columns of a row
-            auto mfma_half = [&](const Ops& o, f32x4 y, int s, int ct) {
+            // six products of one half (k-step s) of a row tile, Y^T orientation: a lane ends with 4 consecutive columns of a row
+            auto mfma_half = [&](const Ops& o, f32x4 y, int s) {
 #pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    if (RGCN_P3_ABL & 2) {
-                        y += __builtin_bit_cast(f32x4, o.pl[px[q]][s]);
-                        continue;
-                    }
-                    y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wcur[ct][pwl[q]][s]), o.pl[px[q]][s], y, 0, 0, 0);
-                }
+                for (int q = 0; q < 6; ++q)
+                    y = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wcur[pwl[q]][s]), o.pl[px[q]][s], y, 0, 0, 0);
                 return y;
             };
             // ---- row tiles without repeated destinations: straight-line, operands LA tiles ahead -----------------------------
@@ -515,9 +376,9 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
             // the same destination at place p + 1 of tile t and place p of tile t + 1.)
             auto consume = [&](auto nrt_c) {
                 constexpr int NRT = decltype(nrt_c)::value;
-                constexpr int LA = RGCN_P3_LA;
+                constexpr int LA = kP3Lookahead;
                 Ops o[NRT];
-                f32x4 y[NRT][NCT], old[NRT][NCT];
+                f32x4 y[NRT], old[NRT];
                 float* dst[NRT];
 #pragma unroll
                 for (int t = 0; t < LA; ++t)
@@ -527,55 +388,34 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
                 for (int step = 0; step <= NRT; ++step) {
                     if (step < NRT) {
                         if (step + LA < NRT) load_ops(o[step + LA], step + LA);
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) y[step][ct] = mfma_half(o[step], f32x4{0.f, 0.f, 0.f, 0.f}, 0, ct);
+                        y[step] = mfma_half(o[step], f32x4{0.f, 0.f, 0.f, 0.f}, 0);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     // one group of vector instructions per tile: store of tile step - 1, then address + accumulator read of
                     // tile step (in this order: consecutive tiles may scatter into the same accumulator row)
-                    if (RGCN_P3_ABL & 4) {
-                        if (step >= 1) asm volatile("" ::"v"(y[step - 1][0]), "v"(y[step - 1][NCT - 1]), "v"(o[step - 1].w1), "v"(o[step - 1].d1));
-                        if (step < NRT)
-#pragma unroll
-                            for (int ct = 0; ct < NCT; ++ct) old[step][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    } else if (step >= 1) {
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct)
-                            *(f32x4*)(dst[step - 1] + 16 * ct) = y[step - 1][ct] * o[step - 1].w1 + old[step - 1][ct];
-                    }
-                    if (step == NRT - 1 && (RGCN_P3_ABL & 128)) {      // timing only: the LAST row tile's accumulator row is not read
+                    if (step >= 1) *(f32x4*)dst[step - 1] = y[step - 1] * o[step - 1].w1 + old[step - 1];
+                    if (step < NRT) {
                         dst[step] = acc_ptr(o[step].d1, col4_bytes);
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) old[step][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    } else if (step < NRT && !(RGCN_P3_ABL & 4)) {
-                        // (RGCN_P3_ABL & 64, timing only, wrong results: the 16 lanes of a phase address rows that differ mod
-                        // 16 -- what a conflict-free accumulator order could buy)
-                        dst[step] = acc_ptr((RGCN_P3_ABL & 64) ? ((o[step].d1 & 0xFFFFF0) | rowl) : o[step].d1, col4_bytes);
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) old[step][ct] = *(const f32x4*)(dst[step] + 16 * ct);
+                        old[step] = *(const f32x4*)dst[step];
                     }
                     if (step < NRT) {
                         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) y[step][ct] = mfma_half(o[step], y[step][ct], 1, ct);
+                        y[step] = mfma_half(o[step], y[step], 1);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
             };
             // ---- tile by tile: chunks with a repeated destination in some row tile (a flagged tile takes the Y orientation
-            // and the run-sum product Z = P Y + old in exact fp32, rgcn_tile_kernel stage B), and serial chunks
+            // and the run-sum product Z = P Y + old in exact fp32, rgcn_tile_kernel stage B)
             auto process_slow = [&](int t, bool dup) {
                 Ops o;
                 load_ops(o, t);
                 if (!dup) {
                     float* d = acc_ptr(o.d1, col4_bytes);
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) {
-                        const f32x4 oldv = *(const f32x4*)(d + 16 * ct);
-                        f32x4 yv = mfma_half(o, f32x4{0.f, 0.f, 0.f, 0.f}, 0, ct);
-                        yv = mfma_half(o, yv, 1, ct);
-                        *(f32x4*)(d + 16 * ct) = yv * o.w1 + oldv;
-                    }
+                    const f32x4 oldv = *(const f32x4*)d;
+                    f32x4 yv = mfma_half(o, f32x4{0.f, 0.f, 0.f, 0.f}, 0);
+                    yv = mfma_half(o, yv, 1);
+                    *(f32x4*)d = yv * o.w1 + oldv;
                     return;
                 }
                 f32x4 w4;
@@ -589,48 +429,44 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
                 float pm[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pm[i] = ((unsigned)d4[i] >> 24) == (unsigned)rowl ? w4[i] : 0.f;
+                f32x4 yv = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    f32x4 yv = {0.f, 0.f, 0.f, 0.f};
+                for (int s = 0; s < 2; ++s)
 #pragma unroll
-                    for (int s = 0; s < 2; ++s)
+                    for (int q = 0; q < 6; ++q)
+                        yv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.pl[px[q]][s], __builtin_bit_cast(bf16x8, wcur[pwl[q]][s]), yv, 0, 0, 0);
+                float* d[4];
+                f32x4 oldv;
 #pragma unroll
-                        for (int q = 0; q < 6; ++q)
-                            yv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o.pl[px[q]][s], __builtin_bit_cast(bf16x8, wcur[ct][pwl[q]][s]), yv, 0, 0, 0);
-                    float* d[4];
-                    f32x4 oldv;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        d[i] = acc_ptr(d4[i], col1_bytes) + 16 * ct;
-                        oldv[i] = *d[i];
-                    }
-                    f32x4 z1 = {0.f, 0.f, 0.f, 0.f};
-                    f32x4 z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[0], yv[0], oldv, 0, 0, 0);
-                    z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[1], yv[1], z1, 0, 0, 0);
-                    z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[2], yv[2], z0, 0, 0, 0);
-                    z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[3], yv[3], z1, 0, 0, 0);
-                    const f32x4 v = z0 + z1;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) *d[i] = v[i];
+                for (int i = 0; i < 4; ++i) {
+                    d[i] = acc_ptr(d4[i], col1_bytes);
+                    oldv[i] = *d[i];
                 }
+                f32x4 z1 = {0.f, 0.f, 0.f, 0.f};
+                f32x4 z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[0], yv[0], oldv, 0, 0, 0);
+                z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[1], yv[1], z1, 0, 0, 0);
+                z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[2], yv[2], z0, 0, 0, 0);
+                z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pm[3], yv[3], z1, 0, 0, 0);
+                const f32x4 v = z0 + z1;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) *d[i] = v[i];
             };
             using std::integral_constant;
-            if (flags == 0 && !serial) {
-                switch (n) {
+            if (flags == 0) {
+                switch (nrt) {
                     case 1: consume(integral_constant<int, 1>{}); break;
                     case 2: consume(integral_constant<int, 2>{}); break;
                     case 3: consume(integral_constant<int, 3>{}); break;
                     case 4: consume(integral_constant<int, 4>{}); break;
-                    case 5: if constexpr (TEAMS == 1) consume(integral_constant<int, 5>{}); break;
-                    case 6: if constexpr (TEAMS == 1) consume(integral_constant<int, 6>{}); break;
-                    case 7: if constexpr (TEAMS == 1) consume(integral_constant<int, 7>{}); break;
-                    case 8: if constexpr (TEAMS == 1 && ST >= 8) consume(integral_constant<int, 8>{}); break;
+                    case 5: consume(integral_constant<int, 5>{}); break;
+                    case 6: consume(integral_constant<int, 6>{}); break;
+                    case 7: consume(integral_constant<int, 7>{}); break;
+                    case 8: if constexpr (ST >= 8) consume(integral_constant<int, 8>{}); break;
                     default: break;
                 }
             } else {
-                for (int t = 0; t < n; ++t) process_slow(t, (flags >> t) & 1);
+                for (int t = 0; t < nrt; ++t) process_slow(t, (flags >> t) & 1);
             }
-            P3S(t2s);
             // (Round 4, tried: the chunk loop unrolled by two with two register sets that trade places, so that these 24 v_mov
             // go.  With the prefetch where it is, the register allocator copies the set right behind the loads -- before they
             // have landed -- wherever a live range is split at the back edge: wrong results.  With the prefetch at the top of
@@ -640,53 +476,39 @@ __global__ void __launch_bounds__((P3Cfg<TEAMS, NCT>::kThreads), (P3Cfg<TEAMS, N
             if (swap_b) {
                 wait_vmcnt<0>();                     // the asm prefetch (this wave's only vector-memory traffic)
 #pragma unroll
-                for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        wcur[ct][pl][0] = wnext[ct][pl][0];
-                        wcur[ct][pl][1] = wnext[ct][pl][1];
-                    }
+                for (int pl = 0; pl < 3; ++pl) {
+                    wcur[pl][0] = wnext[pl][0];
+                    wcur[pl][1] = wnext[pl][1];
+                }
             }
             rel_cur = rel_next;
             pending = it + 2 < nch && rel_next2 != rel_next;
             if (pending) prefetch_rel(rel_next2);
-            P3S(t3s);
             // The barrier that hands the ring slot back.  What it must order is this wave's READS of the slot -- all consumed by
             // MFMAs by now -- not its accumulator stores: those rows are read again only by this wave (LDS operations of a wave
             // execute in order) until the tile closes.  So no lgkmcnt(0) in front of it except where a tile closes and the other
-            // consumer waves read these columns (RGCN_P3_DRAIN=1: always drain, the round-2 behaviour)
-            static_assert(RGCN_P3_DRAIN == 1, "the scalar buffer loads of the next chunk's words share lgkmcnt with the LDS queue");
-            if (RGCN_P3_DRAIN || (it + 1 == tend) || it + 1 == nch) wg_barrier();
-            else asm volatile("s_barrier" ::: "memory");
+            // consumer waves read these columns.  It drains anyway (the round-2 behaviour, measured at the top of this file): the
+            // scalar buffer loads of the next chunk's words share lgkmcnt with the LDS queue.
+            wg_barrier();
             // the words of the next chunk, fetched at the top of this iteration: wg_barrier's lgkmcnt(0) has retired them; the
             // tie keeps every use (and every copy the register allocator makes) behind this point
             sbuf_wait(ld_cnt, ld_flg, ld_rel);
             if (it + 1 == tend && it + 1 < nch) {
                 // this chunk closed a tile: the consumer threads store it and reset the accumulator; the producers wait at
                 // the same extra barrier with the next tile's first chunks already in LDS / in flight
-#ifndef RGCN_P3_ABL_NOEPI     // timing-only build: what a tile boundary costs
                 // (round 4, profiles/r04w_*: the producer waves storing too, or no vmcnt(0) behind the stores: no change -- what is
                 // left of a tile boundary, ~0.26 ms per launch, is the LDS pass, the 2.56 GB of output and two barriers)
-                tile_epilogue<LDO, true>(a, out_lds, tile_cur, cw * 64 + lane, 64 * kConsumers);
-#endif
+                tile_epilogue<LDO, true>(a, out_lds, tile_cur, cw * 64 + lane, 256);
                 ++tile_cur;
                 tend = ldc(a.tile_ptr, tile_cur + 1) - c0;
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): retire the epilogue's memory operations here, once per tile
                 wg_barrier();
             }
-            P3S(t4s);
-            P3A(sc_meta, t0s, t1s); P3A(sc_comp, t1s, t2s); P3A(sc_swap, t2s, t3s); P3A(sc_bar, t3s, t4s);
         }
-#ifdef RGCN_P3_STAMPS
-        if (g_p3_stamps && lane == 0) {
-            unsigned long long* o = g_p3_stamps + ((size_t)blockIdx.x * 12 + 4 + cw) * 8;
-            o[0] = sc_meta; o[1] = sc_comp; o[2] = sc_swap; o[3] = sc_bar; o[4] = nch;
-        }
-#endif
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): nothing of the consumers is pending when the producer code follows
     }
     if (!is_consumer) p3_producer_loop<ST>(a, ring, wring, dring, c0, nch, lane, role_idx, tile0);
-    tile_epilogue<LDO, false>(a, out_lds, tile1 - 1, tid, kThreadsAll);
+    tile_epilogue<LDO, false>(a, out_lds, tile1 - 1, tid, kP3Threads);
 }
 
 // bytes of dynamic LDS at tile size `tile` with ring slots of `st` row tiles
@@ -695,22 +517,13 @@ static size_t p3_lds_bytes(int tile, int st) {
 }
 
 // Launch (called by run_tile in rgcn_tile_fp32.hip when RGCN_FLAG_SPLIT_PRODUCERS is set and the shapes fit): `a.wp` points at
-// the bf16 planes of the packed weights.  Layout-1 plans run the two-team form, layout-0 plans the one-team form.
+// the bf16 planes of the packed weights.  Every plan layout runs the one-team kernel above.
 // Returns RGCN_ERR_LDS / RGCN_ERR_PLAN when it does not apply.
-// The two-team forms are EXPERIMENT builds (tools/debug/build_variant_p3.sh -DRGCN_P3_TEAMS=2 [-DRGCN_P3_NCT=2]): parity-green
-// (tests/test_gpu_parity.py::test_split_producers_kernel_matches_oracle runs whatever form the library was built with on
-// layout-1 plans), not faster -- round 3, forward launch at the headline config on a graph without repeated (dst, relation)
-// pairs, A/B on one box: one team 9.09 ms, two teams x four 16-column owners (8 consumer waves) 9.16, two teams x two
-// 32-column owners (half the operand reads) 9.47; stamps: a consumer's time per row tile grows from 468 to 650-820 cycles
-// when eight waves share the LDS (profiles/r03a_*).  The product library instantiates the one-team kernel only; any
-// placement is valid for it.
-#ifndef RGCN_P3_NCT          // 16-column tiles per consumer wave of the two-team form (1: 8 consumer waves, 2: 4)
-#define RGCN_P3_NCT 1
-#endif
-#ifndef RGCN_P3_TEAMS        // 2: layout-1 plans run the two-team kernel
-#define RGCN_P3_TEAMS 1
-#endif
-template <int TEAMS, int NCT, int ST>
+// Two teams of consumer waves, each on its own part of a layout-1 chunk, were parity-green but not faster -- round 3, forward
+// launch at the headline config on a graph without repeated (dst, relation) pairs, A/B on one box: one team 9.09 ms, two
+// teams x four 16-column owners (8 consumer waves) 9.16, two teams x two 32-column owners (half the operand reads) 9.47;
+// stamps: a consumer's time per row tile grows from 468 to 650-820 cycles when eight waves share the LDS (profiles/r03a_*).
+template <int ST>
 static int launch_tile3p_as(const TileArgs& b, int nwg, size_t lds, hipStream_t stream) {
     static std::atomic<unsigned long long> done{0};
     int dev = 0;
@@ -718,15 +531,15 @@ static int launch_tile3p_as(const TileArgs& b, int nwg, size_t lds, hipStream_t 
     if (e != hipSuccess) return (int)e;
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(done.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute((const void*)rgcn_tile3p_kernel<TEAMS, NCT, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+        e = hipFuncSetAttribute((const void*)rgcn_tile3p_kernel<ST>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
         if (e != hipSuccess) return (int)e;
         done.fetch_or(bit, std::memory_order_release);
     }
-    hipLaunchKernelGGL((rgcn_tile3p_kernel<TEAMS, NCT, ST>), dim3(nwg), dim3(P3Cfg<TEAMS, NCT>::kThreads), lds, stream, b);
+    hipLaunchKernelGGL((rgcn_tile3p_kernel<ST>), dim3(nwg), dim3(kP3Threads), lds, stream, b);
     return (int)hipGetLastError();
 }
 
-int launch_tile3p(const TileArgs& a, int n_tiles, int layout, int chunk_rows, void* stream) {
+int launch_tile3p(const TileArgs& a, int n_tiles, int chunk_rows, void* stream) {
     if (a.x_bytes == 0) return RGCN_ERR_PLAN;          // buffer-descriptor addressing only
     // plans whose chunks hold at most 112 rows run on 42 KiB ring slots (tiles up to 272), any other 128-slot plan on 48 KiB ones
     const int st = chunk_rows > 0 && chunk_rows <= 112 ? 7 : 8;
@@ -737,16 +550,8 @@ int launch_tile3p(const TileArgs& a, int n_tiles, int layout, int chunk_rows, vo
     TileArgs b = a;
     if (n_tiles < 16 * 256) b.tiles_per_wg = 1;
     const int nwg = (n_tiles + b.tiles_per_wg - 1) / b.tiles_per_wg;
-    if constexpr (RGCN_P3_TEAMS == 2)
-        if (layout == 1) return launch_tile3p_as<2, RGCN_P3_NCT, 8>(b, nwg, lds, (hipStream_t)stream);
-    if (st == 7) return launch_tile3p_as<1, 1, 7>(b, nwg, lds, (hipStream_t)stream);
-    return launch_tile3p_as<1, 1, 8>(b, nwg, lds, (hipStream_t)stream);
+    if (st == 7) return launch_tile3p_as<7>(b, nwg, lds, (hipStream_t)stream);
+    return launch_tile3p_as<8>(b, nwg, lds, (hipStream_t)stream);
 }
-
-#ifdef RGCN_P3_STAMPS
-extern "C" int rgcn_debug_set_p3_stamps(unsigned long long* p) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_p3_stamps), &p, sizeof(p));
-}
-#endif
 
 }  // namespace rgcn

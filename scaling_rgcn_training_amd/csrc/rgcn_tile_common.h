@@ -24,7 +24,7 @@ struct TileArgs {
     const float* mask;  // dX only: rows of the layer INPUT when that input is a ReLU output (dx *= mask > 0), or NULL
     int ldm;
     int act;            // forward only: RGCN_ACT_* applied in the tile store
-    int dbg;            // diagnostic builds only (RGCN_DBG)
+    int reserved;       // unused: kept so that the kernel arguments after it keep their offsets (and registers)
     int n_tiles;        // tiles of the plan
     int n_chunks;       // chunks of the plan (bounds of the scalar buffer loads of the per-chunk arrays)
     int merged;         // the plan is layout 3 (runs of equal (destination, relation) compacted: rgcn_plan.hip compact_runs_kernel)
@@ -189,6 +189,6 @@ __device__ __forceinline__ void tile_epilogue(const TileArgs& a, float* out_lds,
 }
 
 // rgcn_tile3p.hip: producer-split bf16 kernel (64 -> 64, 128-slot chunks, buffer-addressable x; layout 1: two consumer teams)
-int launch_tile3p(const TileArgs& a, int n_tiles, int layout, int chunk_rows, void* stream);
+int launch_tile3p(const TileArgs& a, int n_tiles, int chunk_rows, void* stream);
 
 }  // namespace rgcn

@@ -17,9 +17,6 @@ static int dispatch_tile(int KP, int NP, const TileArgs& a, int n_tiles, int chu
     return KP <= 32 ? dispatch_tile_narrow(KP, NP, a, n_tiles, chunk, s) : dispatch_tile_wide(KP, NP, a, n_tiles, chunk, s);
 }
 
-#ifdef RGCN_DEBUG_KNOBS
-static std::atomic<int> g_debug_mode{0};
-#endif
 
 // shared by rgcn_fwd and rgcn_bwd_dx: gather rows of `x` (width kin), scatter into `out` (width nout)
 static int run_tile(const rgcn_plan_t* plan, const float* x, int ldx, int kin, const float* packed, const float* bias,
@@ -61,22 +58,15 @@ static int run_tile(const rgcn_plan_t* plan, const float* x, int ldx, int kin, c
     a.n_chunks = plan->n_chunks;
     a.merged = plan->layout == 3 ? 1 : 0;
     a.tiles_per_wg = tiles_per_workgroup(plan->n_tiles);
-#ifdef RGCN_TPW_ENV        // experiment build only (tools/debug/tpw_sweep.py)
-    if (const char* e = getenv("RGCN_TPW")) a.tiles_per_wg = atoi(e) > 0 ? atoi(e) : a.tiles_per_wg;
-#endif
-#ifdef RGCN_DEBUG_KNOBS
-    a.dbg = g_debug_mode.load();
-#else
-    a.dbg = 0;
-#endif
+    a.reserved = 0;
     const int KP = padded_width(kin), NP = padded_width(nout);
     // Producer-split bf16 x 3 kernel (rgcn_tile3p.hip): 64 x 64 layers, 128-slot chunks, tiles that leave room for its 48 KiB
-    // ring slots (layout-1 plans: two consumer teams); anything else falls through to the kernels below
+    // ring slots (layout-1 plans as well, on the same one-team kernel); anything else falls through to the kernels below
     if ((flags & RGCN_FLAG_SPLIT_PRODUCERS) && !(flags & RGCN_FLAG_EXACT_FP32) && KP == 64 && NP == 64 && plan->chunk == 128 &&
         a.x_bytes != 0) {
         TileArgs b = a;
         b.wp = packed + (size_t)(plan->num_relations + 1) * KP * NP;
-        const int st3 = launch_tile3p(b, plan->n_tiles, plan->layout, plan->chunk_rows, stream);
+        const int st3 = launch_tile3p(b, plan->n_tiles, plan->chunk_rows, stream);
         if (st3 != RGCN_ERR_LDS || plan->layout == 3) return st3;
     }
     // layout 3 (runs of equal (destination, relation) on ONE slot, their other rows in shadow row tiles): besides the kernel above
@@ -89,9 +79,6 @@ static int run_tile(const rgcn_plan_t* plan, const float* x, int ldx, int kin, c
 
 using namespace rgcn;
 
-#ifdef RGCN_DEBUG_KNOBS
-extern "C" void rgcn_debug_set_mode(int mode) { rgcn::g_debug_mode.store(mode); }
-#endif
 
 extern "C" int rgcn_fwd(const rgcn_plan_t* plan, const float* x, int ldx, int din, const float* packed_w,
                         const float* bias, float* out, int ldo, int dout, int act, unsigned flags, void* stream) {

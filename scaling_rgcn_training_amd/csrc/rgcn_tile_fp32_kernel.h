@@ -10,17 +10,12 @@ namespace rgcn {
 // forward / dX kernel
 // ------------------------------------------------------------------------------------------------
 // second launch bound = waves per SIMD the register allocation must allow.  2: one 8-wave workgroup per CU at
-// full register budget; two workgroups per CU (bound 4 = 128 VGPRs, tiles of 160 nodes, RGCN_LDS_KB=80) measured
+// full register budget; two workgroups per CU (bound 4 = 128 VGPRs, tiles of 160 nodes, 80 KiB of LDS) measured
 // no faster (11.5 vs 11.6 ms): the limiter is SIMD issue, not latency
-#ifndef RGCN_TILE_WAVES
-#define RGCN_TILE_WAVES 2
-#endif
-// Producer waves of the tile kernel (experiment knob): 4 = one 8-wave workgroup per CU; 2 = 6-wave workgroups, two per
-// CU when their LDS fits twice (3 waves per SIMD at the full register budget)
-#ifndef RGCN_TILE_PW
-#define RGCN_TILE_PW 4
-#endif
-constexpr int kTileProducers = RGCN_TILE_PW;
+constexpr int kTileWavesPerSimd = 2;
+// Producer waves of the tile kernel: 4 = one 8-wave workgroup per CU (2, 6-wave workgroups two per CU when their LDS fits
+// twice, 3 waves per SIMD at the full register budget, was the alternative)
+constexpr int kTileProducers = 4;
 constexpr int kTileThreads = 64 * (kTileProducers + 4);
 
 // ---- producers of the forward / dX kernels: LDS-DMA gather, D chunks ahead of the consumers -----------------------
@@ -41,16 +36,13 @@ __device__ __forceinline__ void tile_producer_loop(const TileArgs& a, float* rin
         }
     };
         // The producers' few instructions must not queue behind the consumer wave's MFMAs on the shared SIMD
-        // (issue is arbitrated by priority, then age; an fp32 MFMA holds the pipe 32 cycles): RGCN_PRIO
-        __builtin_amdgcn_s_setprio(RGCN_PRIO);
+        // (kProducerPrio)
+        __builtin_amdgcn_s_setprio(kProducerPrio);
         // ---- producers: LDS-DMA gather, D chunks ahead of the consumers; wave (k % 4) owns chunk k ----
         const int pw = wave;
         int knext = pw;                                   // this wave's next chunk
         RowGather<KP, kRowRead, BUF> gather;
-        gather.init(lane, (RGCN_DBG(a) & 2) ? 0 : a.din4, a.ldx);
-#ifdef RGCN_STAMPS
-        unsigned long long sp_issue = 0, sp_wait = 0, sp_bar = 0;
-#endif
+        gather.init(lane, a.din4, a.ldx);
         using Gather = RowGather<KP, kRowRead, BUF>;
         constexpr int RW = CH / kTileProducers;           // rows of a chunk per producer wave in the spread scheme
         if constexpr (D == 1 && RW >= 16 && RW <= 64 && RW % Gather::RPI == 0) {
@@ -153,7 +145,6 @@ __device__ __forceinline__ void tile_producer_loop(const TileArgs& a, float* rin
             srat_cur = srat_nxt;
             wg_barrier();                                 // chunk 0 (and the accumulator init) visible
             for (int it = 0; it < nch; ++it) {
-                STAMP(p0);
                 int idx_next = idx_cur, sidx_next = sidx_cur;
                 if (it + 1 < nch) {
                     issue_part(it + 1, idx_cur, wd_cur, sidx_cur);
@@ -162,19 +153,13 @@ __device__ __forceinline__ void tile_producer_loop(const TileArgs& a, float* rin
                     srat_nxt = load_shadow(a.slot_acc, it + 2);
                     wd_nxt = load_word(it + 2);
                 }
-                STAMP(p1);
                 wait_vmcnt<0>();                          // chunk it + 1 landed
                 if (it + 1 < nch) merge_part(it + 1, wd_cur, srat_cur);
                 idx_cur = idx_next;
                 sidx_cur = sidx_next;
                 wd_cur = wd_nxt;
                 srat_cur = srat_nxt;
-                STAMP(p2);
                 wg_barrier();
-                STAMP(p3);
-                STAMP_ADD(sp_issue, p0, p1);
-                STAMP_ADD(sp_wait, p1, p2);
-                STAMP_ADD(sp_bar, p2, p3);
                 tile_boundary(it);
             }
         } else {
@@ -210,35 +195,21 @@ __device__ __forceinline__ void tile_producer_loop(const TileArgs& a, float* rin
         for (int it = 0; it < nch; ++it) {
             // slot (it+D)%NBUF held chunk it-1, which the consumers finished before the last barrier
             const int ki = it + D, kw = it + 1;
-            STAMP(p0);
             if (ki % kTileProducers == pw && ki < nch) issue(ki);
-            STAMP(p1);
             // a wave has at most ONE chunk in flight (D <= 4), plus the index load issued with it (which
             // hipcc may schedule among the DMAs): vmcnt(0) is exact
             if (kw % kTileProducers == pw && kw < nch) wait_vmcnt<0>();   // chunk it+1 landed
-            STAMP(p2);
             wg_barrier();
-            STAMP(p3);
-            STAMP_ADD(sp_issue, p0, p1);
-            STAMP_ADD(sp_wait, p1, p2);
-            STAMP_ADD(sp_bar, p2, p3);
             tile_boundary(it);
         }
         }
         wait_vmcnt<0>();
-#ifdef RGCN_STAMPS
-        if (g_stamps && lane == 0) {
-            unsigned long long* o = g_stamps + (size_t)blockIdx.x * 32;
-            if (pw == 0) { o[4] = sp_issue; o[5] = sp_wait; o[6] = sp_bar; }
-            if (pw == 1) o[7] = nch;
-        }
-#endif
 }
 
 // CH = edge slots per chunk = rows of one ring slot (64 or 128): a 128-slot chunk is consumed as two 64-row parts
 // with no barrier, metadata fetch or B swap between them
 template <int KP, int NP, int NBUF, bool BUF, int CH>
-__global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kernel(const TileArgs a) {
+__global__ void __launch_bounds__(kTileThreads, kTileWavesPerSimd) rgcn_tile_kernel(const TileArgs a) {
     constexpr int KT = KP / 16, NT = NP / 16;
     constexpr int D = NBUF - 1;                  // chunks the producers run ahead
     static_assert(D >= 1 && D <= kTileProducers, "one chunk in flight per producer wave");
@@ -312,7 +283,7 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
         // LDS-DMAs, so the CU's vector-memory queue is empty and these few loads issue at once.  Issued at the TOP of
         // an iteration -- right behind the barrier, when the producers flood the queue with the next chunk's 32 gathers --
         // every global_load of a consumer wave took hundreds of cycles to ISSUE (~1,000 cycles per chunk, the "fixed cost
-        // that does not scale with the chunk" of the stamp profile; tools/debug/stamps.py).
+        // that does not scale with the chunk" of a cycle-stamp profile).
         constexpr bool kAsmPrefetch = SL * KT <= 4;
         int rel_n1 = nch > 1 ? ldc(a.chunk_rel, c0 + 1) : rel_cur;
         int ld_rel = nch > 2 ? ldc(a.chunk_rel, c0 + 2) : rel_n1;
@@ -329,19 +300,14 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
             }
         };
         bool pending = false;       // bnext is receiving the fragments of chunk it + 1
-        if (kAsmPrefetch && active && rel_n1 != rel_cur && !(RGCN_DBG(a) & 4)) {
+        if (kAsmPrefetch && active && rel_n1 != rel_cur) {
             prefetch_rel(rel_n1);
             pending = true;
         }
         int tile_cur = tile0;
         int tend = ldc(a.tile_ptr, tile0 + 1) - c0;     // first chunk (relative) of the next tile
         wg_barrier();
-#ifdef RGCN_STAMPS
-        unsigned long long st_scal = 0, st_comp = 0, st_bwait = 0, st_bar = 0;
-        unsigned long long st_nrt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
         for (int it = 0; it < nch; ++it) {
-            STAMP(t0);
             const int chunk = c0 + it;
             const int buf = it % NBUF;
             // chunk metadata arrives one iteration ahead (scalar loads issued a whole chunk earlier)
@@ -355,15 +321,11 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
             sbuf_load(ld_rel, rs_rel, moff);
             moff += 4;
             (void)chunk;
-#ifdef RGCN_STAMPS
-            asm volatile("" ::"s"(cnt), "s"(rel_next));
-#endif
-            STAMP(t1);
             // (the asm prefetch must never be spilled before its wait -- hipcc believes the value is there --: only used
             // where the fragment sets fit the register file comfortably; the plain-load form keeps the early prefetch)
-            const bool swap_b = kAsmPrefetch ? pending : (active && rel_next != rel_cur && !(RGCN_DBG(a) & 4));
+            const bool swap_b = kAsmPrefetch ? pending : (active && rel_next != rel_cur);
             if (!kAsmPrefetch && swap_b) prefetch_rel(rel_next);
-            const int nrt_all = (!active || (RGCN_DBG(a) & 1)) ? 0 : (cnt + 15) >> 4;
+            const int nrt_all = !active ? 0 : (cnt + 15) >> 4;
             const int flags_all = flags_chunk & 0xFF;     // bit 8 (layout 1: the chunk's halves share a destination) is not ours
             // A chunk without repeated destinations runs as ONE straight-line block over all its row tiles (up to
             // CH / 16); otherwise 64-row parts of up to four tiles, each on the path its own flags ask for.
@@ -434,49 +396,32 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
             // 4+ issue cycles ON TOP of the MFMA time, plus ~10 cycles per MFMA->VALU->MFMA switch
             // (tools/probes/mfma_f32_overlap.hip: only LDS traffic hides under v_mfma_f32_16x16x4_f32); the Y
             // layout spends 4 b32 reads + 4 b32 writes + 4 addresses + 6 more VALU per slice.
-            // `half` 0 / 1: the first / second 2 KT MFMAs of each chain pair (the accumulate of the PREVIOUS tile is
+            // The 16 MFMAs of a row tile form ONE dependent chain (back-to-back dependent v_mfma_f32_16x16x4_f32 issue at full
+            // rate on gfx950), so the accumulate is 2 packed FMAs per tile; two chains folded by 6 FMAs measured 0.9 % slower.
+            // `half` 0 / 1: the first / second 2 KT MFMAs of the chain (the accumulate of the PREVIOUS tile is
             // issued between the halves, see consume)
             auto stage_a_t = [&](const Ops& o, Tile& t, int half) {
 #pragma unroll
                 for (int s = 0; s < SL; ++s) {
-                    f32x4 acc0 = t.y[s], acc1 = t.z[s];
-                    if (half == 0) acc0 = acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+                    f32x4 acc0 = half == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : t.y[s];
 #pragma unroll
                     for (int m = 0; m < 4 * KT; m += 2) {
                         if ((m < 2 * KT) != (half == 0)) continue;
                         const int j = m >> 2, i = m & 3;
-                        if (RGCN_ABL & 1) {
-                            acc0 += o.av[j];
-                            continue;
-                        }
                         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bcur[s][j][i], o.av[j][i], acc0, 0, 0, 0);
-                        if (RGCN_ONE_CHAIN)
-                            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bcur[s][j][i + 1], o.av[j][i + 1], acc0, 0, 0, 0);
-                        else
-                            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(bcur[s][j][i + 1], o.av[j][i + 1], acc1, 0, 0, 0);
+                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bcur[s][j][i + 1], o.av[j][i + 1], acc0, 0, 0, 0);
                     }
-                    t.y[s] = acc0;      // the two chains are folded in stage C's FMAs
-                    t.z[s] = acc1;
+                    t.y[s] = acc0;
                 }
             };
             auto stage_b_t = [&](const Ops& o, Tile& t) {     // old accumulator contents (after tile t-1's store)
-#if RGCN_ABL & 8
-                // timing-only diagnostic (WRONG results): the 16 lanes of a ds_read_b128 phase address rows that differ
-                // mod 16 -- what a conflict-free accumulator layout could buy
-                t.dst[0] = acc_ptr((o.d1 & 0xFFFFF0) | rowl, lane_col4_bytes);
-#else
                 t.dst[0] = acc_ptr(o.d1, lane_col4_bytes);
-#endif
 #pragma unroll
                 for (int s = 0; s < SL; ++s) t.old[s] = *(const f32x4*)(t.dst[0] + 16 * CW * s);
             };
-            auto stage_c_t = [&](const Ops& o, Tile& t) {     // acc_new = old + w * chain0 + w * chain1
+            auto stage_c_t = [&](const Ops& o, Tile& t) {     // acc_new = old + w * chain
 #pragma unroll
-                for (int s = 0; s < SL; ++s) {
-                    f32x4 v = t.y[s] * o.w1 + t.old[s];
-                    if (!RGCN_ONE_CHAIN) v = t.z[s] * o.w1 + v;
-                    *(f32x4*)(t.dst[0] + 16 * CW * s) = v;
-                }
+                for (int s = 0; s < SL; ++s) *(f32x4*)(t.dst[0] + 16 * CW * s) = t.y[s] * o.w1 + t.old[s];
             };
 
             // ===== chunks with a repeated destination in some row tile: the Y path ===========================
@@ -571,13 +516,7 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
                         // first half of this tile's MFMAs, the next tile's operand reads in between (an LDS
                         // instruction between two MFMAs costs ~2 cycles; in front of the block its full issue slot)
                         if (step + 1 < NRT) {
-                            if (RGCN_ABL & 4) {     // diagnostic: no operand reads after tile 0 (opaque copy: no CSE)
-                                ops[step + 1] = ops[0];
-#pragma unroll
-                                for (int j = 0; j < KT; ++j) asm volatile("" : "+v"(ops[step + 1].av[j]));
-                            } else {
-                                load_ops(ops[step + 1], step + 1, tr_c);
-                            }
+                            load_ops(ops[step + 1], step + 1, tr_c);
                         }
                         if (step < NRT) stage_a_t(ops[step], tl[step], 0);
                         if (step + 1 < NRT) {
@@ -592,12 +531,8 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
                         // tile t-1 (its MFMA results completed during the first half: no pipeline drain) and the
                         // address + accumulator read of tile t (used a whole block later).  Store(t-1) precedes
                         // read(t) in program order: consecutive tiles may hit the same accumulator row.
-                        if (RGCN_ABL & 2) {
-                            if (step >= 1) asm volatile("" ::"v"(tl[step - 1].y[0]), "v"(tl[step - 1].z[0]), "v"(ops[step - 1].w1), "v"(ops[step - 1].d1));
-                        } else {
-                            if (step >= 1) stage_c_t(ops[step - 1], tl[step - 1]);
-                            if (step < NRT) stage_b_t(ops[step], tl[step]);
-                        }
+                        if (step >= 1) stage_c_t(ops[step - 1], tl[step - 1]);
+                        if (step < NRT) stage_b_t(ops[step], tl[step]);
                         __builtin_amdgcn_sched_barrier(0);
                         if (step < NRT) stage_a_t(ops[step], tl[step], 1);
                         __builtin_amdgcn_sched_barrier(0);
@@ -636,26 +571,20 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
             }
             }   // part
             const int nrt = nrt_all;
-            STAMP(t2);
             if (swap_b) {
                 if constexpr (kAsmPrefetch) wait_vmcnt<0>();   // the asm prefetch (this wave's only vector-memory traffic)
 #pragma unroll
                 for (int s = 0; s < SL; ++s)
 #pragma unroll
                     for (int j = 0; j < KT; ++j) bcur[s][j] = bnext[s][j];
-#ifdef RGCN_STAMPS
-                asm volatile("" ::"v"(bcur[0][0][0]), "v"(bcur[SL - 1][KT - 1][3]));
-#endif
             }
             rel_cur = rel_next;
             if constexpr (kAsmPrefetch) {      // fragments of chunk it + 2, issued while the memory queue is idle
-                pending = active && it + 2 < nch && rel_next2 != rel_next && !(RGCN_DBG(a) & 4);
+                pending = active && it + 2 < nch && rel_next2 != rel_next;
                 if (pending) prefetch_rel(rel_next2);
             }
-            STAMP(t3);
             wg_barrier();
             sbuf_wait(ld_cnt, ld_flg, ld_rel);      // the next chunk's words: retired by wg_barrier's lgkmcnt(0); uses stay behind here
-            STAMP(t4);
             if (it + 1 == tend && it + 1 < nch) {
                 // this chunk closed a tile: store it and reset the accumulator (the 256 consumer threads; the producers
                 // wait at the same extra barrier with the next tile's first chunk landed and the second one on its way)
@@ -668,26 +597,7 @@ __global__ void __launch_bounds__(kTileThreads, RGCN_TILE_WAVES) rgcn_tile_kerne
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
                 wg_barrier();
             }
-            STAMP_ADD(st_scal, t0, t1);
-            STAMP_ADD(st_comp, t1, t2);
-            STAMP_ADD(st_bwait, t2, t3);
-            STAMP_ADD(st_bar, t3, t4);
-#ifdef RGCN_STAMPS
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (nrt == i + 1) {
-                    st_nrt[i] += t2 - t1;
-                    st_cnt[i] += 1;
-                }
-#endif
         }
-#ifdef RGCN_STAMPS
-        if (g_stamps && cwv == 0 && lane == 0) {
-            unsigned long long* o = g_stamps + (size_t)blockIdx.x * 32;
-            o[0] = st_scal; o[1] = st_comp; o[2] = st_bwait; o[3] = st_bar;
-            for (int i = 0; i < 8; ++i) { o[8 + i] = st_nrt[i]; o[16 + i] = st_cnt[i]; }
-        }
-#endif
         // tell the waitcnt pass that no consumer load is pending when the producer code (next in program
         // order) reuses these registers; otherwise it waits vmcnt(0) between the prologue DMAs
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)

@@ -13,8 +13,3 @@ int dispatch_tile_narrow(int KP, int NP, const TileArgs& a, int n_tiles, int chu
 
 }  // namespace rgcn
 
-#ifdef RGCN_STAMPS
-extern "C" int rgcn_debug_set_stamps_narrow(unsigned long long* p) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(rgcn::g_stamps), &p, sizeof(p));
-}
-#endif

@@ -32,10 +32,9 @@ without atomics").  Everything here is torch tensor plumbing and runs on CPU or 
 from __future__ import annotations
 
 import functools
+import os as _os
 
 import numpy as np
-from os import environ as _env
-_os_environ_get = _env.get
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Tuple
 
@@ -242,8 +241,10 @@ def build_plan(gather: Tensor, scatter: Tensor, rel: Tensor, w: Tensor, n_nodes:
     chunk_order = torch.sort(order_key, stable=True)[1]
     units = (chunk_order[:, None] * upc + torch.arange(upc, device=dev)[None, :]).reshape(-1)
     used = (chunk_cnt.to(torch.int64)[chunk_order][:, None] > UNIT * torch.arange(upc, device=dev)[None, :]).reshape(-1)
-    rel_order = interleave_walk(units[used], chunk_rel.to(torch.int64)[chunk_order].repeat_interleave(upc)[used],
-                                r1).to(torch.int32)
+    # a dW launch hands every wave one CONTIGUOUS range of this (relation, tile) order: few relation changes = few accumulator
+    # flushes.  (Interleaves that deal a relation's units over the concurrent waves, so that the caches might serve the gathered
+    # upstream-gradient rows, were tried in round 2: no gain)
+    rel_order = units[used].to(torch.int32)
     return TilePlan(n_nodes=n_nodes, node_begin=node_begin, node_end=node_end,
                     num_relations=num_relations, tile=tile, chunk=CHUNK, n_tiles=n_tiles, n_chunks=n_chunks,
                     n_edges=n_edges, tile_ptr=tile_ptr, chunk_rel=chunk_rel, chunk_cnt=chunk_cnt,
@@ -536,58 +537,6 @@ def team_placement(dstl: Tensor, gcnt: Tensor, grp_of_edge: Tensor, rank: Tensor
     return chunk_of_row * C + in_chunk, chunk_cnt, straddle
 
 
-import os as _os
-_WALK_MODE = _os.environ.get("RGCN_WALK", "sorted")   # experiment knob (read once at import): sorted | rr | phase
-DW_WALKERS = 2048   # waves that walk rel_order side by side in the largest dW launch (512 workgroups x 4 waves)
-
-
-def interleave_walk(units: Tensor, unit_rel: Tensor, r1: int, walkers: int = DW_WALKERS, mode: Optional[str] = None) -> Tensor:
-    """Order of the weight-gradient walk.  ``units`` arrive sorted by (relation, tile); a dW launch hands every wave
-    one CONTIGUOUS range of the walk (few relation changes = few accumulator flushes).
-
-    ``sorted`` (the product default) keeps that order.  ``rr`` and ``phase`` are the two interleaves tried in round 2
-    to let L2 / the Infinity Cache serve the gathered upstream-gradient rows (E * 4 * out bytes per launch although
-    only N rows exist: 55 GB moved for a 29 GB job at the headline config): the units of relation r are dealt over the
-    ~``walkers`` concurrent waves so that all of them pass the same tiles at the same point of their walk (``rr``:
-    round-robin over J_r = round(U_r * walkers / n) pieces; ``phase``: exactly aligned with the waves' ranges).
-    Measured (tools/debug/dw_walk_experiment.py, 10M / 100M / 32, 64 -> 64): sorted 9.44 ms, rr 10.00, phase 9.51, and
-    the same with nt loads on the x rows (9.33 / 9.92 / 9.31) -- no gain: ~5.5 TB/s of gathers push 256 MiB through the
-    memory-side cache every ~46 us, i.e. a row survives about four walk steps of the 2,048 waves, while free-running
-    waves drift apart by far more than that.  Relations stay contiguous and ascending in every mode
-    (what the slab reduction relies on); any order inside a relation gives the same sums up to fp32 re-association."""
-    n = int(units.shape[0])
-    if n == 0:
-        return units
-    dev = units.device
-    mode = mode or _WALK_MODE
-    if mode == "sorted":
-        return units
-    cnt = torch.bincount(unit_rel, minlength=r1)                       # U_r
-    start = torch.cumsum(cnt, 0) - cnt                                  # A_r
-    if mode == "phase":
-        # walker w owns positions [w n / walkers, (w + 1) n / walkers): the PHASE of position p is how far into its
-        # walker's range it lies, frac(p * walkers / n) = ((p * walkers) mod n) / n.  Inside a relation the k-th
-        # position in (phase, p) order takes the relation's k-th unit in tile order, so every walker -- also one
-        # that straddles two relations -- passes tile fraction ~phase at the same point of its own walk.
-        p = torch.arange(n, device=dev)
-        phase = (p * walkers) % n
-        o1 = torch.sort(phase, stable=True)[1]
-        o2 = torch.sort(unit_rel[o1], stable=True)[1]
-        pos = o1[o2]                                                    # positions, relation-major, by (phase, p)
-        out = torch.empty_like(units)
-        out[pos] = units
-        return out
-    pieces = torch.clamp((cnt * walkers + n // 2) // n, min=1)          # J_r
-    q = torch.arange(n, device=dev) - start[unit_rel]
-    jr, ur = pieces[unit_rel], cnt[unit_rel]
-    j = q % jr
-    base, rem = ur // jr, ur % jr                                       # the first `rem` pieces hold base + 1 units
-    pos = start[unit_rel] + j * base + torch.minimum(j, rem) + q // jr
-    out = torch.empty_like(units)
-    out[pos] = units
-    return out
-
-
 ROWS_PER_MFMA_TILE = 16
 LDS_BYTES = 160 * 1024
 ACC_PAD = 4    # floats of padding per accumulator row in the tile kernel's LDS tile (bank spread)
@@ -602,7 +551,7 @@ def padded_width(w: int) -> int:
 # (exact fp32: 10.15 ms where the model says 8.6; bf16 x 3: 8.4 ms where its model -- 1,800 cycles per chunk, 420 per row tile,
 # DESIGN.md 8.0f -- says 9.2)
 _KERNEL_MODEL = {"fp32": (800.0, 650.0, 1.18), "bf16x3": (1800.0, 420.0, 0.91)}
-DW_PLAN_LAYOUT = int(_os_environ_get("RGCN_DW_PLAN_LAYOUT", "5"))      # 5: pairs on one slot (round 4); 0: one slot per row
+DW_PLAN_LAYOUT = 5      # pairs on one slot (round 4); layout 0 (one slot per row) stays reachable through _device_plan
 P3_MAX_TILE = 224          # rgcn_tile3p_kernel: two 48 KiB ring slots (any 128-slot chunk) + the fp32 accumulator in 160 KiB
 P3_MAX_TILE_112 = 272      # ... two 42 KiB slots (chunks of at most 112 rows: CHUNK_112)
 
@@ -620,7 +569,7 @@ def _choose_layout(n_nodes: int, n_edges: int, num_relations: int, in_channels: 
     rgcn_tile3p_kernel (64 x 64 layers: 128-slot chunks, tiles up to 224, its own per-chunk / per-row-tile cycles);
     ``with_cost``: also the modelled time of one launch, comparable between the two kernels (conv.RGCNConv.layout picks with it).
 
-    Cost model of the forward / dX kernel, calibrated on the 10M-node / 100M-edge graph (tools/debug/stamps.py): a
+    Cost model of the forward / dX kernel, calibrated on the 10M-node / 100M-edge graph (a cycle-stamp build): a
     chunk costs ~800 cycles whatever it holds (barrier, metadata, pipeline fill and drain) and every 16-row MFMA tile
     ~650 (512 of them MFMA issue).  A (tile, relation) group of g = tile * E / (N R') edges (roughly normal, sd
     sqrt(g)) takes E[ceil(g / chunk)] chunks and ~g / 16 + 1/2 row tiles, so larger tiles and 128-slot chunks
@@ -874,7 +823,7 @@ def build_graph_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_r
                       bwd_range: Optional[Tuple[int, int]] = None, chunk: int = CHUNK,
                       split: bool = False, dw_tiles: bool = False, paths: Tuple[str, str] = ("ring", "ring")) -> GraphPlans:
     """Device tensors: the HIP plan builder behind the C ABI.  CPU tensors (tests without a GPU): the torch form."""
-    if edge_type.device.type == "cuda" and _WALK_MODE == "sorted":
+    if edge_type.device.type == "cuda":
         return build_graph_plans_device(edge_index, edge_type, n_nodes, num_relations, tile, aggr, fwd_range, bwd_range, chunk,
                                         split=split, dw_tiles=dw_tiles, paths=paths)
     return build_graph_plans_torch(edge_index, edge_type, n_nodes, num_relations, tile, aggr, fwd_range, bwd_range, chunk, split,

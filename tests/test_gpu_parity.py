@@ -448,15 +448,15 @@ def test_dw_root_streaming_kernel(dev, rows, din, dout):
     assert torch.equal(dr, dr2) and torch.equal(db, db2)
 
 
-@pytest.mark.parametrize("teams", [False, True], ids=["layout0-one-team", "layout1-two-teams"])
+@pytest.mark.parametrize("teams", [False, True], ids=["layout0-one-team", "layout1"])
 @pytest.mark.parametrize("n,e,r,tile,skew", [(3000, 330000, 3, 224, False), (2000, 200000, 4, 128, True), (5000, 90000, 7, 224, False),
                                              (800, 120000, 2, 64, True), (40, 300, 2, 16, False), (3000, 60000, 40, 224, True)])
 def test_split_producers_kernel_matches_oracle(dev, n, e, r, tile, skew, teams):
     """The bf16 x 3 forward / dX kernel whose PRODUCER waves split the gathered rows (csrc/rgcn_tile3p.hip; 64 x 64, 128-slot
-    chunks, tiles up to 224) in both of its forms -- layout-0 plans: one team of consumer waves; layout-1 plans
-    (plan.team_placement): two teams on the destination-disjoint parts of every chunk.  Hubs and duplicate triples so that
-    row tiles repeat destinations and take the run-sum path and some chunks' parts share a destination (flag 256: one team
-    takes the chunk), chunks of 1 to 8 row tiles (one-tile chunks leave team B idle), a graph of three tiles.  Against the
+    chunks, tiles up to 224) on layout-0 plans and on layout-1 plans (plan.team_placement: the destination-disjoint parts of
+    every chunk), which it walks like any other.  Hubs and duplicate triples so that row tiles repeat destinations and take
+    the run-sum path and some chunks' parts share a destination (flag 256), chunks of 1 to 8 row tiles, a graph of three
+    tiles.  Against the
     float64 oracle under both bounds of oracle/tolerance.py, and against the exact-fp32 kernel on the same plan;
     bit-reproducible."""
     from scaling_rgcn_training_amd import _lib

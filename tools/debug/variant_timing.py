@@ -1,6 +1,9 @@
-"""A/B timing of library variants (tools/debug/build_variant.sh) at the headline size, one subprocess per variant.
+"""A/B timing of two or more builds of the library at the headline size, one subprocess per build.
 
-    python tools/debug/variant_timing.py base onechain ...        (names under scaling_rgcn_training_amd/_build/variants/)
+    python tools/debug/variant_timing.py base candidate ...       (NAME.so under scaling_rgcn_training_amd/_build/variants/)
+
+A variant is a librgcn_mi355x.so built from another commit (for example with tools/build_lib.sh in a checkout of it),
+copied there under a name of its own; each child loads its build through RGCN_LIB.
 
 Per variant: median HIP-event time of the forward launch, the dX launch, the tile-major dW launch and the root-only dW
 pass, plus a checksum of every result so that a variant that changes the numbers shows up next to its time."""
