@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 17
+#define RGCN_ABI_VERSION 18
 #define RGCN_UNIT 64 /* edge slots per unit of the weight-gradient walk (rel_order); a chunk is 1 or 2 units */
 #define RGCN_CHUNK_MAX 128 /* plan->chunk is 64 or 128 edge slots (rows of one LDS ring slot of the forward / dX kernel) */
 #define RGCN_MAX_WIDTH 128
@@ -305,6 +305,30 @@ int rgcn_ep_transform(const rgcn_edge_units_t* units, const float* x, int ldx, i
 int rgcn_ep_segment_sum(const float* in, int ldin, const int32_t* seg_ptr, const int32_t* seg_idx, const float* seg_w, int n_out,
                         int width, const float* bias, int act, const float* mask, int ldm, int final_level, float* out, int ldo,
                         void* stream);
+
+/* ---- featureless layers (scaling_rgcn_training_amd/csrc/rgcn_featureless.hip) -----------------------------------------------
+ * PyG's RGCNConv with x = None or an int64 node-index vector: the weight tables are per-node embeddings,
+ *   out[i] = bias + root[x_i] + sum_{slots j -> i} w_e * W_{rel}[x_j]     (x_index NULL: x_j = j, and in_rows = plan->n_nodes)
+ * weight: full [R', in_rows, dout] (comp NULL, num_bases 0) or bases [B, in_rows, dout] with comp [R', B]: W_r = sum_b comp[r, b] V_b,
+ * composed per gathered row ([R', in_rows, dout] is never formed).  Tables have row stride dout (any dout in 1..128) and are
+ * addressed with 64-bit offsets.  Plans: layout 0 over the whole node range (n_owned = n_nodes), chunk 64 or 128, tile from
+ * rgcn_featureless_geometry; layouts 1 / 2 / 3 / 5 answer RGCN_ERR_PLAN.  x_index values outside [0, in_rows) read zeros (the
+ * Python host refuses them once per index vector).  Deterministic: fixed summation orders, no atomics. */
+/* (tile, chunk) of the featureless plans of a graph of n_nodes nodes; RGCN_ERR_LDS when B bases of that width do not fit */
+int rgcn_featureless_geometry(int32_t n_nodes, int dout, int num_bases, int* tile, int* chunk);
+/* out: [plan->n_nodes, ldo], columns dout .. roundup4(dout) written as zeros; root / bias may be NULL (zeros). */
+int rgcn_featureless_fwd(const rgcn_plan_t* plan, const int64_t* x_index, int64_t in_rows, const float* weight, const float* comp,
+                         int num_bases, const float* root, const float* bias, float* out, int ldo, int dout, void* stream);
+/* Gradients from g [plan_t->n_nodes, ldg] on the TRANSPOSED plan: d_weight [R', in_rows, dout] (every row written, zeros where no
+ * edge gathers it), or with bases d_weight = d_bases [B, in_rows, dout] and d_comp [R', B]; d_root [in_rows, dout]; d_bias [dout].
+ * Any of them may be NULL.  x_index given: inv_ptr [in_rows + 1] / inv_idx [n_nodes] is its inverted index (the node ids sorted by
+ * x value, inv_ptr[v] the first of value v); the per-node rows go through `workspace` and are summed per value in index order.
+ * indexed != 0 in the query: the size for an x_index call. */
+size_t rgcn_featureless_bwd_workspace_bytes(const rgcn_plan_t* plan_t, int dout, int num_bases, int indexed);
+int rgcn_featureless_bwd(const rgcn_plan_t* plan_t, const int64_t* x_index, const int32_t* inv_ptr, const int32_t* inv_idx,
+                         int64_t in_rows, const float* g, int ldg, int dout, const float* weight, const float* comp, int num_bases,
+                         void* workspace, size_t workspace_bytes, float* d_weight, float* d_comp, float* d_root, float* d_bias,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RGCN_LIB: an alternative build of the same library (kernel experiments: tools/debug/)
 LIB_PATH = os.environ.get("RGCN_LIB") or os.path.join(_HERE, "librgcn_mi355x.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 EXPORTS = (
     "rgcn_abi_version", "rgcn_status_string", "rgcn_padded_width", "rgcn_packed_weight_floats",
@@ -23,6 +23,7 @@ EXPORTS = (
     "rgcn_dw_tiles_geometry", "rgcn_dw_tiles_walk", "rgcn_bwd_dw_tiles_workspace_bytes", "rgcn_bwd_dw_tiles",
     "rgcn_bwd_dw_root_workspace_bytes", "rgcn_bwd_dw_root", "rgcn_ep_transform", "rgcn_ep_segment_sum",
     "rgcn_pack_weights_basis", "rgcn_pack_weights_block", "rgcn_basis_backward", "rgcn_block_backward", "rgcn_eplan_segments",
+    "rgcn_featureless_geometry", "rgcn_featureless_fwd", "rgcn_featureless_bwd_workspace_bytes", "rgcn_featureless_bwd",
 )
 
 # enum rgcn_act / RGCN_FLAG_* of include/rgcn_mi355x.h
@@ -138,6 +139,15 @@ def load() -> C.CDLL:
     lib.rgcn_ep_transform.argtypes = [C.POINTER(RgcnEdgeUnits), vp, i32, i32, vp, vp, i32, i32, u32, vp]
     lib.rgcn_ep_segment_sum.restype = i32
     lib.rgcn_ep_segment_sum.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]
+    lib.rgcn_featureless_geometry.restype = i32
+    lib.rgcn_featureless_geometry.argtypes = [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.rgcn_featureless_fwd.restype = i32
+    lib.rgcn_featureless_fwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]
+    lib.rgcn_featureless_bwd_workspace_bytes.restype = sz
+    lib.rgcn_featureless_bwd_workspace_bytes.argtypes = [C.POINTER(RgcnPlanStruct), i32, i32, i32]
+    lib.rgcn_featureless_bwd.restype = i32
+    lib.rgcn_featureless_bwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, vp, vp, i64, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
+                                         vp, vp, vp]
     if lib.rgcn_abi_version() != ABI_VERSION:
         raise RgcnLibraryError(f"ABI version mismatch: library {lib.rgcn_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -482,3 +492,37 @@ def eplan_segments(slot_row: torch.Tensor, n_owned: int):
         check(lib.rgcn_eplan_segments(slot_row.data_ptr(), n_slots, int(n_owned), ws.data_ptr(), ws.numel(), seg_ptr.data_ptr(),
                                       seg_idx.data_ptr(), _stream(slot_row)), "rgcn_eplan_segments")
     return seg_ptr, seg_idx
+
+
+# ---- featureless layers (csrc/rgcn_featureless.hip) -----------------------------------------------------------------
+def featureless_geometry(n_nodes: int, dout: int, num_bases: int):
+    """(tile, chunk) of the featureless plans (rgcn_featureless_geometry)"""
+    tile, chunk = C.c_int(), C.c_int()
+    check(load().rgcn_featureless_geometry(int(n_nodes), int(dout), int(num_bases), C.byref(tile), C.byref(chunk)),
+          "rgcn_featureless_geometry")
+    return tile.value, chunk.value
+
+
+def featureless_fwd(ps: RgcnPlanStruct, x_index: Optional[torch.Tensor], in_rows: int, weight: torch.Tensor,
+                    comp: Optional[torch.Tensor], root: Optional[torch.Tensor], bias: Optional[torch.Tensor], out: torch.Tensor,
+                    dout: int) -> None:
+    nb = 0 if comp is None else int(comp.shape[1])
+    with torch.cuda.device(weight.device):
+        check(load().rgcn_featureless_fwd(C.byref(ps), _ptr(x_index), int(in_rows), weight.data_ptr(), _ptr(comp), nb, _ptr(root),
+                                          _ptr(bias), out.data_ptr(), out.stride(0), int(dout), _stream(weight)), "rgcn_featureless_fwd")
+
+
+def featureless_bwd(ps_t: RgcnPlanStruct, x_index: Optional[torch.Tensor], inv: Optional[tuple], in_rows: int, g: torch.Tensor,
+                    dout: int, weight: torch.Tensor, comp: Optional[torch.Tensor], d_weight, d_comp, d_root, d_bias) -> None:
+    """gradients of rgcn_featureless_fwd on the transposed plan; ``inv`` = (inv_ptr, inv_idx) of an integer x"""
+    lib = load()
+    nb = 0 if comp is None else int(comp.shape[1])
+    nbytes = lib.rgcn_featureless_bwd_workspace_bytes(C.byref(ps_t), int(dout), nb, int(x_index is not None))
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_featureless_bwd_workspace_bytes refused the plan")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+    ip, ii = inv if inv is not None else (None, None)
+    with torch.cuda.device(g.device):
+        check(lib.rgcn_featureless_bwd(C.byref(ps_t), _ptr(x_index), _ptr(ip), _ptr(ii), int(in_rows), g.data_ptr(), g.stride(0),
+                                       int(dout), weight.data_ptr(), _ptr(comp), nb, ws.data_ptr(), nbytes, _ptr(d_weight),
+                                       _ptr(d_comp), _ptr(d_root), _ptr(d_bias), _stream(g)), "rgcn_featureless_bwd")

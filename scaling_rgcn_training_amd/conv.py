@@ -449,6 +449,67 @@ class _RGCNLayerFn(torch.autograd.Function):
         return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None
 
 
+class _FeaturelessFn(torch.autograd.Function):
+    """Featureless layer (x = None or node indices): out = bias + sum over slots of w * W_rel[x_src] (root = rel R'), forward by
+    rgcn_featureless_fwd on the forward plan, every parameter gradient by rgcn_featureless_bwd on the transposed plan.  There
+    is no dX: x is an index."""
+
+    @staticmethod
+    def forward(ctx, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor], plans: GraphPlans,
+                index, in_rows: int, dout: int):
+        n = plans.fwd.n_nodes
+        wf = weight.detach().float().contiguous()
+        cp = None if comp is None else comp.detach().float().contiguous()
+        rt = None if root is None else root.detach().float().contiguous()
+        bs = None if bias is None else bias.detach().float().contiguous()
+        out = torch.empty(n, _round4(dout), dtype=torch.float32, device=wf.device)
+        _lib.featureless_fwd(_lib.plan_struct(plans.fwd), None if index is None else index[0], in_rows, wf, cp, rt, bs, out, dout)
+        ctx.plans, ctx.index, ctx.in_rows, ctx.dout = plans, index, in_rows, dout
+        ctx.has_root, ctx.has_bias = root is not None, bias is not None
+        ctx.save_for_backward(wf, cp)
+        return out if out.shape[1] == dout else out[:, :dout]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        wf, cp = ctx.saved_tensors
+        need_w, need_comp, need_root, need_bias = ctx.needs_input_grad[:4]
+        need_comp = need_comp and cp is not None
+        need_root = need_root and ctx.has_root
+        need_bias = need_bias and ctx.has_bias
+        dout, in_rows, dev = ctx.dout, ctx.in_rows, g.device
+        dw = torch.empty_like(wf) if need_w else None
+        dcomp = torch.empty_like(cp) if need_comp else None
+        droot = torch.empty(in_rows, dout, dtype=torch.float32, device=dev) if need_root else None
+        dbias = torch.empty(dout, dtype=torch.float32, device=dev) if need_bias else None
+        if need_w or need_comp or need_root or need_bias:
+            idx = ctx.index
+            _lib.featureless_bwd(_lib.plan_struct(ctx.plans.bwd), None if idx is None else idx[0], None if idx is None else idx[1:3],
+                                 in_rows, _rows16(g, dout), dout, wf, cp, dw, dcomp, droot, dbias)
+        return dw, dcomp, droot, dbias, None, None, None, None
+
+
+# inverted indices of integer x (featureless layers), keyed on the index tensor's identity like the plan cache: the node ids
+# sorted by x value and where each value starts -- built (and range-checked, one host synchronisation) once per x
+_INDEX_CACHE: dict = {}
+_INDEX_CACHE_MAX = 16
+
+
+def _node_index(x: Tensor, in_rows: int):
+    key = (x.data_ptr(), x._version, tuple(x.shape), x.dtype, str(x.device), in_rows)
+    hit = _INDEX_CACHE.pop(key, None)
+    if hit is None:
+        x64 = x.to(torch.int64).contiguous()
+        if x64.numel() and bool(((x64 < 0) | (x64 >= in_rows)).any()):
+            raise ValueError(f"featureless RGCNConv: node indices must lie in [0, {in_rows})")
+        vals, perm = torch.sort(x64, stable=True)
+        ptr = torch.searchsorted(vals, torch.arange(in_rows + 1, device=x.device, dtype=torch.int64)).to(torch.int32)
+        hit = ((x64, ptr, perm.to(torch.int32)), x)     # (hold x: its storage must not be recycled while cached)
+        while len(_INDEX_CACHE) >= _INDEX_CACHE_MAX:
+            _INDEX_CACHE.pop(next(iter(_INDEX_CACHE)))
+    _INDEX_CACHE[key] = hit
+    return hit[0]
+
+
 def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: Optional[Tensor],
                        plans: GraphPlans, dctx: Optional[DistContext] = None, activation: Optional[str] = None,
                        input_relu: bool = False, grad_premasked: bool = False, flags: int = 0,
@@ -487,15 +548,28 @@ class RGCNConv(nn.Module):
     Parameters (registered in PyG's order): ``weight`` ``[R,in,out]`` (``[B,in,out]`` with
     ``num_bases=B``; ``[R,nb,in/nb,out/nb]`` with ``num_blocks=nb``), ``comp`` ``[R,B]`` or ``None``,
     ``root`` ``[in,out]`` or ``None``, ``bias`` ``[out]`` or ``None``.
+
+    ``featureless=True`` (opt-in): PyG's featureless mode, ``x`` is ``None`` (then N = ``in_channels``) or an int64 ``[N]``
+    node-index tensor and every table ``W_r [in,out]`` is a per-node embedding (``in_channels`` = table rows, any positive
+    int); kernels of ``csrc/rgcn_featureless.hip``.  Not with ``num_blocks`` nor a ``dist`` context.
     """
 
     def __init__(self, in_channels: int, out_channels: int, num_relations: int,
                  num_bases: Optional[int] = None, num_blocks: Optional[int] = None, aggr: str = "mean",
-                 root_weight: bool = True, is_sorted: bool = False, bias: bool = True, **kwargs):
+                 root_weight: bool = True, is_sorted: bool = False, bias: bool = True, featureless: bool = False,
+                 **kwargs):
         super().__init__()
         if num_bases is not None and num_blocks is not None:
             raise ValueError("Can not apply both basis-decomposition and block-diagonal-decomposition "
                              "at the same time.")
+        self.featureless = bool(featureless)
+        if self.featureless:
+            if num_blocks is not None:
+                raise ValueError("Block-diagonal decomposition not supported for non-continuous input features.")
+            if isinstance(in_channels, (tuple, list)) or int(in_channels) != in_channels or in_channels < 1:
+                raise ValueError(f"featureless RGCNConv: in_channels is the number of table rows, got {in_channels!r}")
+            if not 1 <= out_channels <= 128:
+                raise ValueError(f"RGCNConv out_channels must be in 1..128, got {out_channels}")
         if isinstance(in_channels, (tuple, list)):
             if in_channels[0] != in_channels[1]:
                 raise NotImplementedError("bipartite RGCNConv is not used by the reference and not built")
@@ -545,7 +619,8 @@ class RGCNConv(nn.Module):
             self.bias = nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
-        tile_for(in_channels, out_channels)  # validates the widths early
+        if not self.featureless:
+            tile_for(in_channels, out_channels)  # validates the widths early
         self.reset_parameters()
 
     def reset_parameters(self) -> None:
@@ -653,6 +728,8 @@ class RGCNConv(nn.Module):
         ReLU output of the previous layer, so the dX kernel stores dL/dz_prev = dX * (x > 0); ``_grad_premasked`` says
         every consumer of THIS layer's ReLU output does that, so no ReLU backward runs here."""
         assert edge_type is not None, "edge_type is required (PyG RGCNConv asserts the same)"
+        if self.featureless:
+            return self._forward_featureless(x, edge_index, edge_type)
         if x is None or not torch.is_floating_point(x):
             raise NotImplementedError("featureless (integer / None x) RGCNConv is never used by the reference "
                                       "(x is always float: model/layers.py:21,62,108) and is not built")
@@ -669,6 +746,26 @@ class RGCNConv(nn.Module):
         return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, self.dist,
                                   _activation, _input_relu, _grad_premasked and _activation == "relu", flags,
                                   comp=self.comp, num_relations=self.num_relations, out_channels=self.out_channels)
+
+    def _forward_featureless(self, x: Optional[Tensor], edge_index: Tensor, edge_type: Tensor) -> Tensor:
+        if self.dist is not None:
+            raise NotImplementedError("featureless RGCNConv runs on one GPU: a dist context is not supported")
+        if x is not None:
+            if torch.is_floating_point(x) or torch.is_complex(x) or x.dtype == torch.bool:
+                raise ValueError("featureless RGCNConv takes x = None or an integer node-index tensor, not float features")
+            if x.dim() != 1:
+                raise ValueError(f"featureless RGCNConv: x must be a [N] node-index tensor, got {tuple(x.shape)}")
+        if edge_index.device.type != "cuda" or (x is not None and x.device.type != "cuda"):
+            raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+        _lib.load()
+        n = self.in_channels if x is None else int(x.shape[0])
+        index = None if x is None else _node_index(x, self.in_channels)
+        nb = 0 if self.num_bases is None else int(self.num_bases)
+        tile, chunk = _lib.featureless_geometry(max(n, 1), self.out_channels, nb)
+        plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, split=False,
+                                   dw_tiles=False, paths=("ring", "ring"), extra_key=("featureless",))
+        return _FeaturelessFn.apply(self.weight, self.comp, self.root, self.bias, plans, index, self.in_channels,
+                                    self.out_channels)
 
     def __repr__(self) -> str:
         return (f"{self.__class__.__name__}({self.in_channels}, {self.out_channels}, "
