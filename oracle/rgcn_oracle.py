@@ -197,6 +197,81 @@ def rgcn_conv_segments(x, edge_index, edge_type, w_full, root, bias, dout=None, 
     return out, grads
 
 
+
+# --------------------------------------------------------------------------------------
+# Featureless layers (x = None or node indices): sparse float64, O(E * out) memory
+# --------------------------------------------------------------------------------------
+def featureless_reference(x_index, edge_index, edge_type, weight, comp, root, bias, g, aggr: str = "mean",
+                          dense: bool = True):
+    """PyG's featureless RGCNConv -- out[i] = bias + root[x_i] + sum_{j -> i in r} w_e W_r[x_j], W_r = weight[r] or
+    sum_b comp[r, b] weight[b] -- and its parameter gradients for the output gradient ``g``, in float64 by gathers and
+    index_add_ over the edges (x_index None: x_j = j).  Mean: w_e = 1 / count(dst, rel), duplicates counted.
+
+    Returns (ref, cond): two dicts with "out", "weight" (d_weight, or d_bases with bases), "comp" (bases only), "root" and
+    "bias" as float64 tensors, ``cond`` the same quantities evaluated on absolute values (oracle/tolerance.assert_close's
+    condition).  ``dense=False``: "weight" holds only the rows of the [T * in_rows, out] gradient table that an edge gathers,
+    "weight_rows" their flat row ids (ascending); every other row of the gradient is zero."""
+    ref = _featureless_eval(x_index, edge_index, edge_type, weight, comp, root, bias, g, aggr, dense, False)
+    cond = _featureless_eval(x_index, edge_index, edge_type, weight, comp, root, bias, g, aggr, dense, True)
+    return ref, cond
+
+
+def _featureless_eval(x_index, edge_index, edge_type, weight, comp, root, bias, g, aggr, dense, absolute):
+    # tables are gathered first and converted after: a [R, in_rows, out] table is never copied whole
+    f64 = (lambda t: t.double().abs()) if absolute else (lambda t: t.double())
+    cpu = lambda t: None if t is None else torch.as_tensor(t).detach().cpu()
+    w, rt = cpu(weight), cpu(root)
+    cp, bs, gg = (None if t is None else f64(cpu(t)) for t in (comp, bias, g))
+    ei = torch.as_tensor(edge_index).cpu().long()
+    typ = torch.as_tensor(edge_type).cpu().long()
+    src, dst = ei[0], ei[1]
+    n, dout = gg.shape
+    in_rows = w.shape[1]
+    num_rel = w.shape[0] if cp is None else cp.shape[0]
+    xi = None if x_index is None else torch.as_tensor(x_index).cpu().long()
+    xs = src if xi is None else xi[src]                  # table row each edge gathers
+    if aggr == "mean":
+        key = dst * num_rel + typ
+        cnt = torch.zeros(n * num_rel, dtype=torch.float64).index_add_(0, key, torch.ones(len(key), dtype=torch.float64))
+        ew = 1.0 / cnt[key]
+    elif aggr in ("sum", "add"):
+        ew = torch.ones(len(dst), dtype=torch.float64)
+    else:
+        raise ValueError(aggr)
+    if cp is None:
+        rows = f64(w[typ, xs])                                               # [E, out]
+    else:
+        vx = f64(w[:, xs])                                                   # [B, E, out]
+        rows = torch.einsum("eb,beo->eo", cp[typ], vx)                       # composed per edge
+    out = torch.zeros(n, dout, dtype=torch.float64).index_add_(0, dst, ew[:, None] * rows)
+    xn = torch.arange(n) if xi is None else xi
+    if rt is not None:
+        out += f64(rt[xn])
+    if bs is not None:
+        out += bs[None, :]
+    ge = ew[:, None] * gg[dst]                                               # [E, out]: what each gathered row receives
+    res = {"out": out, "bias": gg.sum(0)}
+    if rt is not None:
+        res["root"] = torch.zeros(in_rows, dout, dtype=torch.float64).index_add_(0, xn, gg)
+    if cp is None:
+        k, v, tabs = typ * in_rows + xs, ge, num_rel
+    else:
+        nb = w.shape[0]
+        k = torch.cat([b * in_rows + xs for b in range(nb)])
+        v = torch.cat([cp[typ, b, None] * ge for b in range(nb)])
+        tabs = nb
+        # d_comp[r, b] = sum over edges of relation r of < w_e g[dst], V_b[x_src] >
+        dots = torch.einsum("eo,beo->eb", ge, vx)
+        res["comp"] = torch.zeros(num_rel, nb, dtype=torch.float64).index_add_(0, typ, dots)
+    if dense:
+        res["weight"] = torch.zeros(tabs * in_rows, dout, dtype=torch.float64).index_add_(0, k, v).view(tabs, in_rows, dout)
+    else:
+        uk, inv = torch.unique(k, return_inverse=True)
+        res["weight"] = torch.zeros(len(uk), dout, dtype=torch.float64).index_add_(0, inv, v)
+        res["weight_rows"] = uk
+    return res
+
+
 # --------------------------------------------------------------------------------------
 # Parameter init as the reference does it (SURVEY.md 8a row a1)
 # --------------------------------------------------------------------------------------

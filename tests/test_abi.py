@@ -88,7 +88,9 @@ def test_binding_constants_match_the_header():
 # ---- plan refusals: header fields a kernel cannot walk are answered RGCN_ERR_PLAN before anything touches a device ------------
 # Every plan-taking entry point validates the plan before check_device, so these calls stop at an argument check that follows:
 # rgcn_fwd / rgcn_bwd_dx get x = NULL (an accepted plan answers RGCN_ERR_NULL), the weight-gradient entry points a workspace of
-# 0 bytes (RGCN_ERR_WORKSPACE); a refused plan answers RGCN_ERR_PLAN.  Nothing is ever launched, on any machine.
+# 0 bytes (RGCN_ERR_WORKSPACE), rgcn_featureless_fwd a 128-wide output whose accumulator does not fit tile 320 in LDS
+# (RGCN_ERR_LDS), rgcn_featureless_bwd a workspace of 0 bytes; a refused plan answers RGCN_ERR_PLAN.  Nothing is ever launched,
+# on any machine.
 _DUMMY = (ctypes.c_int32 * 64)()       # plan arrays: host memory the argument checks see as non-NULL and never read
 
 
@@ -100,7 +102,7 @@ def _plan(layout, chunk, chunk_rows, tile=320):
 
 
 def _calls(ps):
-    """status of the four plan-taking entry points on plan `ps` (no device memory, no launch)"""
+    """status of the six plan-taking entry points on plan `ps` (no device memory, no launch)"""
     lib = _lib.load()
     b, d = ctypes.byref(ps), ctypes.addressof(_DUMMY)
     return {
@@ -108,19 +110,24 @@ def _calls(ps):
         "bwd_dx": lib.rgcn_bwd_dx(b, None, 64, 64, d, d, 64, 64, None, 0, 0, None),
         "bwd_dw": lib.rgcn_bwd_dw(b, d, 64, 64, d, 64, 64, d, 0, d, d, d, 0, None),
         "bwd_dw_tiles": lib.rgcn_bwd_dw_tiles(b, d, d, 64, 64, d, 64, 64, d, 0, d, 0, None),
+        "featureless_fwd": lib.rgcn_featureless_fwd(b, None, ps.n_nodes, d, None, 0, None, None, d, 128, 128, None),
+        "featureless_bwd": lib.rgcn_featureless_bwd(b, None, None, None, ps.n_nodes, d, 16, 16, d, None, 0, d, 0, d, None, None,
+                                                    None, None),
     }
 
 
-PLAN, NULL, WS = -4, -1, -6
-# (layout, chunk, chunk_rows) -> status of fwd, bwd_dx, bwd_dw, bwd_dw_tiles (tile 320: the tile-major d_weight geometry);
-# NULL / WS: the plan passed (the call stopped at the argument check after it), PLAN: refused
+PLAN, NULL, WS, LDS = -4, -1, -6, -5
+# (layout, chunk, chunk_rows) -> status of fwd, bwd_dx, bwd_dw, bwd_dw_tiles, featureless_fwd, featureless_bwd (tile 320: the
+# tile-major d_weight geometry); NULL / WS / LDS: the plan passed (the call stopped at the argument check after it), PLAN: refused.
+# The featureless kernels walk layout 0 only.
 ACCEPTED = {
-    (0, 64, 64): (NULL, NULL, WS, WS), (0, 64, 0): (NULL, NULL, WS, WS),
-    (0, 128, 128): (NULL, NULL, WS, PLAN), (0, 128, 112): (NULL, NULL, WS, PLAN), (0, 128, 0): (NULL, NULL, WS, PLAN),
-    (1, 128, 128): (NULL, NULL, WS, PLAN),
-    (2, 64, 64): (PLAN, PLAN, WS, PLAN),
-    (3, 128, 128): (NULL, NULL, PLAN, PLAN), (3, 128, 112): (NULL, NULL, PLAN, PLAN),
-    (5, 64, 64): (PLAN, PLAN, PLAN, WS),
+    (0, 64, 64): (NULL, NULL, WS, WS, LDS, WS), (0, 64, 0): (NULL, NULL, WS, WS, LDS, WS),
+    (0, 128, 128): (NULL, NULL, WS, PLAN, LDS, WS), (0, 128, 112): (NULL, NULL, WS, PLAN, LDS, WS),
+    (0, 128, 0): (NULL, NULL, WS, PLAN, LDS, WS),
+    (1, 128, 128): (NULL, NULL, WS, PLAN, PLAN, PLAN),
+    (2, 64, 64): (PLAN, PLAN, WS, PLAN, PLAN, PLAN),
+    (3, 128, 128): (NULL, NULL, PLAN, PLAN, PLAN, PLAN), (3, 128, 112): (NULL, NULL, PLAN, PLAN, PLAN, PLAN),
+    (5, 64, 64): (PLAN, PLAN, PLAN, WS, PLAN, PLAN),
 }
 
 
@@ -157,3 +164,103 @@ def test_workspace_one_byte_short_is_refused():
     assert lib.rgcn_bwd_dw(ctypes.byref(ps), d, 64, 64, d, 64, 64, d, need - 1, d, d, d, 0, None) == -6
     need_t = lib.rgcn_bwd_dw_tiles_workspace_bytes(3)
     assert lib.rgcn_bwd_dw_tiles(ctypes.byref(ps), d, d, 64, 64, d, 64, 64, d, need_t - 1, d, 0, None) == -6
+
+
+def test_featureless_plans_must_cover_every_node():
+    """slot_row is the node id only when the plan owns the whole node range: a partitioned plan is refused"""
+    ps = _plan(0, 64, 64)
+    assert _calls(ps)["featureless_fwd"] == LDS
+    ps.n_owned = 900
+    st = _calls(ps)
+    assert st["featureless_fwd"] == PLAN and st["featureless_bwd"] == PLAN
+    assert _lib.load().rgcn_featureless_bwd_workspace_bytes(ctypes.byref(ps), 16, 0, 0) == 0
+
+
+WIDTH, STRIDE = -2, -3
+
+
+def test_featureless_argument_refusals():
+    """every refusal of rgcn_featureless_fwd / _bwd on an accepted plan (layout 0, tile 16), before anything touches a device"""
+    lib = _lib.load()
+    d = ctypes.addressof(_DUMMY)
+    ps = _plan(0, 64, 64, tile=16)
+    ps.n_tiles = (ps.n_nodes + 15) // 16
+    ps.n_chunks = ps.n_units = ps.n_tiles
+    b, n = ctypes.byref(ps), ps.n_nodes
+
+    def fwd(x=None, in_rows=n, w=d, comp=None, nb=0, out=d, ldo=16, dout=16):
+        return lib.rgcn_featureless_fwd(b, x, in_rows, w, comp, nb, None, None, out, ldo, dout, None)
+
+    def bwd(x=None, ip=None, ii=None, in_rows=n, g=d, ldg=16, dout=16, w=d, comp=None, nb=0, ws=d, nbytes=0, dw=d, dc=None):
+        return lib.rgcn_featureless_bwd(b, x, ip, ii, in_rows, g, ldg, dout, w, comp, nb, ws, nbytes, dw, dc, None, None, None)
+
+    # the calls as given stop at the workspace check, the last before the device
+    assert bwd() == WS
+    # in_rows must be n_nodes without x_index (x_j = j), and positive with it
+    assert fwd(in_rows=n + 1) == PLAN and fwd(in_rows=n - 1) == PLAN and bwd(in_rows=n + 1) == PLAN
+    assert fwd(x=d, in_rows=0) == PLAN and bwd(x=d, ip=d, ii=d, in_rows=0) == PLAN
+    assert bwd(x=d, ip=d, ii=d, in_rows=n + 5) == WS                 # x_index given: any table height
+    # bases and comp go together
+    assert fwd(comp=d) == PLAN and fwd(nb=2) == NULL and fwd(nb=-1) == NULL
+    assert bwd(nb=2) == NULL and bwd(dc=d) == PLAN                   # d_comp without bases
+    assert bwd(dc=d, comp=d, nb=2, w=None) == NULL                   # d_comp needs the bases
+    # an x_index needs its inverted index
+    assert bwd(x=d) == NULL and bwd(x=d, ip=d) == NULL and bwd(x=d, ii=d) == NULL
+    # widths 1 .. 128 only
+    for w in (0, 129, -1):
+        assert fwd(dout=w, ldo=256) == WIDTH and bwd(dout=w, ldg=256) == WIDTH
+    # strides: multiples of 4, at least round4(width)
+    for dout, ld in ((16, 12), (16, 18), (5, 4), (5, 6), (1, 2), (128, 124), (16, 0)):
+        assert fwd(dout=dout, ldo=ld) == STRIDE and bwd(dout=dout, ldg=ld) == STRIDE, (dout, ld)
+    big = _plan(0, 64, 64, tile=32768)           # an accumulator no LDS holds: an accepted forward stops at RGCN_ERR_LDS
+    for dout, ld in ((5, 8), (1, 4), (16, 20), (128, 128)):
+        assert lib.rgcn_featureless_fwd(ctypes.byref(big), None, n, d, None, 0, None, None, d, ld, dout, None) == LDS, (dout, ld)
+        assert bwd(dout=dout, ldg=ld) == WS, (dout, ld)
+    # NULL operands
+    assert fwd(w=None) == NULL and fwd(out=None) == NULL and bwd(g=None) == NULL and bwd(ws=None) == NULL
+    # the basis backward's LDS: 18 bases of 128 columns fit tile 16 (160,768 B), 19 do not (169,216 B > 160 KiB)
+    need18 = lib.rgcn_featureless_bwd_workspace_bytes(b, 128, 18, 0)
+    need19 = lib.rgcn_featureless_bwd_workspace_bytes(b, 128, 19, 0)
+    assert need18 > 0 and need19 > need18
+    assert bwd(dout=128, ldg=128, comp=d, nb=18, ws=d, nbytes=need18 - 1) == WS
+    assert bwd(dout=128, ldg=128, comp=d, nb=19, ws=d, nbytes=need19) == LDS
+
+
+def test_featureless_workspace_bytes():
+    """bias slab, d_comp slab, per-node rows of an integer x: each piece 256-byte aligned"""
+    lib = _lib.load()
+    ps = _plan(0, 64, 64, tile=16)
+    ps.n_tiles = 63
+    ps.n_chunks = ps.n_units = 100
+    b = ctypes.byref(ps)
+    a256 = lambda v: (v + 255) // 256 * 256
+    for dout, nb, idx in ((16, 0, 0), (16, 0, 1), (5, 0, 1), (128, 3, 0), (7, 2, 1), (1, 1, 1)):
+        d4 = (dout + 3) // 4
+        tabs = (nb if nb else ps.num_relations) + 1
+        want = a256(63 * d4 * 16) + a256(100 * nb * 4 if nb else 0) + a256(tabs * ps.n_nodes * d4 * 16 if idx else 0)
+        assert lib.rgcn_featureless_bwd_workspace_bytes(b, dout, nb, idx) == want, (dout, nb, idx)
+    for dout, nb in ((0, 0), (129, 0), (16, -1)):
+        assert lib.rgcn_featureless_bwd_workspace_bytes(b, dout, nb, 0) == 0
+
+
+# (n_nodes, out, bases) -> tile, or a status.  tile = (n / 4096) / 16 * 16 in [16, 128], cut by 16 while the backward's LDS
+# ((tile + 1) d4 16 B, + B tile d4 16 B + B 256 B with bases) passes 20 KiB; RGCN_ERR_LDS when tile 16 passes 160 KiB.
+FEATURELESS_GEOMETRY = {
+    (1, 1, 0): 16, (1000, 16, 0): 16, (65535, 16, 0): 16, (65536, 16, 0): 16, (131071, 16, 0): 16, (131072, 16, 0): 32,
+    (140010, 100, 0): 32, (200000, 24, 0): 48, (270000, 24, 2): 64, (300017, 40, 2): 32, (400000, 16, 0): 96,
+    (524288, 16, 0): 128, (600000, 16, 0): 128, (1_500_000, 16, 0): 128, (2**31 - 1, 1, 0): 128,
+    (600000, 64, 0): 64, (600000, 65, 0): 64, (600000, 96, 0): 48, (1_000_000, 128, 0): 32, (600000, 16, 1): 128, (600000, 16, 3): 64,
+    (1_000_000, 100, 2): 16, (1_000_000, 128, 1): 16, (1000, 128, 18): 16,
+    (1000, 128, 19): LDS, (1000, 0, 0): WIDTH, (1000, 129, 0): WIDTH, (0, 16, 0): PLAN, (-5, 16, 0): PLAN, (1000, 16, -1): PLAN,
+}
+
+
+@pytest.mark.parametrize("key", list(FEATURELESS_GEOMETRY), ids=lambda k: "n%d-out%d-b%d" % k)
+def test_featureless_geometry_table(key):
+    tile, chunk = ctypes.c_int(-1), ctypes.c_int(-1)
+    st = _lib.load().rgcn_featureless_geometry(*key, ctypes.byref(tile), ctypes.byref(chunk))
+    want = FEATURELESS_GEOMETRY[key]
+    if want < 0:
+        assert st == want and (tile.value, chunk.value) == (-1, -1)
+    else:
+        assert st == 0 and (tile.value, chunk.value) == (want, 64)

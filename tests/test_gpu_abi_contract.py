@@ -825,3 +825,180 @@ def test_capture_from_a_cold_process(dev):
     points (the first launch of a kernel instantiation sets its LDS attribute), replays it and compares with an eager run."""
     res = subprocess.run([sys.executable, "-c", _CHILD, ROOT], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0 and "cold capture ok" in res.stdout, (res.returncode, res.stdout[-2000:], res.stderr[-4000:])
+
+
+# ---- featureless layers: rgcn_featureless_fwd / _bwd on guarded operands -----------------------------------------------------------
+# Tables, comp, root, bias and x_index in sentinel buffers with row stride exactly `out` (a read past the last table row is a NaN),
+# out / g at three strides, every backward output subset, the workspace at exactly its queried size.  Tile 128 x out 128: the
+# forward's accumulator is 66,048 B of LDS (past 64 KiB), the basis backward with B = 1 131,840 B.
+FL_IN_ROWS = 300          # rows of the tables under an integer x (x values repeat; the last 10 rows are never gathered)
+
+
+def _guarded_flat(t, dev, dtype=torch.float32):
+    """a Flat holding t (float32 / int32 / int64), and a snapshot of its bits"""
+    t = t.contiguous().view(-1)
+    if dtype == torch.int64:
+        f = Flat(2 * t.numel(), dev, torch.int32)
+        f.t = f.buf[f.g:f.g + 2 * t.numel()].view(torch.int64)
+    else:
+        f = Flat(t.numel(), dev, dtype)
+    f.t.copy_(t.to(dev, dtype))
+    f.snap = f.buf.clone()
+    return f
+
+
+@functools.lru_cache(None)
+def fl_operands(dout, nb, indexed):
+    """float32 tables (weight or bases, comp, root, bias), g, and an integer x (None when not indexed) for the module's graph"""
+    gen = torch.Generator().manual_seed(dout * 17 + nb * 3 + indexed)
+    in_rows = FL_IN_ROWS if indexed else N
+    w = torch.randn(nb if nb else R, in_rows, dout, generator=gen)
+    comp = torch.randn(R, nb, generator=gen) if nb else None
+    root = torch.randn(in_rows, dout, generator=gen)
+    bias = torch.randn(dout, generator=gen)
+    dg = torch.randn(N, dout, generator=gen)
+    x = torch.randint(0, in_rows - 10, (N,), generator=gen) if indexed else None
+    return dict(w=w, comp=comp, root=root, bias=bias, dg=dg, x=x, in_rows=in_rows)
+
+
+def fl_call_fwd(ps, o, dout, nb, ldo, dev, x=None, root=True, bias=True):
+    lib = _lib().load()
+    ins = {"weight": _guarded_flat(o["w"], dev), "root": _guarded_flat(o["root"], dev), "bias": _guarded_flat(o["bias"], dev)}
+    if nb:
+        ins["comp"] = _guarded_flat(o["comp"], dev)
+    x = o["x"] if x is None else x
+    if x is not None:
+        ins["x"] = _guarded_flat(x, dev, torch.int64)
+    out = Guarded(N, ldo, dev, g1=G_OUT)
+    p = lambda k: ins[k].ptr if k in ins else None
+    st = lib.rgcn_featureless_fwd(C.byref(ps), p("x"), o["in_rows"], p("weight"), p("comp"), nb, p("root") if root else None,
+                                  p("bias") if bias else None, out.ptr, ldo, dout, _stream())
+    torch.cuda.synchronize()
+    for k, f in ins.items():
+        assert torch.equal(f.buf, f.snap), f"rgcn_featureless_fwd: input {k} was written"
+    return st, out
+
+
+WANT = ("weight", "comp", "root", "bias")
+
+
+def fl_call_bwd(ps_t, o, dout, nb, ldg, dev, want=WANT, ws_bytes=None):
+    """rgcn_featureless_bwd with the outputs in `want` (others NULL) -> (status, {name: values}, workspace)"""
+    from scaling_rgcn_training_amd.conv import _node_index
+    L = _lib()
+    lib = L.load()
+    in_rows = o["in_rows"]
+    ins = {"weight": _guarded_flat(o["w"], dev)}
+    if nb:
+        ins["comp"] = _guarded_flat(o["comp"], dev)
+    if o["x"] is not None:
+        x64, ptr, perm = _node_index(o["x"].to(dev), in_rows)
+        ins["x"] = _guarded_flat(x64, dev, torch.int64)
+        ins["inv_ptr"] = _guarded_flat(ptr, dev, torch.int32)
+        ins["inv_idx"] = _guarded_flat(perm, dev, torch.int32)
+    g = Guarded(N, ldg, dev).fill(o["dg"])
+    sizes = {"weight": o["w"].numel(), "comp": R * nb, "root": in_rows * dout, "bias": dout}
+    outs = {k: Flat(sizes[k], dev) for k in want if sizes[k]}
+    need = lib.rgcn_featureless_bwd_workspace_bytes(C.byref(ps_t), dout, nb, int(o["x"] is not None))
+    assert need > 0
+    ws = Workspace(need if ws_bytes is None else ws_bytes, dev)
+    p = lambda d, k: d[k].ptr if k in d else None
+    st = lib.rgcn_featureless_bwd(C.byref(ps_t), p(ins, "x"), p(ins, "inv_ptr"), p(ins, "inv_idx"), in_rows, g.ptr, ldg, dout,
+                                  p(ins, "weight"), p(ins, "comp"), nb, ws.ptr, ws.n, p(outs, "weight"), p(outs, "comp"),
+                                  p(outs, "root"), p(outs, "bias"), _stream())
+    torch.cuda.synchronize()
+    ws.check("rgcn_featureless_bwd workspace")
+    g.unchanged("rgcn_featureless_bwd g")
+    for k, f in ins.items():
+        assert torch.equal(f.buf, f.snap), f"rgcn_featureless_bwd: input {k} was written"
+    vals = {k: f.out(f"featureless d_{k}") for k, f in outs.items()}
+    return st, vals, need
+
+
+def _fl_ref(o, dout, x=None):
+    x = o["x"] if x is None else x
+    return O.featureless_reference(x, *graph(), o["w"], o["comp"], o["root"], o["bias"], o["dg"], "mean")
+
+
+FL_CASES = [(16, 64, 7, 0, False), (16, 128, 5, 3, True), (48, 64, 33, 2, False), (48, 128, 24, 0, True),
+            (128, 64, 128, 0, False), (128, 128, 128, 1, True), (128, 64, 1, 2, True)]
+
+
+@pytest.mark.parametrize("k", range(3), ids=["round4", "round4+4", "padded+4"])
+@pytest.mark.parametrize("tile,chunk,dout,nb,indexed", FL_CASES, ids=lambda v: str(v))
+def test_featureless_guarded(dev, tile, chunk, dout, nb, indexed, k):
+    fp = plans(tile, chunk, 0)
+    ps, ps_t = _lib().plan_struct(fp.fwd), _lib().plan_struct(fp.bwd)
+    assert (ps.tile, ps.chunk, ps.layout, ps_t.tile, ps_t.chunk) == (tile, chunk, 0, tile, chunk)
+    assert N % tile != 0
+    o = fl_operands(dout, nb, indexed)
+    ref, cond = _fl_ref(o, dout)
+    tag = f"tile {tile} chunk {chunk} out {dout} B {nb} x {indexed} ld {k}"
+    ldo, ldg = _pair(dout, dout, k)
+    st, out = fl_call_fwd(ps, o, dout, nb, ldo, dev)
+    assert st == OK, tag
+    assert_close(out.out(dout, "featureless out " + tag), ref["out"].numpy(), cond["out"].numpy(), "abi featureless out " + tag)
+    # root and bias may be NULL
+    st, out = fl_call_fwd(ps, o, dout, nb, ldo, dev, root=False, bias=False)
+    assert st == OK
+    xn = torch.arange(N) if o["x"] is None else o["x"]
+    assert_close(out.out(dout, "featureless out no root " + tag), (ref["out"] - o["root"].double()[xn] - o["bias"].double()).numpy(),
+                 cond["out"].numpy(), "abi featureless out without root / bias " + tag)
+    # the backward: all outputs, then every subset with the others NULL, bit-identical
+    st, full, need = fl_call_bwd(ps_t, o, dout, nb, ldg, dev)
+    assert st == OK, tag
+    for name in full:
+        got = full[name].view(ref[name].shape).double().cpu().numpy()
+        assert_close(got, ref[name].numpy(), cond[name].numpy(), f"abi featureless d_{name} {tag}")
+    names = [n for n in WANT if n != "comp" or nb]
+    for mask in range(1 << len(names)):
+        sub = tuple(n for i, n in enumerate(names) if mask >> i & 1)
+        if len(sub) == len(names):
+            continue
+        st, vals, _ = fl_call_bwd(ps_t, o, dout, nb, ldg, dev, want=sub)
+        assert st == OK and set(vals) == set(sub), (sub, st)
+        for name in sub:
+            assert torch.equal(vals[name], full[name]), f"{tag}: d_{name} with only {sub} differs from the all-outputs call"
+    if k == 0:
+        st, _, _ = fl_call_bwd(ps_t, o, dout, nb, ldg, dev, ws_bytes=need - 1)
+        assert st == ERR_WORKSPACE
+
+
+@pytest.mark.parametrize("nb", [1, 2])
+def test_featureless_lds_past_64k(dev, nb):
+    """tile 128 x out 128: the basis backward with one basis needs 131,840 B of LDS and runs; with two, 197,632 B > 160 KiB,
+    RGCN_ERR_LDS before anything is launched"""
+    fp = plans(128, 64, 0)
+    o = fl_operands(128, nb, False)
+    st, vals, _ = fl_call_bwd(_lib().plan_struct(fp.bwd), o, 128, nb, 128, dev)
+    if nb == 1:
+        assert st == OK
+        ref, cond = _fl_ref(o, 128)
+        for name in vals:
+            assert_close(vals[name].view(ref[name].shape).double().cpu().numpy(), ref[name].numpy(), cond[name].numpy(),
+                         f"abi featureless d_{name} LDS 131,840 B")
+    else:
+        assert st == ERR_LDS
+        for f in vals.values():
+            assert bool((f.view(torch.int32) == SENT).all()), "a refused call wrote an output"
+
+
+@pytest.mark.parametrize("nb", [0, 2])
+def test_featureless_out_of_range_index_reads_zeros(dev, nb):
+    """x_index entries in_rows and -1 gather zero rows (table, root) in the forward, as the header promises"""
+    fp = plans(48, 64, 0)
+    dout = 12
+    o = fl_operands(dout, nb, True)
+    x = o["x"].clone()
+    x[::7] = FL_IN_ROWS
+    x[3::11] = -1
+    st, out = fl_call_fwd(_lib().plan_struct(fp.fwd), o, dout, nb, r4(dout), dev, x=x)
+    assert st == OK
+    # the reference: one zero row appended to every table, the out-of-range entries pointed at it
+    z = dict(o)
+    z["w"] = torch.cat([o["w"], torch.zeros(o["w"].shape[0], 1, dout)], 1)
+    z["root"] = torch.cat([o["root"], torch.zeros(1, dout)])
+    xr = torch.where((x < 0) | (x >= FL_IN_ROWS), torch.full_like(x, FL_IN_ROWS), x)
+    ref, cond = _fl_ref(z, dout, x=xr)
+    assert_close(out.out(dout, "featureless out-of-range x"), ref["out"].numpy(), cond["out"].numpy(),
+                 "abi featureless out, x out of range")

@@ -59,7 +59,7 @@ def _run(conv, x, ei, et, g):
     out = conv(x, ei, et)
     out.backward(g)
     torch.cuda.synchronize()
-    return out.detach().cpu(), {k: p.grad.detach().cpu().clone() for k, p in conv.named_parameters()}
+    return out.detach().cpu(), {k: p.grad.detach().cpu().clone() for k, p in conv.named_parameters() if p.requires_grad}
 
 
 CASES = [(idx, mode, aggr, rb) for idx in (False, True) for mode in ("full", "basis") for aggr in ("mean", "sum")
@@ -221,3 +221,255 @@ def test_basis_weights_are_never_materialised(dev):
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated() - base
     assert peak < dense_bytes / 8, (peak, dense_bytes)
+
+
+# ---- against the sparse fp64 reference (oracle.featureless_reference): tiles above 16, hubs, long reduction loops ------------
+def _layer(in_rows, dout, r, nb, aggr, seed, root_bias=True):
+    from scaling_rgcn_training_amd.conv import RGCNConv
+    torch.manual_seed(seed)
+    conv = RGCNConv(in_rows, dout, r, num_bases=nb, aggr=aggr, root_weight=root_bias, bias=root_bias, featureless=True).cuda()
+    if root_bias:
+        with torch.no_grad():
+            conv.bias.uniform_(-1, 1)
+    return conv
+
+
+def _run_dev(conv, x, ei, et, g):
+    """(out, grads) with the gradients left on the device"""
+    for p in conv.parameters():
+        p.grad = None
+    out = conv(x, ei, et)
+    out.backward(g)
+    torch.cuda.synchronize()
+    return out.detach(), {k: p.grad for k, p in conv.named_parameters()}
+
+
+def _check_sparse(conv, x, ei, et, g, aggr, tag, got=None):
+    """output and every gradient against the sparse reference; the rows of d_weight (d_bases) no edge gathers: exact zeros,
+    checked on the device.  Returns the device results."""
+    dev = torch.device("cuda:0")
+    xd = None if x is None else x.to(dev)
+    if got is None:
+        got = _run_dev(conv, xd, ei.to(dev), et.to(dev), g.to(dev))
+    out, grads = got
+    p = {k: None if v is None else v.detach().cpu() for k, v in
+         (("weight", conv.weight), ("comp", conv.comp), ("root", conv.root), ("bias", conv.bias))}
+    ref, cond = O.featureless_reference(x, ei, et, p["weight"], p["comp"], p["root"], p["bias"], g, aggr, dense=False)
+    assert_close(out.cpu().numpy(), ref["out"].numpy(), cond["out"].numpy(), f"featureless out {tag}")
+    dw = grads["weight"].view(-1, conv.out_channels)
+    rows = ref["weight_rows"].to(dev)
+    assert_close(dw[rows].cpu().numpy(), ref["weight"].numpy(), cond["weight"].numpy(), f"featureless d_weight rows {tag}")
+    nz = (dw != 0).any(1)
+    nz[rows] = False
+    assert not bool(nz.any()), f"{tag}: {int(nz.sum())} d_weight rows no edge gathers are not zero"
+    for k in ("comp", "root", "bias"):
+        if p[k] is not None:
+            assert_close(grads[k].cpu().numpy(), ref[k].numpy(), cond[k].numpy(), f"featureless d_{k} {tag}")
+    return got
+
+
+def _big_graph(n, e, r, seed):
+    g = torch.Generator().manual_seed(seed)
+    src = torch.randint(0, n, (e,), generator=g)
+    dst = torch.randint(0, n, (e,), generator=g)
+    typ = torch.randint(0, r - 1, (e,), generator=g)          # relation r - 1 without edges
+    return torch.stack([src, dst]), typ
+
+
+# (n, out, bases, aggr, in_rows of an integer x or None) -> the tile rgcn_featureless_geometry picks.  No n is a multiple of
+# its tile; every case has thousands of tiles and, per relation, hundreds of units (fl_bias_reduce / fl_comp_reduce loops).
+TILE_CASES = {
+    (600_000, 16, None, "mean", None): 128,
+    (400_000, 16, None, "sum", 150_000): 96,
+    (270_000, 24, 2, "mean", 40_000): 64,          # L = 8
+    (200_000, 24, None, "sum", None): 48,          # L = 8
+    (140_010, 100, None, "mean", None): 32,        # L = 32
+    (300_017, 40, 2, "sum", None): 32,             # L = 16
+}
+
+
+@pytest.mark.parametrize("key", list(TILE_CASES), ids=lambda k: "n%d-out%d-b%s-%s-x%s" % k)
+def test_featureless_tiles_against_sparse_fp64(dev, key):
+    from scaling_rgcn_training_amd import _lib
+    n, dout, nb, aggr, in_rows = key
+    tile = TILE_CASES[key]
+    assert _lib.featureless_geometry(n, dout, nb or 0) == (tile, 64)
+    assert n % tile != 0
+    r = 4
+    ei, et = _big_graph(n, 2 * n, r, seed=n % 1000)
+    x = None
+    if in_rows is not None:
+        x = torch.randint(0, in_rows - 10, (n,), generator=torch.Generator().manual_seed(3))
+    conv = _layer(in_rows or n, dout, r, nb, aggr, seed=dout)
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(6))
+    out, grads = _check_sparse(conv, x, ei, et, g, aggr, f"tile {tile}")
+    if tile == 128:                 # bit-reproducible at the largest tile as well
+        out2, grads2 = _run_dev(conv, None if x is None else x.to(dev), ei.to(dev), et.to(dev), g.to(dev))
+        assert torch.equal(out, out2)
+        for k in grads:
+            assert torch.equal(grads[k], grads2[k]), k
+    del conv, out, grads
+    torch.cuda.empty_cache()
+
+
+WIDTHS = [1, 3, 4, 5, 16, 17, 31, 32, 33, 64, 65, 127]
+
+
+@pytest.mark.parametrize("mode", ["full", "basis"])
+@pytest.mark.parametrize("dout", WIDTHS)
+def test_featureless_width_sweep(dev, dout, mode):
+    """both sides of every lanes-per-slot boundary (out 16 / 32 / 64) and of dout % 4; full weights with x = None and mean,
+    bases with an integer x and sum; against the dense fp64 oracle at x = one_hot(x)"""
+    n, r = 150, 4
+    aggr = "mean" if mode == "full" else "sum"
+    in_rows = n if mode == "full" else 70
+    ei, et = _graph(n, 1200, r, seed=dout)
+    conv = _layer(in_rows, dout, r, 2 if mode == "basis" else None, aggr, seed=dout)
+    x = None if mode == "full" else torch.randint(0, in_rows - 5, (n,), generator=torch.Generator().manual_seed(dout))
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(dout + 1))
+    out, grads = _run(conv, None if x is None else x.to(dev), ei.to(dev), et.to(dev), g.to(dev))
+    xoh = np.eye(n) if x is None else torch.nn.functional.one_hot(x, in_rows).double().numpy()
+    p_cpu = tuple(None if p is None else p.detach().cpu() for p in (conv.weight, conv.comp, conv.root, conv.bias))
+    ref, rg = _reference(xoh, ei, et, p_cpu, r, in_rows, dout, g, aggr)
+    c_out, cg = _reference(xoh, ei, et, p_cpu, r, in_rows, dout, g, aggr, absolute=True)
+    assert_close(out.numpy(), ref, c_out, f"featureless out {mode} {dout}")
+    for k in ("weight", "comp", "root", "bias"):
+        if k in grads:
+            assert_close(grads[k].numpy(), rg[k], cg[k], f"featureless d_{k} {mode} {dout}")
+
+
+@pytest.mark.parametrize("mode,indexed", [("full", False), ("full", True), ("basis", False), ("basis", True)])
+def test_featureless_hubs(dev, mode, indexed):
+    """a destination with 5,000 in-edges of one relation (its run crosses row tiles, unroll groups and ~80 chunks of the
+    forward walk), a source with 5,000 out-edges (the same in the transposed walk), and under integer x one table row shared
+    by 1,000 nodes"""
+    n, r, dout = 6000, 3, 33 if mode == "basis" else 16
+    gen = torch.Generator().manual_seed(12)
+    ei, et = _big_graph(n, 12_000, r, seed=12)
+    hub_in = torch.stack([torch.randint(0, n, (5000,), generator=gen), torch.full((5000,), 17)])
+    hub_out = torch.stack([torch.full((5000,), 23), torch.randint(0, n, (5000,), generator=gen)])
+    ei = torch.cat([ei, hub_in, hub_out], 1)
+    et = torch.cat([et, torch.full((5000,), 1), torch.zeros(5000, dtype=torch.int64)])
+    in_rows, x = n, None
+    if indexed:
+        in_rows = 2500
+        x = torch.randint(0, in_rows, (n,), generator=gen)
+        x[torch.randperm(n, generator=gen)[:1000]] = 7
+        assert int((x == 7).sum()) >= 1000
+    conv = _layer(in_rows, dout, r, 2 if mode == "basis" else None, "mean", seed=4)
+    g = torch.randn(n, dout, generator=gen)
+    _check_sparse(conv, x, ei, et, g, "mean", f"hubs {mode} indexed={indexed}")
+
+
+@pytest.mark.parametrize("indexed", [False, True], ids=["x-none", "x-index"])
+def test_featureless_gradient_subsets_are_bit_identical(dev, indexed):
+    """freeze weight, then comp, then root, then everything but bias: every gradient still computed equals the one of the
+    all-gradients call bit for bit"""
+    n, r, dout = 900, 5, 20
+    ei, et = _graph(n, 6000, r, seed=31)
+    in_rows = 400 if indexed else n
+    x = torch.randint(0, in_rows, (n,), generator=torch.Generator().manual_seed(2)).to(dev) if indexed else None
+    conv = _layer(in_rows, dout, r, 3, "mean", seed=5)
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(8)).to(dev)
+    eid, etd = ei.to(dev), et.to(dev)
+    out, full = _run(conv, x, eid, etd, g)
+    names = [k for k, _ in conv.named_parameters()]
+    assert set(names) == {"weight", "comp", "root", "bias"}
+    for frozen in (["weight"], ["comp"], ["root"], ["weight", "comp", "root"]):
+        for k, p in conv.named_parameters():
+            p.requires_grad_(k not in frozen)
+        out2, sub = _run(conv, x, eid, etd, g)
+        assert torch.equal(out, out2)
+        assert set(sub) == set(names) - set(frozen), (frozen, set(sub))
+        for k in sub:
+            assert torch.equal(sub[k], full[k]), (frozen, k)
+    for p in conv.parameters():
+        p.requires_grad_(True)
+
+
+@pytest.mark.parametrize("mode", ["full", "basis"])
+def test_featureless_index_identities(dev, mode):
+    """bit for bit: x = arange(N) is x = None; x = perm with tables T is x = None with the row-permuted tables T[:, perm]
+    (gradients un-permuted)"""
+    n, r, dout = 700, 4, 12
+    nb = 3 if mode == "basis" else None
+    ei, et = _graph(n, 5000, r, seed=41)
+    eid, etd = ei.to(dev), et.to(dev)
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(1)).to(dev)
+    conv = _layer(n, dout, r, nb, "mean", seed=9)
+    out0, gr0 = _run(conv, None, eid, etd, g)
+    out1, gr1 = _run(conv, torch.arange(n, device=dev), eid, etd, g)
+    assert torch.equal(out0, out1)
+    assert set(gr0) == set(gr1)
+    for k in gr0:
+        assert torch.equal(gr0[k], gr1[k]), k
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(4)).to(dev)
+    outp, grp = _run(conv, perm, eid, etd, g)
+    convp = _layer(n, dout, r, nb, "mean", seed=9)
+    with torch.no_grad():
+        convp.weight.copy_(conv.weight[:, perm])
+        convp.root.copy_(conv.root[perm])
+        convp.bias.copy_(conv.bias)
+        if nb:
+            convp.comp.copy_(conv.comp)
+    outq, grq = _run(convp, None, eid, etd, g)
+    assert torch.equal(outp, outq)
+    inv = torch.argsort(perm).cpu()
+    assert torch.equal(grp["weight"], grq["weight"][:, inv])
+    assert torch.equal(grp["root"], grq["root"][inv])
+    assert torch.equal(grp["bias"], grq["bias"])
+    if nb:
+        assert torch.equal(grp["comp"], grq["comp"])
+
+
+def test_featureless_one_basis_of_ones_is_full_weights(dev):
+    """B = 1, comp = 1: W_r = V for every r.  The output equals full weights [V] * R bit for bit; d_bases is the sum of the
+    full d_weight over relations in relation order"""
+    n, r, dout = 500, 4, 24
+    ei, et = _graph(n, 4000, r, seed=5)
+    eid, etd = ei.to(dev), et.to(dev)
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(2)).to(dev)
+    basis = _layer(n, dout, r, 1, "mean", seed=3)
+    full = _layer(n, dout, r, None, "mean", seed=3)
+    with torch.no_grad():
+        basis.comp.fill_(1.0)
+        full.weight.copy_(basis.weight.expand(r, n, dout))
+        full.root.copy_(basis.root)
+        full.bias.copy_(basis.bias)
+    ob, gb = _run(basis, None, eid, etd, g)
+    of, gf = _run(full, None, eid, etd, g)
+    assert torch.equal(ob, of)
+    acc = torch.zeros(n, dout)
+    for rel in range(r):
+        acc = acc + gf["weight"][rel]
+    assert torch.equal(gb["weight"][0], acc)
+    assert torch.equal(gb["root"], gf["root"]) and torch.equal(gb["bias"], gf["bias"])
+
+
+def test_featureless_degenerate_graphs(dev):
+    """E = 0: out = bias + root[x], d_weight zeros, d_root = g summed per row.  N = 1.  in_channels = 1 (one table row shared
+    by every node)."""
+    from scaling_rgcn_training_amd.conv import RGCNConv
+    n, r, dout = 300, 3, 10
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(3))
+    empty_ei, empty_et = torch.zeros(2, 0, dtype=torch.int64), torch.zeros(0, dtype=torch.int64)
+    for mode in ("full", "basis"):
+        for x in (None, torch.randint(0, 50, (n,), generator=torch.Generator().manual_seed(1))):
+            conv = _layer(n if x is None else 50, dout, r, 2 if mode == "basis" else None, "mean", seed=2)
+            xd = None if x is None else x.to(dev)
+            out, grads = _run(conv, xd, empty_ei.to(dev), empty_et.to(dev), g.to(dev))
+            rows = torch.arange(n) if x is None else x
+            assert torch.equal(out, conv.root.detach().cpu()[rows] + conv.bias.detach().cpu()), mode
+            assert bool((grads["weight"] == 0).all())
+            if mode == "basis":
+                assert bool((grads["comp"] == 0).all())
+            _check_sparse(conv, x, empty_ei, empty_et, g, "mean", f"E = 0 {mode}")
+    # one node, a self loop
+    conv = _layer(1, 7, 2, None, "sum", seed=1)
+    ei, et = torch.zeros(2, 1, dtype=torch.int64), torch.zeros(1, dtype=torch.int64)
+    _check_sparse(conv, None, ei, et, torch.randn(1, 7), "sum", "N = 1")
+    # in_channels = 1: every node gathers row 0
+    ei, et = _graph(n, 2000, r, seed=3)
+    for nb in (None, 2):
+        conv = RGCNConv(1, dout, r, num_bases=nb, featureless=True).to(dev)
+        _check_sparse(conv, torch.zeros(n, dtype=torch.int64), ei, et, g, "mean", f"in_channels = 1 bases={nb}")

@@ -1,6 +1,7 @@
 """The oracle against its independent pins: dense formula, analytic grads,
 gradcheck, and the committed golden vectors.  CPU only."""
 import numpy as np
+import pytest
 import torch
 
 from oracle import rgcn_oracle as O
@@ -93,3 +94,54 @@ def test_reference_init_bounds():
     assert abs(w.abs().max().item() - 0.07715) < 2e-4
     assert root.abs().max().item() <= (6.0 / (63 + 16)) ** 0.5
     assert torch.all(bias == 0)
+
+
+@pytest.mark.parametrize("indexed", [False, True], ids=["x-none", "x-index"])
+@pytest.mark.parametrize("mode", ["full", "basis"])
+@pytest.mark.parametrize("aggr", ["mean", "sum"])
+@pytest.mark.parametrize("root_bias", [True, False], ids=["root-bias", "no-root-bias"])
+def test_featureless_reference_matches_dense_one_hot(indexed, mode, aggr, root_bias):
+    """the sparse fp64 featureless reference against the dense oracle at x = one_hot(x), gradients of the bases through
+    effective_weight by fp64 autograd; repeated indices, duplicate edges and a relation without edges"""
+    n, r, dout, nb = 40, 4, 5, 3
+    in_rows = 15 if indexed else n
+    g = torch.Generator().manual_seed(21)
+    ei = torch.randint(0, n, (2, 260), generator=g)
+    ei[:, 200:230] = ei[:, 0:30]
+    et = torch.randint(0, r - 1, (260,), generator=g)
+    et[200:230] = et[0:30]
+    x = torch.randint(0, in_rows - 3, (n,), generator=g) if indexed else None
+    w = torch.randn(nb if mode == "basis" else r, in_rows, dout, generator=g, dtype=torch.float64)
+    comp = torch.randn(r, nb, generator=g, dtype=torch.float64) if mode == "basis" else None
+    root = torch.randn(in_rows, dout, generator=g, dtype=torch.float64) if root_bias else None
+    bias = torch.randn(dout, generator=g, dtype=torch.float64) if root_bias else None
+    dg = torch.randn(n, dout, generator=g, dtype=torch.float64)
+    for absolute in (False, True):
+        f = (lambda t: None if t is None else t.abs()) if absolute else (lambda t: t)
+        wl, cl = f(w).clone().requires_grad_(True), None if comp is None else f(comp).clone().requires_grad_(True)
+        wfull = O.effective_weight(wl, cl, r, None, in_rows, dout)
+        xoh = np.eye(in_rows) if x is None else torch.nn.functional.one_hot(x, in_rows).double().numpy()
+        rn = None if root is None else f(root).numpy()
+        bn = None if bias is None else f(bias).numpy()
+        out = O.rgcn_conv_dense(xoh, ei.numpy(), et.numpy(), wfull.detach().numpy(), rn, bn, aggr=aggr)
+        gd = O.rgcn_conv_grads_dense(xoh, ei.numpy(), et.numpy(), wfull.detach().numpy(), rn, f(dg).numpy(), aggr=aggr)
+        want = {"out": out, "bias": gd["bias"], "root": gd.get("root")}
+        if comp is None:
+            want["weight"] = gd["weight"]
+        else:
+            dv, dc = torch.autograd.grad(wfull, (wl, cl), torch.from_numpy(gd["weight"]))
+            want["weight"], want["comp"] = dv.numpy(), dc.numpy()
+        ref, cond = O.featureless_reference(x, ei, et, w, comp, root, bias, dg, aggr)
+        got = cond if absolute else ref
+        assert set(got) == {k for k, v in want.items() if v is not None}
+        for k, v in want.items():
+            if v is not None:
+                np.testing.assert_allclose(got[k].numpy(), v, rtol=1e-12, atol=1e-12, err_msg=f"{k} abs={absolute}")
+        assert mode == "basis" or torch.all(got["weight"][r - 1] == 0)
+        # the sparse form: the same rows, zeros elsewhere
+        sp, _ = O.featureless_reference(x, ei, et, w, comp, root, bias, dg, aggr, dense=False)
+        flat = ref["weight"].reshape(-1, dout)
+        assert torch.equal(sp["weight"], flat[sp["weight_rows"]])
+        rest = torch.ones(flat.shape[0], dtype=torch.bool)
+        rest[sp["weight_rows"]] = False
+        assert bool((flat[rest] == 0).all())
