@@ -192,12 +192,15 @@ class NeededRows:
         return sum(t.numel() * 8 for t in self.send_idx + self.recv_idx)
 
 
-def needed_rows(edge_index: Tensor, n_nodes: int, dctx: DistContext):
+def needed_rows(edge_index: Tensor, n_nodes: int, dctx: DistContext, edge_type: Optional[Tensor] = None, paths=("ring", "ring")):
     """(forward, transposed) NeededRows of rank ``dctx.rank``, from the replicated edge list alone -- every rank derives its own
     receive lists AND what every peer will ask of it, so no plan-time communication and every pair of ranks agrees by
     construction.  A plan of rank c gathers, in the forward direction, the rows ``src(e)`` of the edges with ``dst(e)`` in c's
     blocks (the root pseudo edges read c's own rows); the transposed plans gather ``dst(e)`` of the edges with ``src(e)`` in c's
-    blocks.  One [world, N] boolean table per direction (80 MB at 10M nodes, world 8), filled by one scatter."""
+    blocks.  Hubs split across ranks (``dctx.split_hubs``, ``edge_type`` given and the direction on ``paths`` "ep":
+    eplan.SharedHeavy): the edges of heavy segments leave their owner's plans, and every rank c gathers instead the rows of
+    its share of the whole graph's sorted heavy rows, whichever blocks their segments lie in.  One [world, N] boolean table per
+    direction (80 MB at 10M nodes, world 8), filled by one scatter (and one per rank's share)."""
     dev = edge_index.device
     w, me = dctx.world, dctx.rank
     cuts = torch.tensor(dctx.bounds[1:], dtype=torch.int64, device=dev)
@@ -205,9 +208,22 @@ def needed_rows(edge_index: Tensor, n_nodes: int, dctx: DistContext):
     owner = torch.searchsorted(cuts, nodes, right=True) % w       # the rank that owns every node
     src, dst = edge_index[0].long(), edge_index[1].long()
     out = []
-    for consumer_of, row in ((dst, src), (src, dst)):
+    for d, (consumer_of, row) in enumerate(((dst, src), (src, dst))):
         need = torch.zeros(w, n_nodes, dtype=torch.bool, device=dev)
-        need[owner[consumer_of], row] = True
+        hub = None
+        if dctx.split_hubs and edge_type is not None and paths[d] == "ep" and row.numel():
+            from .eplan import HEAVY, shared_heavy_rows, shared_share
+            hub = shared_heavy_rows(row, consumer_of, edge_type, n_nodes, HEAVY)      # (build_shared_heavy's own sort and split)
+        if hub is None:
+            need[owner[consumer_of], row] = True
+        else:
+            hm, _, _, order = hub
+            light = ~hm
+            need[owner[consumer_of[light]], row[light]] = True
+            heavy_rows = row[hm][order]
+            for c in range(w):
+                lo, hi = shared_share(int(heavy_rows.numel()), w, c)
+                need[c, heavy_rows[lo:hi]] = True
         need[owner, nodes] = False          # a rank's own rows never travel
         send_idx, send_splits, recv_idx, recv_splits = [], [], [], []
         for s in range(dctx.pieces):
@@ -264,7 +280,7 @@ def rank_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relation
     laid out from the same edge list: on the GPU by the library's plan builder with the piece's node range (it keeps
     the edges that scatter into the range), on the CPU (tests) by the torch form from this rank's share."""
     ranges = [dctx.node_range(s, n_nodes) for s in range(dctx.pieces)]
-    nf, nb = needed_rows(edge_index, n_nodes, dctx) if dctx.exchange == "needed" else (None, None)
+    nf, nb = needed_rows(edge_index, n_nodes, dctx, edge_type, paths) if dctx.exchange == "needed" else (None, None)
     if edge_type.device.type == "cuda":
         from .plan import build_graph_plans_device
         from . import _lib

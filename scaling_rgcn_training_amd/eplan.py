@@ -82,20 +82,36 @@ class SharedHeavy:
     levels: list            # [(seg_ptr int32, seg_idx int32 or None, seg_w float32 or None, n_out)] over the share; outputs = H[seg_lo : seg_lo + n_out]
 
 
+def shared_heavy_rows(gather: Tensor, scatter: Tensor, rel: Tensor, n_nodes: int, threshold: int):
+    """The heavy rows of one direction in SharedHeavy's order, or None without a heavy segment: (edge mask, segment keys
+    ascending, segment of every heavy row, the heavy rows sorted by (segment, gathered row) as indices into ``gather[mask]``).
+    build_shared_heavy deals them; dist.needed_rows lists what every rank's share gathers from the same sort."""
+    hm = heavy_mask(scatter, rel, n_nodes, threshold)
+    if hm is None:
+        return None
+    g, sc, r_ = gather[hm].to(torch.int64), scatter[hm].to(torch.int64), rel[hm].to(torch.int64)
+    ukey, seg = torch.unique(r_ * n_nodes + sc, return_inverse=True)
+    order = torch.sort(seg * n_nodes + g)[1]                    # rows by (segment, gathered row)
+    return hm, ukey, seg, order
+
+
+def shared_share(n_rows: int, world: int, rank: int) -> Tuple[int, int]:
+    """[row_lo, row_hi): rank ``rank``'s contiguous share of ``n_rows`` sorted heavy rows"""
+    return n_rows * rank // world, n_rows * (rank + 1) // world
+
+
 def build_shared_heavy(gather: Tensor, scatter: Tensor, rel: Tensor, w: Tensor, n_nodes: int, threshold: int, world: int, rank: int,
                        piece: int = PIECE) -> Optional[SharedHeavy]:
     """gather / scatter / rel / w: the WHOLE edge list of one direction (replicated on every rank: every rank derives the same
     segments and the same shares)."""
-    hm = heavy_mask(scatter, rel, n_nodes, threshold)
-    if hm is None:
+    rows = shared_heavy_rows(gather, scatter, rel, n_nodes, threshold)
+    if rows is None:
         return None
-    g, sc, r_, w_ = gather[hm].to(torch.int64), scatter[hm].to(torch.int64), rel[hm].to(torch.int64), w[hm]
-    key = r_ * n_nodes + sc
-    ukey, seg = torch.unique(key, return_inverse=True)
+    hm, ukey, seg, order = rows
+    g, w_ = gather[hm].to(torch.int64), w[hm]
     n_seg = int(ukey.shape[0])
-    order = torch.sort(seg * n_nodes + g)[1]                    # rows by (segment, gathered row)
     m = int(order.shape[0])
-    lo, hi = m * rank // world, m * (rank + 1) // world
+    lo, hi = shared_share(m, world, rank)
     seg_sorted = seg[order]
     levels, seg_lo = [], 0
     if hi > lo:

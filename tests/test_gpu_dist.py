@@ -200,3 +200,160 @@ def test_emulated_world_8_ranks_stitch_to_the_single_rank_layer(exchange):
     finally:
         C.DW_TILES_MIN_EDGES = old
         clear_plan_cache()
+
+
+# ---- a partitioned TWO-layer stack against the float64 oracle ---------------------------------------------------------------
+# Only a layer that reads another partitioned layer's output can see a row the exchange failed to deliver (layer 1 reads the
+# replicated x).  conv1 (64 -> 64, bf16 x 3 on 128-slot chunks) -> ReLU -> conv2 (64 -> 16, exact fp32) on a graph with hubs on
+# BOTH sides and 45 relations (AIFB-like: path="auto" takes the edge-parallel path in both directions, so the heavy segments of
+# both directions are split across the ranks), every exchange / path / split_hubs case with unread rows poisoned with NaN.
+STACK_N, STACK_R = 4000, 45
+STACK_CASES = [(ex, path, split) for ex in ("full", "needed") for path in ("ring", "ep", "auto") for split in (True, False)]
+
+
+def _stack_graph():
+    from oracle import rgcn_oracle as O
+    a, ta = O.synthetic_graph(STACK_N, 30000, STACK_R, seed=3, skew=True)      # hubs at destinations
+    b, tb = O.synthetic_graph(STACK_N, 30000, STACK_R, seed=4, skew=True)      # ... and, flipped, at sources
+    return torch.cat([a, b.flip(0)], 1), torch.cat([ta, tb])
+
+
+def _stack_params():
+    from oracle import rgcn_oracle as O
+    w1, r1, _ = O.synthetic_params(STACK_R, 64, 64, seed=11)
+    w2, r2, _ = O.synthetic_params(STACK_R, 64, 16, seed=12)
+    g = torch.Generator().manual_seed(13)
+    return [(w1, r1, 0.1 * torch.randn(64, generator=g)), (w2, r2, 0.1 * torch.randn(16, generator=g))]
+
+
+def _oracle_stack(x, ei, et, params, dg, dtype):
+    """relu(conv1(x)) -> conv2 through tests.twins.OracleConv under autograd on the CPU: (out, d_x, [(d_W, d_root, d_bias)] * 2)"""
+    from tests.twins import OracleConv
+
+    class _P:       # the parameters OracleConv copies
+        def __init__(self, w, r, b):
+            self.weight, self.root, self.bias = (torch.nn.Parameter(t.clone()) for t in (w, r, b))
+
+    convs = [OracleConv(_P(*p)).to(dtype) for p in params]
+    xd = x.detach().to(dtype).clone().requires_grad_(True)
+    out = convs[1](torch.relu(convs[0](xd, ei, et)), ei, et)
+    out.backward(dg.to(dtype))
+    return out.detach(), xd.grad, [(c.weight.grad, c.root.grad, c.bias.grad) for c in convs]
+
+
+def _stack_worker(rank, world, port, ret):
+    import datetime
+    sys.path.insert(0, ROOT)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    # a rank that raises must not leave its peers waiting in a collective for gloo's default half hour
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+    from scaling_rgcn_training_amd import dist as rdist
+    from scaling_rgcn_training_amd.conv import RGCNConv
+    from scaling_rgcn_training_amd.eplan import decide_paths
+    dev = torch.device("cuda:0")
+    n, r = STACK_N, STACK_R
+    ei, et = _stack_graph()
+    e = int(et.shape[0])
+    eid, etd = ei.to(dev), et.to(dev)
+    params = _stack_params()
+    g = torch.Generator().manual_seed(14)
+    x = torch.randn(n, 64, generator=g)
+    dg = torch.randn(n, 16, generator=g)
+    # the oracle and the fp32 CPU loop (its own error sets the bound, as in test_gpu_shapes._two_layer_case), once per graph
+    ref = _oracle_stack(x, ei, et, params, dg, torch.float64)
+    r32 = _oracle_stack(x, ei, et, params, dg, torch.float32)
+    names = ["out", "d_x"] + [f"conv{i + 1}.{k}" for i in range(2) for k in ("d_weight", "d_root", "d_bias")]
+    flat = lambda res: [res[0], res[1]] + [t for grads in res[2] for t in grads]      # noqa: E731
+    ref_l, cpu_err = flat(ref), [float((a.double() - b).abs().max()) for a, b in zip(flat(r32), flat(ref))]
+    errs = []
+
+    def run(exchange, path, split):
+        convs = [RGCNConv(64, 64, r).to(dev), RGCNConv(64, 16, r).to(dev)]
+        for c, (w, rt, b) in zip(convs, params):
+            c.path = path
+            with torch.no_grad():
+                c.weight.copy_(w)
+                c.root.copy_(rt)
+                c.bias.copy_(b)
+        if exchange is not None:
+            rdist.attach(torch.nn.ModuleList(convs), n, e, edge_index=ei, exchange=exchange, edge_type=et, split_hubs=split)
+            for c in convs:
+                assert c.dist is not None and c.dist.world == world and c.dist.exchange == exchange and c.dist.split_hubs == split
+                c.dist.poison_unread = True
+            # a needed exchange feeds the next layer the rows ITS plans read: both layers must cut the graph alike
+            assert convs[0].dist.bounds == convs[1].dist.bounds
+        xd = x.to(dev).requires_grad_(True)
+        h = convs[0](xd, eid, etd, _activation="relu", _grad_premasked=True)
+        out = convs[1](h, eid, etd, _input_relu=True)
+        out.backward(dg.to(dev))
+        torch.cuda.synchronize()
+        res = [out.detach().cpu(), xd.grad.cpu()] + [p.grad.cpu() for c in convs for p in (c.weight, c.root, c.bias)]
+        return convs, (xd, h), res
+
+    single_ring = run(None, "ring", True)[2]
+    for exchange, path, split in STACK_CASES:
+        case = f"world {world} rank {rank} {exchange} {path} split_hubs={split}"
+        convs, (xd, h), res = run(exchange, path, split)
+        dctx = convs[0].dist
+        owned = torch.zeros(n, dtype=torch.bool)
+        for s_ in range(dctx.pieces):
+            b_, e_ = dctx.node_range(s_, n)
+            owned[b_:e_] = True
+        # which kernels actually ran, per layer
+        for c, inp in zip(convs, (xd, h)):
+            pl = c._plans(inp, eid, etd)
+            live = [pc for s_, pc in enumerate(pl.pieces) if c.dist.node_range(s_, n)[1] > c.dist.node_range(s_, n)[0]]
+            ep = path != "ring"
+            if path == "auto":
+                tile, chunk = c.layout(n, e)
+                assert decide_paths(eid, n, r, c.in_channels, c.out_channels, tile, chunk) == ("ep", "ep"), "auto takes ep here"
+            assert live and all((pc.ep_fwd is not None) == ep and (pc.fwd is None) == ep for pc in live), case
+            assert all((pc.ep_bwd is not None) == ep and (pc.bwd is None) == ep for pc in live), case
+            assert (pl.shared_fwd is not None) == (ep and split) and (pl.shared_bwd is not None) == (ep and split), case
+            assert (pl.needed_fwd is not None) == (exchange == "needed"), case
+        # owned rows of the output and of d_x, every weight gradient: finite, and within the oracle bound
+        got = [res[0][owned], res[1][owned]] + res[2:]
+        want = [ref_l[0][owned], ref_l[1][owned]] + ref_l[2:]
+        for nm, a, b, ce in zip(names, got, want, cpu_err):
+            if not bool(torch.isfinite(a).all()):
+                errs.append(f"{case}: {nm} has {int((~torch.isfinite(a)).sum())} non-finite entries")
+                continue
+            excess = float(((a.double() - b).abs() - (1e-5 + 1e-5 * b.abs())).max())
+            if excess > 2 * ce:
+                errs.append(f"{case}: {nm} excess over flat 1e-5 {excess:.3e} > 2 x fp32 CPU loop error {ce:.3e}")
+        # weight gradients are all-reduced: every rank holds the same bits
+        mine = torch.cat([t.reshape(-1) for t in res[2:]])
+        every = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(every, mine)
+        if not all(torch.equal(t, every[0]) for t in every):
+            errs.append(f"{case}: weight gradients differ across ranks")
+        if exchange == "full" and path == "ring":
+            # tile-aligned blocks: a rank's tiles are the single-rank tiles, bit for bit
+            for nm, a, b in zip(names[:2], res[:2], single_ring[:2]):
+                if not torch.equal(a[owned], b[owned]):
+                    errs.append(f"{case}: owned rows of {nm} differ from the single-rank stack")
+    ret.put((rank, errs))
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [2, 4])
+def test_partitioned_two_layer_stack_matches_the_float64_oracle(world):
+    """Every case of STACK_CASES inside ONE spawn of ``world`` ranks (processes and plan cache set up once): owned rows of the
+    output and of d_x and both layers' weight gradients against a float64 OracleConv stack, no NaN (unread rows are poisoned),
+    weight gradients bit-equal across ranks, ring + full exchange bit-identical to the single-rank stack."""
+    ctx = mp.get_context("spawn")
+    ret = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_stack_worker, args=(r, world, port, ret)) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(300)
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+            p.join(10)
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    errs = [m for _ in range(world) for m in ret.get(timeout=5)[1]]
+    assert not errs, "\n".join(errs)
