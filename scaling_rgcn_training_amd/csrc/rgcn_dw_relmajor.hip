@@ -3,7 +3,7 @@
 //   rgcn_dw_kernel        any padded width: per relation, dB_rel += (w_e x[src_e])^T g[dst_e]; ring + register accumulators
 //   rgcn_dw_wide_kernel   widths that are multiples of 64 (64 x 64 walks too short for the direct kernel, 64 x 128, 128 x 64)
 //   rgcn_dw_direct_kernel 64 x 64, large walks: no ring, every wave gathers its own rows into registers
-//   rgcn_dw_reduce_kernel fixed-order sum of the slabs -> d_weight / d_root / d_bias
+//   rgcn_dw_reduce_kernel fixed-order compensated sum of the slabs -> d_weight / d_root / d_bias
 #include "rgcn_kernels_shared.h"
 
 namespace rgcn {
@@ -672,6 +672,20 @@ __global__ void __launch_bounds__(256, 2) rgcn_dw_direct_kernel(const DwArgs a) 
 }
 
 // The workgroups whose chunk range touches relation r are a contiguous run [b_lo, b_hi].
+// Compensated (Kahan) running sum: the error of the slab sum stays at a few ulp of the result however many workgroup slabs
+// a relation spans.  A plain running sum over the up to 4 x 256 slabs of a capped walk (graphs of 1,024+ units) put d_bias
+// at 2.3 x the fp32 CPU loop's error on a 53k-node graph (tests/test_gpu_kernel_variants.py, multi-tile cases).  Same fixed
+// order as before: bit-reproducible.  (No fast-math here: the compensation term is not reassociated away.)
+struct KahanSum {
+    float s = 0.f, c = 0.f;
+    __device__ __forceinline__ void add(float v) {
+        const float y = v - c;
+        const float t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+
 __global__ void rgcn_dw_reduce_kernel(const float* __restrict__ slabs, const float* __restrict__ bias_slabs,
                                       const int* __restrict__ rel_order, const int* __restrict__ chunk_rel,
                                       int n_chunks, int ushift, int nblocks, int num_rel, int KP, int NP, int din, int dout,
@@ -704,20 +718,20 @@ __global__ void rgcn_dw_reduce_kernel(const float* __restrict__ slabs, const flo
     const int lo = s_lo, hi = s_hi;
     if (is_bias) {      // only the workgroups that walked root units wrote bias slabs (summing all 2048 was 0.7 ms)
         for (int n = threadIdx.x; n < dout; n += blockDim.x) {
-            float s = 0.f;
+            KahanSum s;
             for (int b = lo; b <= hi; ++b)
-                for (int c = 0; c < kDwSlabsPer; ++c) s += bias_slabs[((size_t)b * kDwSlabsPer + c) * NP + n];
-            d_bias[n] = s;
+                for (int c = 0; c < kDwSlabsPer; ++c) s.add(bias_slabs[((size_t)b * kDwSlabsPer + c) * NP + n]);
+            d_bias[n] = s.s;
         }
         return;
     }
     for (int e = blockIdx.y * blockDim.x + threadIdx.x; e < din * dout; e += gridDim.y * blockDim.x) {
         const int k = e / dout, n = e - k * dout;
-        float s = 0.f;
+        KahanSum s;
         for (int b = lo; b <= hi; ++b)
             for (int c = 0; c < kDwSlabsPer; ++c)
-                s += slabs[((size_t)(b + r) * kDwSlabsPer + c) * KP * NP + (size_t)k * NP + n];
-        dst[e] = s;
+                s.add(slabs[((size_t)(b + r) * kDwSlabsPer + c) * KP * NP + (size_t)k * NP + n]);
+        dst[e] = s.s;
     }
 }
 
@@ -820,17 +834,18 @@ extern "C" int rgcn_bwd_dw(const rgcn_plan_t* plan, const float* x, int ldx, int
         d_weight = nullptr;
     }
     // The direct-gather kernel (64 x 64, buffer-addressable operands) pays on large walks; small graphs take fewer
-    // persistent workgroups (>= 16 units each) of the ring kernels, and only their slabs are cleared / summed.
+    // persistent workgroups (>= 4 units each) of the ring kernels, and only their slabs are cleared / summed.
     // RGCN_FLAG_DW_RING / RGCN_FLAG_DW_DIRECT pin the choice (tests exercise both on small graphs).
     const unsigned xb = buffer_bytes(plan->n_nodes, ldx, flags), gb = buffer_bytes(plan->n_owned, ldg, flags);
     const bool can_direct = KP == 64 && NP == 64 && xb != 0 && gb != 0;
     const bool want_direct = can_direct && !(flags & RGCN_FLAG_DW_RING) &&
                              ((flags & RGCN_FLAG_DW_DIRECT) || n_units >= kDwDirectMinUnits);
     const int max_blocks = want_direct ? kDwBlocks : kDwRingBlocks;
-    // dense relation-major units (layout 2, the edge-parallel path's graphs): 4 units per workgroup instead of 16 -- four times
-    // the workgroups on graphs of a few hundred units, and accumulation chains of at most 256 rows before the fixed-order slab
-    // sum takes over (one chain over all rows of a relation measured 2.8 x the error of the CPU loop's blocked GEMM)
-    const int upb = plan->layout == 2 ? 4 : 16;
+    // 4 units per workgroup on every plan layout: accumulation chains of at most 256 rows before the fixed-order slab sum
+    // takes over wherever the workgroup cap allows.  One chain over all rows of a relation measured 2.8 x the error of the CPU
+    // loop's blocked GEMM on layout-2 plans; 16 units (1,024-row chains) on tile plans put d_weight / d_root at 2.2-2.6 x on
+    // 2,500-node graphs (tests/test_gpu_kernel_variants.py).  Walks of 4,096+ units are unchanged (the cap binds either way).
+    const int upb = 4;
     const int nblocks = n_units / upb < 1 ? 1 : (n_units / upb > max_blocks ? max_blocks : n_units / upb);
     const size_t slab_bytes = sizeof(float) * (size_t)(nblocks + plan->num_relations + 1) * kDwSlabsPer * KP * NP;
     float* bias_slabs = (float*)workspace + dw_slab_floats(plan->num_relations, KP, NP);
