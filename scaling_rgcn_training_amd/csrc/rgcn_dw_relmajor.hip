@@ -37,6 +37,16 @@ struct DwArgs {
     int ushift;        // log2(units per chunk): unit u belongs to chunk u >> ushift, rows 64 * (u & mask) .. + 63 of it
 };
 
+
+// Compensated add of the bias column sums: a lane adds up to n / (workgroups x lanes per column) dOut rows into one register
+// (33,000 rows per workgroup at 2^24 nodes); a plain running sum put d_bias at 5 x the error of ATen's fp32 column sum there
+// (tests/test_gpu_past_4gib.py).  (No fast-math here: the compensation term is not reassociated away.)
+__device__ __forceinline__ void bias_add(float& s, float& c, float v) {
+    const float y = v - c;
+    const float t = s + y;
+    c = (t - s) - y;
+    s = t;
+}
 template <int KP, int NP, int NBUF, bool BUF>
 __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
     constexpr int MT = KP / 16, NT = NP / 16;
@@ -65,13 +75,13 @@ __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
     const int ntb = NT < 4 ? cwv % NT : cwv;              // first n-slice of this wave (then +4 per s)
     const int mtb = NT < 4 ? cwv / NT : 0;                // first m-tile (then +RWM per i)
     f32x4 acc[NSL][MTW];
-    float bsum[NSL];
+    float bsum[NSL], bcmp[NSL];
     int rel_cur = -1;
 
     auto zero_acc = [&]() {
 #pragma unroll
         for (int s = 0; s < NSL; ++s) {
-            bsum[s] = 0.f;
+            bsum[s] = bcmp[s] = 0.f;
 #pragma unroll
             for (int i = 0; i < MTW; ++i) acc[s][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
@@ -164,7 +174,7 @@ __global__ void __launch_bounds__(kThreads, 2) rgcn_dw_kernel(const DwArgs a) {
                     float bv[NSL];
 #pragma unroll
                     for (int s = 0; s < NSL; ++s) {
-                        if (is_root) bsum[s] += o.gv[t][s];
+                        if (is_root) bias_add(bsum[s], bcmp[s], o.gv[t][s]);
                         bv[s] = o.gv[t][s] * o.wv[t];
                     }
 #pragma unroll
@@ -284,12 +294,12 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
         const int team = cwv >> 2;
         const int ml = lane & 15, kq = lane >> 4;
         f32x4 acc[NA][NB];
-        float bsum[NB];
+        float bsum[NB], bcmp[NB];
         int rel_cur = -1;
         auto zero_acc = [&]() {
 #pragma unroll
             for (int jb = 0; jb < NB; ++jb) {
-                bsum[jb] = 0.f;
+                bsum[jb] = bcmp[jb] = 0.f;
 #pragma unroll
                 for (int ia = 0; ia < NA; ++ia) acc[ia][jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
@@ -427,7 +437,7 @@ __global__ void __launch_bounds__(64 * (kProducerWaves + CONS), (kProducerWaves 
                             for (int u = 0; u < UB; ++u) {
                                 const f32x4 gv = *(const f32x4*)(grow + 16 * g * NP + 64 * u);
 #pragma unroll
-                                for (int c = 0; c < 4; ++c) bsum[4 * u + c] += gv[c];
+                                for (int c = 0; c < 4; ++c) bias_add(bsum[4 * u + c], bcmp[4 * u + c], gv[c]);
                             }
                         }
                     }
@@ -534,12 +544,12 @@ __global__ void __launch_bounds__(256, 2) rgcn_dw_direct_kernel(const DwArgs a) 
     const int perm = kq * 4;                     // ds_bpermute address of row kq of a k-step (further steps: +16 each)
 
     f32x4 acc[4][4];
-    float bsum[4];
+    float bsum[4], bcmp[4];
     int rel_cur = -1;
     auto zero_acc = [&]() {
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
-            bsum[jb] = 0.f;
+            bsum[jb] = bcmp[jb] = 0.f;
 #pragma unroll
             for (int ia = 0; ia < 4; ++ia) acc[ia][jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
@@ -623,7 +633,7 @@ __global__ void __launch_bounds__(256, 2) rgcn_dw_direct_kernel(const DwArgs a) 
 #pragma unroll
                     for (int t = 0; t < 4; ++t)
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) bsum[c] += o.g4[4 * gi + t][c];
+                        for (int c = 0; c < 4; ++c) bias_add(bsum[c], bcmp[c], o.g4[4 * gi + t][c]);
                 }
             }
         }

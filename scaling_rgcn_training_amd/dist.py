@@ -280,6 +280,8 @@ def rank_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relation
     laid out from the same edge list: on the GPU by the library's plan builder with the piece's node range (it keeps
     the edges that scatter into the range), on the CPU (tests) by the torch form from this rank's share."""
     ranges = [dctx.node_range(s, n_nodes) for s in range(dctx.pieces)]
+    from .eplan import check_ep_ranges
+    check_ep_ranges(paths, [(r, r) for r in ranges])
     nf, nb = needed_rows(edge_index, n_nodes, dctx, edge_type, paths) if dctx.exchange == "needed" else (None, None)
     if edge_type.device.type == "cuda":
         from .plan import build_graph_plans_device

@@ -38,6 +38,18 @@ from torch import Tensor
 UNIT = 64          # slots per unit (== plan.UNIT: what the weight-gradient kernels walk)
 PIECE = 256        # rows one lane group sums in a row before the sum goes through another level
 HEAVY = 16         # rows of one (destination, relation) segment from which the segment is aggregated BEFORE the transform
+EP_MAX_OWNED = 1 << 24   # most rows of an owned range the device builder lays out as one relation-major plan (csrc/rgcn_plan.hip,
+                         # layout 2); past it the direction runs the tile kernels
+
+
+def check_ep_ranges(paths, ranges) -> None:
+    """ValueError where a direction pinned to 'ep' owns more than EP_MAX_OWNED rows in one of ``ranges`` ([(fwd range, dX range)]):
+    raised before any plan is built, where the device builder would refuse the layout-2 plan (RGCN_ERR_PLAN)."""
+    for (fb, fe), (bb, be) in ranges:
+        for d, (b, e) in enumerate(((fb, fe), (bb, be))):
+            if paths[d] == "ep" and e - b > EP_MAX_OWNED:
+                raise ValueError(f"path 'ep' ({'forward' if d == 0 else 'dX'}) over an owned range of {e - b} rows: the edge-parallel "
+                                 f"plan holds at most EP_MAX_OWNED = 2^24 = {EP_MAX_OWNED} rows; use path 'ring' or 'auto'")
 
 
 @dataclass
@@ -475,7 +487,10 @@ def ep_launch_us(n_nodes: int, n_edges: int, in_width: int, out_width: int) -> f
 
 def choose_path(n_nodes: int, n_edges: int, num_relations: int, in_width: int, out_width: int, tile: int, chunk: int,
                 max_tile_rows: int) -> str:
-    """'ep' where the edge-parallel path is expected to be faster than the tile kernel for this direction."""
+    """'ep' where the edge-parallel path is expected to be faster than the tile kernel for this direction -- never for more than
+    EP_MAX_OWNED owned rows (``n_nodes``), which the edge-parallel plan cannot hold."""
+    if n_nodes > EP_MAX_OWNED:
+        return "ring"
     ring = ring_launch_us(n_nodes, n_edges, num_relations, max(in_width, out_width), tile, chunk, max_tile_rows)
     ep = ep_launch_us(n_nodes, n_edges, in_width, out_width)
     # (calibrated on the bench ladder, round 3: MUTAG shape -- tile kernels 0.169 ms per step replayed, edge-parallel 0.117 -- is
@@ -486,7 +501,11 @@ def choose_path(n_nodes: int, n_edges: int, num_relations: int, in_width: int, o
 def decide_paths(edge_index: Tensor, n_nodes: int, num_relations: int, in_channels: int, out_channels: int, tile: int,
                  chunk: int) -> Tuple[str, str]:
     """(forward path, dX path) for a layer on this graph.  One pass over the edge list per direction (rows per tile: a hub's
-    tile is walked by one workgroup of the tile kernel) and one host read of the two maxima -- at plan time only."""
+    tile is walked by one workgroup of the tile kernel) and one host read of the two maxima -- at plan time only.  The whole graph's
+    node count stands for the owned range: past EP_MAX_OWNED nodes both directions run the tile kernels (dist ranks, which decide
+    from the whole graph too, alike)."""
+    if n_nodes > EP_MAX_OWNED:
+        return "ring", "ring"
     e = int(edge_index.shape[1])
     n_tiles = (n_nodes + tile - 1) // tile
     if e:

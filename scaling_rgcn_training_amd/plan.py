@@ -669,11 +669,12 @@ def build_graph_plans_torch(edge_index: Tensor, edge_type: Tensor, n_nodes: int,
                             split: bool = False, paths: Tuple[str, str] = ("ring", "ring")) -> GraphPlans:
     """The plans as torch tensor ops (any device): the TEST ORACLE of the device-side builder and what the CPU-only
     tests walk with tests/plan_emulator.py.  paths: 'ring' (tile-major plan) or 'ep' (eplan.EdgePlan) per direction."""
-    from .eplan import build_edge_plan
-    src, dst = edge_index[0], edge_index[1]
-    w = edge_weights(src, dst, edge_type, num_relations, aggr)
+    from .eplan import build_edge_plan, check_ep_ranges
     fb, fe = fwd_range if fwd_range is not None else (0, n_nodes)
     bb, be = bwd_range if bwd_range is not None else (0, n_nodes)
+    check_ep_ranges(paths, [((fb, fe), (bb, be))])
+    src, dst = edge_index[0], edge_index[1]
+    w = edge_weights(src, dst, edge_type, num_relations, aggr)
     gp = GraphPlans(fwd=None, bwd=None, num_edges=int(edge_type.shape[0]))
     from .eplan import HEAVY
     if paths[0] == "ep":
@@ -730,11 +731,13 @@ def build_graph_plans_device(edge_index: Tensor, edge_type: Tensor, n_nodes: int
     edge-parallel direction are the WHOLE graph's, their rows dealt over the ranks (eplan.SharedHeavy, returned in
     ``extras["shared_fwd"]`` / ``["shared_bwd"]``); the pieces' plans hold the light rows and the pseudo rows of their own segments."""
     from . import _lib
+    from .eplan import check_ep_ranges
     if chunk not in CHUNKS and chunk != CHUNK_112:
         raise ValueError(f"chunk must be one of {CHUNKS} (or {CHUNK_112})")
+    rs = ranges if ranges is not None else [(fwd_range or (0, n_nodes), bwd_range or (0, n_nodes))]
+    check_ep_ranges(paths, rs)
     graph, keep = _lib.graph_struct(edge_index, edge_type, n_nodes, num_relations)
     e = int(edge_type.shape[0])
-    rs = ranges if ranges is not None else [(fwd_range or (0, n_nodes), bwd_range or (0, n_nodes))]
     own_max = max([1] + [max(f[1] - f[0], b[1] - b[0]) for f, b in rs] + ([rank_dw_range[1] - rank_dw_range[0]] if rank_dw_range else []))
     ws_tile = min(tile, _lib.dw_tiles_geometry()[0]) if dw_tiles else tile      # the smallest tile sizes the group arrays
     ws = _lib.plan_workspace(e, own_max, num_relations, ws_tile, edge_type.device)
