@@ -22,7 +22,7 @@
  *   - float32 features, int32 indices.  Feature row strides (ld*) are in ELEMENTS, must be multiples
  *     of 4 (16-byte rows) and >= the feature width; columns between the width and the width rounded
  *     up to a multiple of 4 must hold zeros (the Python host pads when needed).
- *   - feature widths 1..128 per side.
+ *   - feature widths 1..128 per side (rgcn_xwide_*: 1..RGCN_XWIDE_MAX_WIDTH).
  */
 #ifndef RGCN_MI355X_H
 #define RGCN_MI355X_H
@@ -34,10 +34,11 @@
 extern "C" {
 #endif
 
-#define RGCN_ABI_VERSION 18
+#define RGCN_ABI_VERSION 19
 #define RGCN_UNIT 64 /* edge slots per unit of the weight-gradient walk (rel_order); a chunk is 1 or 2 units */
 #define RGCN_CHUNK_MAX 128 /* plan->chunk is 64 or 128 edge slots (rows of one LDS ring slot of the forward / dX kernel) */
 #define RGCN_MAX_WIDTH 128
+#define RGCN_XWIDE_MAX_WIDTH 512 /* rgcn_xwide_*: feature widths 1..512 per side */
 #define RGCN_DW_WALKERS 2048 /* waves that walk rel_order side by side in the largest relation-major dW launch (512 workgroups x 4) */
 
 /* activation fused into rgcn_fwd's store (reference model/layers.py:22 F.relu, :24 activation = torch.sigmoid) */
@@ -329,6 +330,29 @@ int rgcn_featureless_bwd(const rgcn_plan_t* plan_t, const int64_t* x_index, cons
                          int64_t in_rows, const float* g, int ldg, int dout, const float* weight, const float* comp, int num_bases,
                          void* workspace, size_t workspace_bytes, float* d_weight, float* d_comp, float* d_root, float* d_bias,
                          void* stream);
+
+/* ---- layers wider than 128 (scaling_rgcn_training_amd/csrc/rgcn_xwide.hip) ---------------------------------------------------
+ * The same layer arithmetic as rgcn_fwd / rgcn_bwd_dx / rgcn_bwd_dw (exact fp32 MFMAs) for 1..RGCN_XWIDE_MAX_WIDTH features per
+ * side; narrower widths are accepted too.  Plans: layout 0, chunk 64 or 128 (rows = chunk), from rgcn_plan_build_* at the
+ * geometry below; layouts 1 / 2 / 3 / 5 answer RGCN_ERR_PLAN.  The weight operand is caller-owned and plain row-major
+ * fp32 [R' + 1, K, N]: block r at r * K * N, the root last (zeros when the layer has none):
+ *   forward: K = din, N = dout, block r = W_r;      dX: K = dout, N = din, block r = W_r^T.
+ * Rows are addressed with 64-bit offsets (no 4 GiB / 2^24-row limit).  Deterministic: fixed summation orders, no atomics.  The
+ * entry points take no flags. */
+/* (tile, chunk) of the forward and transposed plans of a layer din -> dout on a graph of n_nodes nodes (160 KiB of LDS) */
+int rgcn_xwide_geometry(int32_t n_nodes, int din, int dout, int* tile, int* chunk);
+/* out[i] = act(bias + sum_{slots -> i} w_e * x[src_e] @ W_rel) as rgcn_fwd; x [plan->n_nodes, ldx], out [plan->n_owned, ldo],
+ * columns dout .. roundup4(dout) of out written as zeros; bias [dout] or NULL; act RGCN_ACT_*. */
+int rgcn_xwide_fwd(const rgcn_plan_t* plan, const float* x, int ldx, int din, const float* weight, const float* bias, float* out,
+                   int ldo, int dout, int act, void* stream);
+/* dX on the TRANSPOSED plan with the transposed operand, as rgcn_bwd_dx (relu_of: NULL or [plan_t->n_owned, ldr]). */
+int rgcn_xwide_bwd_dx(const rgcn_plan_t* plan_t, const float* g, int ldg, int dout, const float* weight_t, float* dx, int lddx,
+                      int din, const float* relu_of, int ldr, void* stream);
+/* d_weight [R', din, dout], d_root [din, dout], d_bias [dout] on the FORWARD plan, as rgcn_bwd_dw; any of them may be NULL.
+ * Partial slabs in `workspace` are summed in a fixed order.  The query answers 0 on bad arguments. */
+size_t rgcn_xwide_bwd_dw_workspace_bytes(const rgcn_plan_t* plan, int din, int dout);
+int rgcn_xwide_bwd_dw(const rgcn_plan_t* plan, const float* x, int ldx, int din, const float* g, int ldg, int dout, void* workspace,
+                      size_t workspace_bytes, float* d_weight, float* d_root, float* d_bias, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RGCN_LIB: an alternative build of the same library (kernel experiments: tools/debug/)
 LIB_PATH = os.environ.get("RGCN_LIB") or os.path.join(_HERE, "librgcn_mi355x.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 EXPORTS = (
     "rgcn_abi_version", "rgcn_status_string", "rgcn_padded_width", "rgcn_packed_weight_floats",
@@ -24,7 +24,9 @@ EXPORTS = (
     "rgcn_bwd_dw_root_workspace_bytes", "rgcn_bwd_dw_root", "rgcn_ep_transform", "rgcn_ep_segment_sum",
     "rgcn_pack_weights_basis", "rgcn_pack_weights_block", "rgcn_basis_backward", "rgcn_block_backward", "rgcn_eplan_segments",
     "rgcn_featureless_geometry", "rgcn_featureless_fwd", "rgcn_featureless_bwd_workspace_bytes", "rgcn_featureless_bwd",
+    "rgcn_xwide_geometry", "rgcn_xwide_fwd", "rgcn_xwide_bwd_dx", "rgcn_xwide_bwd_dw_workspace_bytes", "rgcn_xwide_bwd_dw",
 )
+XWIDE_MAX_WIDTH = 512  # RGCN_XWIDE_MAX_WIDTH
 
 # enum rgcn_act / RGCN_FLAG_* of include/rgcn_mi355x.h
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
@@ -148,6 +150,16 @@ def load() -> C.CDLL:
     lib.rgcn_featureless_bwd.restype = i32
     lib.rgcn_featureless_bwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, vp, vp, i64, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
                                          vp, vp, vp]
+    lib.rgcn_xwide_geometry.restype = i32
+    lib.rgcn_xwide_geometry.argtypes = [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.rgcn_xwide_fwd.restype = i32
+    lib.rgcn_xwide_fwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]
+    lib.rgcn_xwide_bwd_dx.restype = i32
+    lib.rgcn_xwide_bwd_dx.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, vp, i32, i32, vp, i32, vp]
+    lib.rgcn_xwide_bwd_dw_workspace_bytes.restype = sz
+    lib.rgcn_xwide_bwd_dw_workspace_bytes.argtypes = [C.POINTER(RgcnPlanStruct), i32, i32]
+    lib.rgcn_xwide_bwd_dw.restype = i32
+    lib.rgcn_xwide_bwd_dw.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, vp]
     if lib.rgcn_abi_version() != ABI_VERSION:
         raise RgcnLibraryError(f"ABI version mismatch: library {lib.rgcn_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -526,3 +538,40 @@ def featureless_bwd(ps_t: RgcnPlanStruct, x_index: Optional[torch.Tensor], inv: 
         check(lib.rgcn_featureless_bwd(C.byref(ps_t), _ptr(x_index), _ptr(ip), _ptr(ii), int(in_rows), g.data_ptr(), g.stride(0),
                                        int(dout), weight.data_ptr(), _ptr(comp), nb, ws.data_ptr(), nbytes, _ptr(d_weight),
                                        _ptr(d_comp), _ptr(d_root), _ptr(d_bias), _stream(g)), "rgcn_featureless_bwd")
+
+
+# ---- layers wider than 128 (csrc/rgcn_xwide.hip) --------------------------------------------------------------------
+def xwide_geometry(n_nodes: int, din: int, dout: int):
+    """(tile, chunk) of the forward and transposed plans of a wide layer (rgcn_xwide_geometry)"""
+    tile, chunk = C.c_int(), C.c_int()
+    check(load().rgcn_xwide_geometry(int(n_nodes), int(din), int(dout), C.byref(tile), C.byref(chunk)), "rgcn_xwide_geometry")
+    return tile.value, chunk.value
+
+
+def xwide_fwd(ps: RgcnPlanStruct, x: torch.Tensor, din: int, weight: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor,
+              dout: int, act: int = ACT_NONE) -> None:
+    """``weight``: the row-major operand [R' + 1, din, dout] (root last)"""
+    with torch.cuda.device(x.device):
+        check(load().rgcn_xwide_fwd(C.byref(ps), x.data_ptr(), x.stride(0), int(din), weight.data_ptr(), _ptr(bias), out.data_ptr(),
+                                    out.stride(0), int(dout), int(act), _stream(x)), "rgcn_xwide_fwd")
+
+
+def xwide_bwd_dx(ps_t: RgcnPlanStruct, g: torch.Tensor, dout: int, weight_t: torch.Tensor, dx: torch.Tensor, din: int,
+                 relu_of: Optional[torch.Tensor] = None) -> None:
+    """``weight_t``: the row-major operand [R' + 1, dout, din] (blocks W_r^T, root last)"""
+    with torch.cuda.device(g.device):
+        check(load().rgcn_xwide_bwd_dx(C.byref(ps_t), g.data_ptr(), g.stride(0), int(dout), weight_t.data_ptr(), dx.data_ptr(),
+                                       dx.stride(0), int(din), _ptr(relu_of), 0 if relu_of is None else relu_of.stride(0), _stream(g)),
+              "rgcn_xwide_bwd_dx")
+
+
+def xwide_bwd_dw(ps: RgcnPlanStruct, x: torch.Tensor, din: int, g: torch.Tensor, dout: int, d_weight: Optional[torch.Tensor],
+                 d_root: Optional[torch.Tensor], d_bias: Optional[torch.Tensor]) -> None:
+    lib = load()
+    nbytes = lib.rgcn_xwide_bwd_dw_workspace_bytes(C.byref(ps), int(din), int(dout))
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_xwide_bwd_dw_workspace_bytes refused the plan")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib.rgcn_xwide_bwd_dw(C.byref(ps), x.data_ptr(), x.stride(0), int(din), g.data_ptr(), g.stride(0), int(dout),
+                                    ws.data_ptr(), nbytes, _ptr(d_weight), _ptr(d_root), _ptr(d_bias), _stream(x)), "rgcn_xwide_bwd_dw")

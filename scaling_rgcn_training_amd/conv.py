@@ -1,7 +1,8 @@
 """``RGCNConv``: constructor-, attribute- and forward-compatible with PyG 2.3.1
 ``torch_geometric.nn.RGCNConv`` as the reference uses it (/root/reference/model/layers.py:15-16,
 21-23, 33-46), with forward and backward running as the HIP kernels of
-``csrc/rgcn_tile_fp32*.hip`` / ``rgcn_tile3p.hip`` / ``rgcn_ep.hip`` / ``rgcn_dw_*.hip`` through the C ABI of ``include/rgcn_mi355x.h``.
+``csrc/rgcn_tile_fp32*.hip`` / ``rgcn_tile3p.hip`` / ``rgcn_ep.hip`` / ``rgcn_dw_*.hip`` through the C ABI of ``include/rgcn_mi355x.h``
+(layers with a side above 128, opt-in ``wide=True``: ``csrc/rgcn_xwide.hip``).
 
 Mutability contract (model/layers.py:33-46, model/modelTrainer.py:26-39): ``weight`` / ``root`` /
 ``bias`` are plain ``nn.Parameter`` attributes that callers REPLACE after construction and may
@@ -41,6 +42,9 @@ def _rows16(t: Tensor, width: int) -> Tensor:
 _SPLIT_PRODUCERS_DEFAULT = os.environ.get("RGCN_SPLIT_PRODUCERS", "1")
 _MERGE_RUNS_DEFAULT = os.environ.get("RGCN_MERGE_RUNS", "1") == "1"
 _PATH_DEFAULT = os.environ.get("RGCN_PATH", "auto")       # auto | ring | ep
+# layers with up to 512 features per side on the kernels of csrc/rgcn_xwide.hip: RGCNConv(..., wide=None) takes this default
+_WIDE_DEFAULT = os.environ.get("RGCN_WIDE", "0") == "1"
+NARROW_MAX_WIDTH = 128          # RGCN_MAX_WIDTH: the widest side the other kernels take
 SPLIT_PRODUCERS_TILE = 224       # the largest tile whose fp32 accumulator fits beside the kernel's two 48 KiB ring slots
 # exact-fp32 forward / dX of 64 x 64 layers on layout-3 plans (round 4): the largest tile it takes.  Measured at the headline
 # config, forward / dX launch, A/B on one box (profiles/r04g_exact_merge_timing.txt): layout 0 at the cost model's 352: 10.42 /
@@ -235,6 +239,35 @@ def _gather_pieces(dctx: "DistContext", plans_list, launch, ld: int, n: int, dev
     return full[:n]
 
 
+def _xwide_operand(wf: Tensor, cp: Optional[Tensor], rt: Optional[Tensor], num_rel: int, din: int, dout: int,
+                   transpose: bool) -> Tensor:
+    """The weight operand of rgcn_xwide_*: row-major [R' + 1, K, N], relation blocks then the root (zeros without one); blocks W_r
+    (forward) or W_r^T (dX).  A basis or block-diagonal decomposition is composed into it by torch ops."""
+    if cp is not None:
+        w = (cp @ wf.view(wf.shape[0], -1)).view(num_rel, din, dout)
+    elif wf.dim() == 4:
+        eye = torch.eye(wf.shape[1], device=wf.device, dtype=wf.dtype)
+        w = torch.einsum("rbio,bc->rbico", wf, eye).reshape(num_rel, din, dout)
+    else:
+        w = wf
+    r = rt if rt is not None else torch.zeros(din, dout, dtype=torch.float32, device=wf.device)
+    op = torch.cat([w, r.unsqueeze(0)], 0)
+    return op.transpose(1, 2).contiguous() if transpose else op
+
+
+def _xwide_decomposed_grads(dw: Tensor, wf: Tensor, cp: Optional[Tensor], need_weight: bool, need_comp: bool):
+    """(d_weight, d_comp) of a decomposition from the dense d_W [R', in, out] scratch of rgcn_xwide_bwd_dw, by torch ops:
+    basis d_bases = comp^T d_W, d_comp[r, b] = <d_W[r], bases[b]>; blocks: the diagonal blocks of d_W."""
+    r = dw.shape[0]
+    if cp is not None:
+        flat = dw.view(r, -1)
+        dv = (cp.t() @ flat).view_as(wf) if need_weight else None
+        dc = flat @ wf.view(wf.shape[0], -1).t() if need_comp else None
+        return dv, dc
+    nb, bi, bo = wf.shape[1], wf.shape[2], wf.shape[3]
+    return dw.view(r, nb, bi, nb, bo).diagonal(dim1=1, dim2=3).permute(0, 3, 1, 2).contiguous(), None
+
+
 def _shared_heavy_sums(shared, x: Tensor, width: int, dctx: "DistContext") -> Optional[Tensor]:
     """H[segment] = sum of the weighted rows of every heavy (node, relation) segment of the WHOLE graph: this rank's share of the
     rows (rgcn_ep_segment_sum), then one all-reduce over the ranks (eplan.SharedHeavy)"""
@@ -251,12 +284,12 @@ def _shared_heavy_sums(shared, x: Tensor, width: int, dctx: "DistContext") -> Op
 
 class _RGCNLayerFn(torch.autograd.Function):
     """a = act(sum_r mean-aggregate_r(x) @ W_r + x @ root + bias)   (forward: rgcn_fwd with the activation fused
-    into its store; backward: rgcn_bwd_dx on the transposed plan + rgcn_bwd_dw)."""
+    into its store; backward: rgcn_bwd_dx on the transposed plan + rgcn_bwd_dw; ``xwide``: rgcn_xwide_fwd / _bwd_dx / _bwd_dw)."""
 
     @staticmethod
     def forward(ctx, x: Tensor, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor],
                 plans: GraphPlans, dctx: Optional[DistContext], act: int, input_relu: bool, grad_premasked: bool,
-                flags: int, num_rel: int, dout: int):
+                flags: int, num_rel: int, dout: int, xwide: bool = False):
         # weight / comp: the layer's OWN parameters -- dense [R, in, out], bases [B, in, out] + comp [R, B], or blocks
         # [R, nb, in / nb, out / nb]: a decomposition is composed inside the weight packer and differentiated from the dense
         # d_W scratch of the weight-gradient kernels (rgcn_pack_weights_basis / _block, rgcn_basis_backward / rgcn_block_backward),
@@ -268,9 +301,15 @@ class _RGCNLayerFn(torch.autograd.Function):
         cp = None if comp is None else comp.detach().float().contiguous()
         rt = None if root is None else root.detach().float().contiguous()
         bs = None if bias is None else bias.detach().float().contiguous()
-        packed = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
+        packed = None if xwide else _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
         ldo = _round4(dout)
-        if dctx is None and plans.ep_fwd is not None:
+        if xwide:
+            # layers with a side above 128: the dense [R' + 1, in, out] operand instead of the MFMA-fragment pack
+            out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
+            op = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=False)
+            _lib.xwide_fwd(_lib.plan_struct(fp), xp, din, op, bs, out, dout, act)
+            del op
+        elif dctx is None and plans.ep_fwd is not None:
             # edge-parallel path (eplan.py): relation-major dense units -> weighted products per slot -> per-destination sums
             out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
             ctx.ep_heavy = _lib.ep_layer(plans.ep_fwd, xp, din, packed, bs, out, dout, act, None, flags)
@@ -298,6 +337,7 @@ class _RGCNLayerFn(torch.autograd.Function):
         ctx.dims = (n, din, dout, num_rel)
         ctx.has_root, ctx.has_bias = root is not None, bias is not None
         ctx.act, ctx.input_relu, ctx.flags = act, input_relu, flags
+        ctx.xwide = xwide
         # the activated output is only needed to differentiate the activation; a ReLU whose consumer folds the mask
         # into its dX store (grad_premasked) needs nothing
         need_a = act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
@@ -322,6 +362,9 @@ class _RGCNLayerFn(torch.autograd.Function):
         need_root = need_root and ctx.has_root
         need_bias = need_bias and ctx.has_bias
         dev = g.device
+        if ctx.xwide:
+            return _RGCNLayerFn._backward_xwide(ctx, xp, wf, cp, rt, gp, need_x, need_w, need_wparam, need_comp, need_root,
+                                                need_bias)
         # ONE flat buffer for the three weight gradients (a single all-reduce in the distributed case)
         sizes = [num_rel * din * dout if need_w else 0, din * dout if need_root else 0, dout if need_bias else 0]
 
@@ -446,7 +489,31 @@ class _RGCNLayerFn(torch.autograd.Function):
         dcomp = None
         if decomposed and dw is not None:
             dw, dcomp = _lib.decomposed_weight_grads(dw.contiguous(), wf, cp, need_wparam, need_comp)
-        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None
+        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None, None
+
+    @staticmethod
+    def _backward_xwide(ctx, xp, wf, cp, rt, gp, need_x, need_w, need_wparam, need_comp, need_root, need_bias):
+        """backward of a layer with a side above 128: dX on the transposed plan, the weight gradients on the forward plan
+        (csrc/rgcn_xwide.hip); a decomposition's gradients from the dense d_W scratch, which is dropped here"""
+        n, din, dout, num_rel = ctx.dims
+        plans, dev = ctx.plans, gp.device
+        dx = dw = droot = dbias = dcomp = None
+        if need_x:
+            opt = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=True)
+            ldx = _round4(din)
+            dxp = torch.empty(n, ldx, dtype=torch.float32, device=dev)
+            _lib.xwide_bwd_dx(_lib.plan_struct(plans.bwd), gp, dout, opt, dxp, din, xp if ctx.input_relu else None)
+            del opt
+            dx = dxp if ldx == din else dxp[:, :din]
+        if need_w or need_root or need_bias:
+            f32 = dict(dtype=torch.float32, device=dev)
+            dw = torch.empty(num_rel, din, dout, **f32) if need_w else None
+            droot = torch.empty(din, dout, **f32) if need_root else None
+            dbias = torch.empty(dout, **f32) if need_bias else None
+            _lib.xwide_bwd_dw(_lib.plan_struct(plans.fwd), xp, din, gp, dout, dw, droot, dbias)
+        if dw is not None and (cp is not None or wf.dim() == 4):
+            dw, dcomp = _xwide_decomposed_grads(dw, wf, cp, need_wparam, need_comp)
+        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None, None
 
 
 class _FeaturelessFn(torch.autograd.Function):
@@ -513,9 +580,11 @@ def _node_index(x: Tensor, in_rows: int):
 def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: Optional[Tensor],
                        plans: GraphPlans, dctx: Optional[DistContext] = None, activation: Optional[str] = None,
                        input_relu: bool = False, grad_premasked: bool = False, flags: int = 0,
-                       comp: Optional[Tensor] = None, num_relations: Optional[int] = None, out_channels: Optional[int] = None) -> Tensor:
+                       comp: Optional[Tensor] = None, num_relations: Optional[int] = None, out_channels: Optional[int] = None,
+                       xwide: bool = False) -> Tensor:
     """weight: dense [R, in, out]; or, with ``comp [R, B]``, the bases [B, in, out]; or blocks [R, nb, in / nb, out / nb]
-    (then ``out_channels`` = nb * weight.shape[3])."""
+    (then ``out_channels`` = nb * weight.shape[3]).  ``xwide``: the kernels of csrc/rgcn_xwide.hip (1..512 per side; ``plans``
+    at rgcn_xwide_geometry, layout 0, single GPU)."""
     if x.device.type != "cuda":
         raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
     if activation not in _ACT_CODES:
@@ -528,7 +597,7 @@ def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: 
     else:
         num_rel, dout = int(weight.shape[0]), int(weight.shape[2])
     return _RGCNLayerFn.apply(x, weight, comp, root, bias, plans, dctx, _ACT_CODES[activation], bool(input_relu),
-                              bool(grad_premasked), int(flags), num_relations or num_rel, out_channels or dout)
+                              bool(grad_premasked), int(flags), num_relations or num_rel, out_channels or dout, bool(xwide))
 
 
 def glorot_(t: Tensor) -> Tensor:
@@ -552,17 +621,25 @@ class RGCNConv(nn.Module):
     ``featureless=True`` (opt-in): PyG's featureless mode, ``x`` is ``None`` (then N = ``in_channels``) or an int64 ``[N]``
     node-index tensor and every table ``W_r [in,out]`` is a per-node embedding (``in_channels`` = table rows, any positive
     int); kernels of ``csrc/rgcn_featureless.hip``.  Not with ``num_blocks`` nor a ``dist`` context.
+
+    ``wide`` (opt-in; ``None``: ``RGCN_WIDE=1`` in the environment at import time switches it on): up to 512 features per side.
+    A layer with both sides at most 128 runs exactly as without it; one with a side above 128 runs on the kernels of
+    ``csrc/rgcn_xwide.hip`` (exact fp32) -- one GPU, no ``dist`` context, ``path`` not pinned to ``"ep"``.  Not with ``featureless``.
     """
 
     def __init__(self, in_channels: int, out_channels: int, num_relations: int,
                  num_bases: Optional[int] = None, num_blocks: Optional[int] = None, aggr: str = "mean",
                  root_weight: bool = True, is_sorted: bool = False, bias: bool = True, featureless: bool = False,
-                 **kwargs):
+                 wide: Optional[bool] = None, **kwargs):
         super().__init__()
         if num_bases is not None and num_blocks is not None:
             raise ValueError("Can not apply both basis-decomposition and block-diagonal-decomposition "
                              "at the same time.")
         self.featureless = bool(featureless)
+        if self.featureless and wide:
+            raise ValueError("featureless RGCNConv has no wide mode: its tables stay at 1..128 columns")
+        # (a featureless layer under RGCN_WIDE=1 keeps its own limit)
+        self.wide = (_WIDE_DEFAULT if wide is None else bool(wide)) and not self.featureless
         if self.featureless:
             if num_blocks is not None:
                 raise ValueError("Block-diagonal decomposition not supported for non-continuous input features.")
@@ -619,7 +696,10 @@ class RGCNConv(nn.Module):
             self.bias = nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
-        if not self.featureless:
+        if self.wide:
+            if not (1 <= in_channels <= _lib.XWIDE_MAX_WIDTH and 1 <= out_channels <= _lib.XWIDE_MAX_WIDTH):
+                raise ValueError(f"wide RGCNConv widths must be in 1..{_lib.XWIDE_MAX_WIDTH}, got {in_channels}->{out_channels}")
+        elif not self.featureless:
             tile_for(in_channels, out_channels)  # validates the widths early
         self.reset_parameters()
 
@@ -693,10 +773,17 @@ class RGCNConv(nn.Module):
         return (not self.split_producers and self.merge_runs and chunk == 128
                 and padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64)
 
+    @property
+    def xwide(self) -> bool:
+        """whether this layer runs on the kernels of csrc/rgcn_xwide.hip: ``wide`` and a side above 128"""
+        return self.wide and max(self.in_channels, self.out_channels) > NARROW_MAX_WIDTH
+
     def layout(self, n_nodes: int, n_edges: int) -> Tuple[int, int]:
         """(tile, chunk) of this layer's plans on a graph of that size: ``layout_for``, capped at the producer-split kernel's
         tile where that kernel will run (dist.attach aligns the ranks' node ranges to the same tile), or at the tile that leaves
         the exact-fp32 kernel's chunks room for their shadow row tiles where it will walk layout-3 plans."""
+        if self.xwide:
+            raise NotImplementedError("RGCNConv wider than 128 runs on one GPU only: no dist layout")
         tile, chunk = layout_for(self.in_channels, self.out_channels, n_nodes, n_edges, self.num_relations)
         if self._use_split_producers(128):
             # 64 x 64 with the bf16 x 3 kernel available: its own layout (128-slot chunks, tiles up to 224, its own cycles per chunk
@@ -735,6 +822,8 @@ class RGCNConv(nn.Module):
                                       "(x is always float: model/layers.py:21,62,108) and is not built")
         if x.dim() != 2 or x.shape[1] != self.in_channels:
             raise ValueError(f"x must be [N, {self.in_channels}], got {tuple(x.shape)}")
+        if self.xwide:
+            return self._forward_xwide(x, edge_index, edge_type, _activation, _input_relu, _grad_premasked)
         plans = self._plans(x, edge_index, edge_type)
         flags = self.kernel_flags
         # (the arithmetic mode follows the layer and the graph's size -- the chunk of self.layout -- not which path the other
@@ -746,6 +835,23 @@ class RGCNConv(nn.Module):
         return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, self.dist,
                                   _activation, _input_relu, _grad_premasked and _activation == "relu", flags,
                                   comp=self.comp, num_relations=self.num_relations, out_channels=self.out_channels)
+
+    def _forward_xwide(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, activation: Optional[str], input_relu: bool,
+                       grad_premasked: bool) -> Tensor:
+        if self.dist is not None:
+            raise NotImplementedError("RGCNConv wider than 128 runs on one GPU: a dist context is not supported")
+        paths = (self.path,) if isinstance(self.path, str) else tuple(self.path)
+        if "ep" in paths:
+            raise ValueError("RGCNConv wider than 128 has no edge-parallel path: path must be 'auto' or 'ring'")
+        if x.device.type != "cuda":
+            raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+        n = int(x.shape[0])
+        tile, chunk = _lib.xwide_geometry(max(n, 1), self.in_channels, self.out_channels)
+        plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, split=False,
+                                   dw_tiles=False, paths=("ring", "ring"), extra_key=("xwide",))
+        return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, None, activation, input_relu,
+                                  grad_premasked and activation == "relu", 0, comp=self.comp, num_relations=self.num_relations,
+                                  out_channels=self.out_channels, xwide=True)
 
     def _forward_featureless(self, x: Optional[Tensor], edge_index: Tensor, edge_type: Tensor) -> Tensor:
         if self.dist is not None:
