@@ -190,11 +190,11 @@ def plan_struct(plan) -> RgcnPlanStruct:
         raise RgcnLibraryError("the graph plan must live on the GPU (plan tensors are on %s)" % plan.slot_src.device)
     plan._cstruct = RgcnPlanStruct(
         plan.n_nodes, plan.n_owned, plan.num_relations, plan.tile, plan.n_tiles, plan.n_chunks, plan.chunk, plan.n_units,
-        int(getattr(plan, "layout", 0)), int(getattr(plan, "chunk_rows", 0) or plan.chunk),
+        int(plan.layout), int(plan.chunk_rows or plan.chunk),
         plan.tile_ptr.data_ptr(), plan.chunk_rel.data_ptr(), plan.chunk_cnt.data_ptr(),
         plan.chunk_tile.data_ptr(), plan.chunk_flags.data_ptr(), plan.rel_order.data_ptr(), plan.slot_src.data_ptr(),
         plan.slot_w.data_ptr(), plan.slot_row.data_ptr(), plan.slot_acc.data_ptr(),
-        _ptr(getattr(plan, "slot_src2", None)))
+        _ptr(plan.slot_src2))
     return plan._cstruct
 
 
@@ -433,10 +433,10 @@ def ep_segment_sum(src: torch.Tensor, ptr: torch.Tensor, idx, w, n_out: int, wid
 def ep_aggregate_heavy(ep, x: torch.Tensor, din: int) -> Optional[torch.Tensor]:
     """H[seg] = sum_e w_e x[src_e] over the rows of every heavy (destination, relation) segment of the plan (eplan.HeavyPart):
     rgcn_ep_segment_sum over x itself, weighted, in levels.  None when the plan has no heavy part."""
-    h = getattr(ep, "heavy", None)
+    h = ep.heavy
     if h is None:
         return None
-    if getattr(h, "shared", None) is not None:
+    if h.shared is not None:
         raise RgcnLibraryError("this plan's heavy segments are shared across ranks: H comes from ep_aggregate_shared + all-reduce")
     cur = x
     for ptr, idx, w, n_out in h.levels:
@@ -468,7 +468,7 @@ def ep_layer(ep, x: torch.Tensor, din: int, packed: torch.Tensor, bias: Optional
     lib = load()
     ldz = out.stride(0)
     st = _stream(x)
-    h = getattr(ep, "heavy", None)
+    h = ep.heavy
     if hmat is None:      # (given: the all-reduced H of the heavy segments shared across ranks)
         hmat = ep_aggregate_heavy(ep, x, din)
     with torch.cuda.device(x.device):

@@ -14,13 +14,14 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib
-from .plan import GraphPlans, TilePlan, cached_graph_plans
+from .plan import GraphPlans, TilePlan, cached_graph_plans, choose_layout, padded_width
 
 
 def _round4(n: int) -> int:
@@ -38,7 +39,7 @@ def _rows16(t: Tensor, width: int) -> Tensor:
 
 
 # forward / dX on the bf16 x 3 kernel whose PRODUCER waves split the gathered rows (csrc/rgcn_tile3p.hip):
-# fp32-equivalent arithmetic; layers padded to 64 x 64 on graphs dense enough for 128-slot chunks.  "1" / "0" / "auto"
+# fp32-equivalent arithmetic; layers padded to 64 x 64 on graphs dense enough for 128-slot chunks.  "1": on, anything else: off
 _SPLIT_PRODUCERS_DEFAULT = os.environ.get("RGCN_SPLIT_PRODUCERS", "1")
 _MERGE_RUNS_DEFAULT = os.environ.get("RGCN_MERGE_RUNS", "1") == "1"
 _PATH_DEFAULT = os.environ.get("RGCN_PATH", "auto")       # auto | ring | ep
@@ -74,9 +75,7 @@ def layout_for(in_channels: int, out_channels: int, n_nodes: int = 0, n_edges: i
     the wider side, tuned to the graph's density."""
     if not (1 <= in_channels <= 128 and 1 <= out_channels <= 128):
         raise ValueError(f"RGCNConv widths must be in 1..128, got {in_channels}->{out_channels}")
-    from .plan import choose_layout
-    tile, chunk = choose_layout(n_nodes, n_edges, num_relations, in_channels, out_channels)
-    return tile, chunk
+    return choose_layout(n_nodes, n_edges, num_relations, in_channels, out_channels)
 
 
 def tile_for(in_channels: int, out_channels: int, n_nodes: int = 0, n_edges: int = 0, num_relations: int = 1) -> int:
@@ -131,6 +130,7 @@ class DistContext:
         self.stats = {"all_gather": 0, "all_gather_bytes": 0, "all_reduce": 0, "all_reduce_bytes": 0,
                       "wait_events": []}
         self.time_waits = False     # bench.py: HIP events around the waits on the collectives, piece by piece
+        self.poison_unread = False  # tests: a row no exchange wrote is a NaN wherever it is read
 
     @property
     def total_rows(self) -> int:
@@ -168,7 +168,7 @@ def _gather_pieces(dctx: "DistContext", plans_list, launch, ld: int, n: int, dev
     gathered rows and run under the dX exchange) a pair (matrix, finish) -- ``finish()`` makes the current stream wait for what
     is still in flight."""
     full = torch.empty(max(dctx.total_rows, n), ld, dtype=dtype, device=device)
-    if getattr(dctx, "poison_unread", False):      # tests: a row no exchange wrote is a NaN wherever it is read
+    if dctx.poison_unread:
         full.fill_(float("nan"))
     handles = []
     w = dctx.world
@@ -282,40 +282,74 @@ def _shared_heavy_sums(shared, x: Tensor, width: int, dctx: "DistContext") -> Op
     return hmat
 
 
+def _operands(*params):
+    """the layer's parameters as the kernels read them: detached, float32, contiguous (None stays None)"""
+    return [None if p is None else p.detach().float().contiguous() for p in params]
+
+
+def _launch_fwd(pl, xp: Tensor, din: int, packed: Tensor, bs: Optional[Tensor], rows: Tensor, dout: int, act: int, flags: int,
+                hmat: Optional[Tensor] = None) -> Optional[Tensor]:
+    """forward of one plan into ``rows``: rgcn_fwd, or the edge-parallel path for an eplan.EdgePlan (returns its H)"""
+    if not isinstance(pl, TilePlan):
+        return _lib.ep_layer(pl, xp, din, packed, bs, rows, dout, act, None, flags, hmat=hmat)
+    _lib.fwd(_lib.plan_struct(pl), xp, din, packed, bs, rows, dout, act, flags)
+
+
+def _launch_dx(pl, gp: Tensor, dout: int, packed_t: Tensor, rows: Tensor, din: int, mask: Optional[Tensor], flags: int,
+               hmat: Optional[Tensor] = None):
+    """dX of one transposed plan into ``rows``: rgcn_bwd_dx, or the edge-parallel path for an eplan.EdgePlan"""
+    if not isinstance(pl, TilePlan):
+        return _lib.ep_layer(pl, gp, dout, packed_t, None, rows, din, _lib.ACT_NONE, mask, flags, hmat=hmat)
+    _lib.bwd_dx(_lib.plan_struct(pl), gp, dout, packed_t, rows, din, mask, flags)
+
+
+def _dw_tiles(dwp: TilePlan, walk: Tensor, xp: Tensor, din: int, gp: Tensor, dout: int, parts, flags: int) -> None:
+    """d_weight by the tile-major kernel on ``dwp`` and d_root / d_bias by the plan-free streaming kernel, over the rows [b, e)
+    ``dwp`` owns, into ``parts`` = (d_weight, d_root, d_bias) views of the flat buffer: a kernel whose views are None is skipped"""
+    pw, pr, pb = parts
+    b, e = dwp.node_begin, dwp.node_end
+    if pw is not None:
+        _lib.bwd_dw_tiles(_lib.plan_struct(dwp), walk, xp, din, gp[b:e], dout, pw, flags)
+    if pr is not None or pb is not None:
+        _lib.bwd_dw_root(xp[b:e], din, gp[b:e], dout, pr, pb)
+
+
+def _dw_walk(pc: GraphPlans, xp: Tensor, din: int, gp: Tensor, dout: int, parts, flags: int, hmat: Optional[Tensor]) -> None:
+    """one piece's weight gradients by the relation-major kernels on its forward plan's units (GraphPlans.fwd_walk), plus an
+    edge-parallel forward's heavy segments: d_W_r += H_seg^T g[dst] over their pseudo rows (``hmat``: H of the forward)"""
+    fp = pc.fwd_walk
+    pw, pr, pb = parts
+    gr = gp[fp.node_begin:fp.node_end]
+    _lib.bwd_dw(_lib.plan_struct(fp), xp, din, gr, dout, pw, pr, pb, flags)
+    epf = pc.ep_fwd
+    if pw is not None and epf is not None and epf.heavy is not None:
+        if hmat is None:
+            hmat = _lib.ep_aggregate_heavy(epf, xp, din)
+        pw2 = torch.empty_like(pw)
+        _lib.bwd_dw(_lib.plan_struct(epf.heavy_tile_plan()), hmat, din, gr, dout, pw2, None, None, flags)
+        pw.add_(pw2)
+
+
 class _RGCNLayerFn(torch.autograd.Function):
     """a = act(sum_r mean-aggregate_r(x) @ W_r + x @ root + bias)   (forward: rgcn_fwd with the activation fused
-    into its store; backward: rgcn_bwd_dx on the transposed plan + rgcn_bwd_dw; ``xwide``: rgcn_xwide_fwd / _bwd_dx / _bwd_dw)."""
+    into its store; backward: rgcn_bwd_dx on the transposed plan + the weight-gradient kernels)."""
 
     @staticmethod
     def forward(ctx, x: Tensor, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor],
                 plans: GraphPlans, dctx: Optional[DistContext], act: int, input_relu: bool, grad_premasked: bool,
-                flags: int, num_rel: int, dout: int, xwide: bool = False):
+                flags: int, num_rel: int, dout: int):
         # weight / comp: the layer's OWN parameters -- dense [R, in, out], bases [B, in, out] + comp [R, B], or blocks
         # [R, nb, in / nb, out / nb]: a decomposition is composed inside the weight packer and differentiated from the dense
         # d_W scratch of the weight-gradient kernels (rgcn_pack_weights_basis / _block, rgcn_basis_backward / rgcn_block_backward),
         # so autograd never holds an [R, in, out] tensor (PyG materialises it on every call)
         n, din = x.shape
-        fp: Optional[TilePlan] = plans.fwd if dctx is None else None
         xp = _rows16(x, din)
-        wf = weight.detach().float().contiguous()
-        cp = None if comp is None else comp.detach().float().contiguous()
-        rt = None if root is None else root.detach().float().contiguous()
-        bs = None if bias is None else bias.detach().float().contiguous()
-        packed = None if xwide else _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
+        wf, cp, rt, bs = _operands(weight, comp, root, bias)
+        packed = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
         ldo = _round4(dout)
-        if xwide:
-            # layers with a side above 128: the dense [R' + 1, in, out] operand instead of the MFMA-fragment pack
+        if dctx is None:
             out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
-            op = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=False)
-            _lib.xwide_fwd(_lib.plan_struct(fp), xp, din, op, bs, out, dout, act)
-            del op
-        elif dctx is None and plans.ep_fwd is not None:
-            # edge-parallel path (eplan.py): relation-major dense units -> weighted products per slot -> per-destination sums
-            out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
-            ctx.ep_heavy = _lib.ep_layer(plans.ep_fwd, xp, din, packed, bs, out, dout, act, None, flags)
-        elif dctx is None:
-            out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
-            _lib.fwd(_lib.plan_struct(fp), xp, din, packed, bs, out, dout, act, flags)
+            ctx.ep_heavy = _launch_fwd(plans.fwd or plans.ep_fwd, xp, din, packed, bs, out, dout, act, flags)
         else:
             # every rank computes its own blocks straight into the gathered buffer; with destination-range
             # ownership the per-layer all-reduce of SURVEY.md 8e degenerates to an all-gather (each row has
@@ -323,26 +357,16 @@ class _RGCNLayerFn(torch.autograd.Function):
             # (a piece whose forward runs the edge-parallel path -- a hub's block -- carries an eplan.EdgePlan instead)
             # (hubs split across ranks, eplan.SharedHeavy: every rank sums its share of the heavy segments' rows, one all-reduce
             # of the [segments, in] sums, then the owners' pseudo rows go through the transform)
-            hm_f = _shared_heavy_sums(getattr(plans, "shared_fwd", None), xp, din, dctx)
-            ctx.ep_heavy = hm_f
-
-            def launch_fwd(pl, rows):
-                if isinstance(pl, TilePlan):
-                    _lib.fwd(_lib.plan_struct(pl), xp, din, packed, bs, rows, dout, act, flags)
-                else:
-                    _lib.ep_layer(pl, xp, din, packed, bs, rows, dout, act, None, flags, hmat=hm_f)
-            out = _gather_pieces(dctx, [p.fwd if p.fwd is not None else p.ep_fwd for p in plans.pieces], launch_fwd, ldo, n, x.device,
-                                 needed=plans.needed_fwd if dctx.exchange == "needed" else None)
-        ctx.plans, ctx.dctx = plans, dctx
-        ctx.dims = (n, din, dout, num_rel)
-        ctx.has_root, ctx.has_bias = root is not None, bias is not None
-        ctx.act, ctx.input_relu, ctx.flags = act, input_relu, flags
-        ctx.xwide = xwide
+            hm_f = ctx.ep_heavy = _shared_heavy_sums(plans.shared_fwd, xp, din, dctx)
+            out = _gather_pieces(dctx, [p.fwd or p.ep_fwd for p in plans.pieces],
+                                 lambda pl, rows: _launch_fwd(pl, xp, din, packed, bs, rows, dout, act, flags, hm_f), ldo, n,
+                                 x.device, needed=plans.needed_fwd if dctx.exchange == "needed" else None)
+        ctx.plans, ctx.dctx, ctx.dims = plans, dctx, (n, din, dout, num_rel)
+        ctx.input_relu, ctx.flags = input_relu, flags
         # the activated output is only needed to differentiate the activation; a ReLU whose consumer folds the mask
         # into its dX store (grad_premasked) needs nothing
-        need_a = act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
-        ctx.need_a = need_a
-        ctx.save_for_backward(xp, wf, cp, rt, out if need_a else None)
+        ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
+        ctx.save_for_backward(xp, wf, cp, rt, out if ctx.need_a else None)
         return out if ldo == dout else out[:, :dout]
 
     @staticmethod
@@ -350,21 +374,13 @@ class _RGCNLayerFn(torch.autograd.Function):
         xp, wf, cp, rt, a_out = ctx.saved_tensors
         plans, dctx, flags = ctx.plans, ctx.dctx, ctx.flags
         n, din, dout, num_rel = ctx.dims
-        need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]
-        decomposed = cp is not None or wf.dim() == 4
-        need_comp = need_comp and cp is not None
+        need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]      # (False for an input that is None)
         need_w = need_wparam or need_comp              # the dense d_W[R, in, out] (for a decomposition: scratch)
         gp = _rows16(g, dout)
         if ctx.need_a:
             gp = _lib.act_backward(a_out, gp, ctx.act)       # dL/dz = dL/da * act'(a)
-        dx = dw = droot = dbias = None
-        finish_dx = None
-        need_root = need_root and ctx.has_root
-        need_bias = need_bias and ctx.has_bias
         dev = g.device
-        if ctx.xwide:
-            return _RGCNLayerFn._backward_xwide(ctx, xp, wf, cp, rt, gp, need_x, need_w, need_wparam, need_comp, need_root,
-                                                need_bias)
+        dx = acc = finish_dx = side = None
         # ONE flat buffer for the three weight gradients (a single all-reduce in the distributed case)
         sizes = [num_rel * din * dout if need_w else 0, din * dout if need_root else 0, dout if need_bias else 0]
 
@@ -374,107 +390,70 @@ class _RGCNLayerFn(torch.autograd.Function):
                     flat[o0:o1].view(din, dout) if need_root else None,
                     flat[o1:].view(dout) if need_bias else None)
 
-        # Single-GPU layers whose d_weight goes to the tile-major kernel: d_root / d_bias come from the plan-free streaming
-        # kernel (rgcn_bwd_dw_root).  On large graphs it is enqueued on a SIDE stream before the dX launch: it is HBM-bound
-        # with a tenth of a launch's MFMAs, uses no LDS and few registers, so its workgroups share the CUs with the MFMA-bound
-        # dX kernel instead of adding their ~1 ms behind it.  The join is a stream wait, never a host sync.
-        dwp = getattr(plans, "dw", None) if dctx is None else None
-        merged = plans.fwd is not None and getattr(plans.fwd, "layout", 0) == 3 if dctx is None else False
-        tiles_path = (dwp is not None and (need_w or merged) and plans.fwd is not None and plans.fwd.n_owned > 0 and
-                      not (flags & (_lib.FLAG_DW_RING | _lib.FLAG_DW_DIRECT | _lib.FLAG_POINTER_GATHER)) and
-                      _lib.buffer_addressable(n, xp.shape[1]) and _lib.buffer_addressable(n, gp.shape[1]))
-        tiles_part = side = None
-        if tiles_path:
-            tiles_part = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            _, pr, pb = views(tiles_part)
-            if need_root or need_bias:
-                if need_x and n >= _SIDE_STREAM_MIN_ROWS:
-                    side = _side_stream(dev)
-                    side.wait_stream(torch.cuda.current_stream(dev))      # gp (and xp) are produced on the current stream
-                    with torch.cuda.stream(side):
-                        _lib.bwd_dw_root(xp, din, gp, dout, pr, pb)
-                else:
-                    _lib.bwd_dw_root(xp, din, gp, dout, pr, pb)
+        # a piece (one GPU: the graph) with a tile-major d_weight plan takes it (layout-3 forward plans always: the relation-major
+        # kernels refuse them) unless the flags pin other kernels; that kernel gathers x and g through buffer descriptors only
+        tiles_ok = (not flags & (_lib.FLAG_DW_RING | _lib.FLAG_DW_DIRECT | _lib.FLAG_POINTER_GATHER)
+                    and _lib.buffer_addressable(n, xp.shape[1]))
+
+        def on_tiles(pc):
+            return (tiles_ok and pc.dw is not None and (need_w or pc.fwd.layout == 3)
+                    and _lib.buffer_addressable(pc.fwd.n_owned, gp.shape[1]))
+
+        tiles = dctx is None and (need_w or need_root or need_bias) and on_tiles(plans)
+        if tiles:
+            acc = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+            pw, pr, pb = views(acc)
+            if need_x and n >= _SIDE_STREAM_MIN_ROWS and (pr is not None or pb is not None):
+                # d_root / d_bias on a SIDE stream, enqueued before the dX launch: the streaming kernel is HBM-bound with a tenth
+                # of a launch's MFMAs, uses no LDS and few registers, so its workgroups share the CUs with the MFMA-bound dX
+                # kernel instead of adding their ~1 ms behind it.  The join is a stream wait, never a host sync.
+                side = _side_stream(dev)
+                side.wait_stream(torch.cuda.current_stream(dev))      # gp (and xp) are produced on the current stream
+            with torch.cuda.stream(side):
+                _dw_tiles(plans.dw, plans.dw_walk, xp, din, gp, dout, (None, pr, pb), flags)
         if need_x:
             packed_t = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=True)
             ldx = _round4(din)
             mask = xp if ctx.input_relu else None            # x = relu(z_prev): store dL/dz_prev = dx * (x > 0)
-            if dctx is None and plans.ep_bwd is not None:
+            if dctx is None:
                 dxp = torch.empty(n, ldx, dtype=torch.float32, device=dev)
-                _lib.ep_layer(plans.ep_bwd, gp, dout, packed_t, None, dxp, din, _lib.ACT_NONE, mask, flags)
-            elif dctx is None:
-                dxp = torch.empty(n, ldx, dtype=torch.float32, device=dev)
-                _lib.bwd_dx(_lib.plan_struct(plans.bwd), gp, dout, packed_t, dxp, din, mask, flags)
+                _launch_dx(plans.bwd or plans.ep_bwd, gp, dout, packed_t, dxp, din, mask, flags)
             else:
-                hm_b = _shared_heavy_sums(getattr(plans, "shared_bwd", None), gp, dout, dctx)
-
-                def launch_dx(pl, rows):
-                    m = None if mask is None else mask[pl.node_begin:pl.node_end]
-                    if isinstance(pl, TilePlan):
-                        _lib.bwd_dx(_lib.plan_struct(pl), gp, dout, packed_t, rows, din, m, flags)
-                    else:
-                        _lib.ep_layer(pl, gp, dout, packed_t, None, rows, din, _lib.ACT_NONE, m, flags, hmat=hm_b)
+                hm_b = _shared_heavy_sums(plans.shared_bwd, gp, dout, dctx)
                 # the exchange of the dX pieces stays in flight under the weight-gradient kernels below (they read x and the
                 # rank's own rows of g, none of the gathered rows); finish_dx() is the wait
-                dxp, finish_dx = _gather_pieces(dctx, [p.bwd if p.bwd is not None else p.ep_bwd for p in plans.pieces], launch_dx, ldx, n, dev,
-                                                needed=plans.needed_bwd if dctx.exchange == "needed" else None, defer=True)
+                dxp, finish_dx = _gather_pieces(
+                    dctx, [p.bwd or p.ep_bwd for p in plans.pieces],
+                    lambda pl, rows: _launch_dx(pl, gp, dout, packed_t, rows, din,
+                                                None if mask is None else mask[pl.node_begin:pl.node_end], flags, hm_b),
+                    ldx, n, dev, needed=plans.needed_bwd if dctx.exchange == "needed" else None, defer=True)
             dx = dxp if ldx == din else dxp[:, :din]
-        if tiles_path:
-            # relations: tile-major kernel (gradient rows staged in LDS)
-            if need_w:
-                _lib.bwd_dw_tiles(_lib.plan_struct(dwp), plans.dw_walk, xp, din, gp, dout, views(tiles_part)[0], flags)
+        if tiles:
+            _dw_tiles(plans.dw, plans.dw_walk, xp, din, gp, dout, (pw, None, None), flags)
             if side is not None:
                 torch.cuda.current_stream(dev).wait_stream(side)
-            dw, droot, dbias = views(tiles_part)
         elif need_w or need_root or need_bias:
-            # (an edge-parallel forward hands its dense relation-major units to the same kernels: GraphPlans.fwd_walk)
             pieces = [plans] if dctx is None else plans.pieces
-            pinned = flags & (_lib.FLAG_DW_RING | _lib.FLAG_DW_DIRECT | _lib.FLAG_POINTER_GATHER)
-            acc = None
-            rank_dw = getattr(plans, "dw_rank", None) if dctx is not None else None
-            if rank_dw is not None and not pinned and _lib.buffer_addressable(n, xp.shape[1]):
+            if dctx is not None and plans.dw_rank is not None and tiles_ok:
                 # full exchange: x and g are replicated, so this rank's share of the weight gradients is ONE contiguous node
-                # range of its own (dist.dw_range) -- one tile-major launch + the streaming root part, whatever the forward's pieces
-                dwp_, walk_ = rank_dw
-                if dwp_ is None:        # an empty range
-                    acc = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+                # range of its own (dist.dw_range) -- one tile-major launch + the streaming root part, whatever the pieces
+                dwp, walk = plans.dw_rank
+                if dwp is None:        # an empty range: zeros below
                     pieces = []
-                b, e = (dwp_.node_begin, dwp_.node_end) if dwp_ is not None else (0, 0)
-                if dwp_ is not None and _lib.buffer_addressable(e - b, gp.shape[1]):
-                    acc = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-                    pw, pr, pb = views(acc)
-                    if need_w:
-                        _lib.bwd_dw_tiles(_lib.plan_struct(dwp_), walk_, xp, din, gp[b:e], dout, pw, flags)
-                    if need_root or need_bias:
-                        _lib.bwd_dw_root(xp[b:e], din, gp[b:e], dout, pr, pb)
+                elif _lib.buffer_addressable(dwp.n_owned, gp.shape[1]):
+                    acc, pieces = torch.empty(sum(sizes), dtype=torch.float32, device=dev), []
+                    _dw_tiles(dwp, walk, xp, din, gp, dout, views(acc), flags)
                     dctx.stats["dw_tiles_rank"] = dctx.stats.get("dw_tiles_rank", 0) + 1
-                    pieces = []
             for pc in pieces:
-                fp = pc.fwd_walk
-                if fp.n_owned <= 0:
+                if pc.fwd_walk.n_owned <= 0:
                     continue
                 part = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-                pw, pr, pb = views(part)
-                b, e = fp.node_begin, fp.node_end
-                if (dctx is not None and (need_w or getattr(fp, "layout", 0) == 3) and getattr(pc, "dw", None) is not None and not pinned
-                        and _lib.buffer_addressable(n, xp.shape[1]) and _lib.buffer_addressable(e - b, gp.shape[1])):
+                if dctx is not None and on_tiles(pc):
                     # a rank's piece on the tile-major kernel, as the single-GPU step (its root part: the piece's own rows)
-                    if need_w:
-                        _lib.bwd_dw_tiles(_lib.plan_struct(pc.dw), pc.dw_walk, xp, din, gp[b:e], dout, pw, flags)
-                    if need_root or need_bias:
-                        _lib.bwd_dw_root(xp[b:e], din, gp[b:e], dout, pr, pb)
+                    _dw_tiles(pc.dw, pc.dw_walk, xp, din, gp, dout, views(part), flags)
                     dctx.stats["dw_tiles_pieces"] = dctx.stats.get("dw_tiles_pieces", 0) + 1
                 else:
-                    _lib.bwd_dw(_lib.plan_struct(fp), xp, din, gp[b:e], dout, pw, pr, pb, flags)
-                    epf = getattr(pc, "ep_fwd", None)
-                    if need_w and epf is not None and epf.heavy is not None:
-                        # the heavy segments' share: d_W_r += H_seg^T g[dst] over their pseudo rows (H from the forward)
-                        hmat = getattr(ctx, "ep_heavy", None)
-                        if hmat is None:
-                            hmat = _lib.ep_aggregate_heavy(epf, xp, din)
-                        pw2 = torch.empty_like(pw)
-                        _lib.bwd_dw(_lib.plan_struct(epf.heavy_tile_plan()), hmat, din, gp[b:e], dout, pw2, None, None, flags)
-                        pw.add_(pw2)
+                    _dw_walk(pc, xp, din, gp, dout, views(part), flags, ctx.ep_heavy)
                 acc = part if acc is None else acc.add_(part)
             if acc is None:
                 acc = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
@@ -483,37 +462,59 @@ class _RGCNLayerFn(torch.autograd.Function):
                     torch.distributed.all_reduce(acc, group=dctx.group)
                 dctx.stats["all_reduce"] += 1
                 dctx.stats["all_reduce_bytes"] += acc.numel() * 4
-            dw, droot, dbias = views(acc)
+        dw, droot, dbias = (None, None, None) if acc is None else views(acc)
         if finish_dx is not None:
             finish_dx()
         dcomp = None
-        if decomposed and dw is not None:
+        if dw is not None and (cp is not None or wf.dim() == 4):
             dw, dcomp = _lib.decomposed_weight_grads(dw.contiguous(), wf, cp, need_wparam, need_comp)
-        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None, None
+        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None
+
+
+class _XwideFn(torch.autograd.Function):
+    """A layer with a side above 128 on csrc/rgcn_xwide.hip (one GPU, layout-0 plans): dX on the transposed plan, the weight
+    gradients on the forward plan; a decomposition composed into / differentiated from a dense operand by torch ops."""
 
     @staticmethod
-    def _backward_xwide(ctx, xp, wf, cp, rt, gp, need_x, need_w, need_wparam, need_comp, need_root, need_bias):
-        """backward of a layer with a side above 128: dX on the transposed plan, the weight gradients on the forward plan
-        (csrc/rgcn_xwide.hip); a decomposition's gradients from the dense d_W scratch, which is dropped here"""
+    def forward(ctx, x: Tensor, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor],
+                plans: GraphPlans, act: int, input_relu: bool, grad_premasked: bool, num_rel: int, dout: int):
+        n, din = x.shape
+        xp = _rows16(x, din)
+        wf, cp, rt, bs = _operands(weight, comp, root, bias)
+        out = torch.empty(n, _round4(dout), dtype=torch.float32, device=x.device)
+        op = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=False)
+        _lib.xwide_fwd(_lib.plan_struct(plans.fwd), xp, din, op, bs, out, dout, act)
+        del op
+        ctx.plans, ctx.dims, ctx.input_relu = plans, (n, din, dout, num_rel), input_relu
+        ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
+        ctx.save_for_backward(xp, wf, cp, rt, out if ctx.need_a else None)
+        return out if out.shape[1] == dout else out[:, :dout]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        xp, wf, cp, rt, a_out = ctx.saved_tensors
         n, din, dout, num_rel = ctx.dims
-        plans, dev = ctx.plans, gp.device
+        need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]
+        gp = _rows16(g, dout)
+        if ctx.need_a:
+            gp = _lib.act_backward(a_out, gp, ctx.act)
         dx = dw = droot = dbias = dcomp = None
         if need_x:
             opt = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=True)
             ldx = _round4(din)
-            dxp = torch.empty(n, ldx, dtype=torch.float32, device=dev)
-            _lib.xwide_bwd_dx(_lib.plan_struct(plans.bwd), gp, dout, opt, dxp, din, xp if ctx.input_relu else None)
+            dxp = torch.empty(n, ldx, dtype=torch.float32, device=g.device)
+            _lib.xwide_bwd_dx(_lib.plan_struct(ctx.plans.bwd), gp, dout, opt, dxp, din, xp if ctx.input_relu else None)
             del opt
             dx = dxp if ldx == din else dxp[:, :din]
-        if need_w or need_root or need_bias:
-            f32 = dict(dtype=torch.float32, device=dev)
-            dw = torch.empty(num_rel, din, dout, **f32) if need_w else None
+        if need_wparam or need_comp or need_root or need_bias:
+            f32 = dict(dtype=torch.float32, device=g.device)
+            dw = torch.empty(num_rel, din, dout, **f32) if need_wparam or need_comp else None
             droot = torch.empty(din, dout, **f32) if need_root else None
             dbias = torch.empty(dout, **f32) if need_bias else None
-            _lib.xwide_bwd_dw(_lib.plan_struct(plans.fwd), xp, din, gp, dout, dw, droot, dbias)
+            _lib.xwide_bwd_dw(_lib.plan_struct(ctx.plans.fwd), xp, din, gp, dout, dw, droot, dbias)
         if dw is not None and (cp is not None or wf.dim() == 4):
             dw, dcomp = _xwide_decomposed_grads(dw, wf, cp, need_wparam, need_comp)
-        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None, None
+        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None
 
 
 class _FeaturelessFn(torch.autograd.Function):
@@ -525,24 +526,17 @@ class _FeaturelessFn(torch.autograd.Function):
     def forward(ctx, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor], plans: GraphPlans,
                 index, in_rows: int, dout: int):
         n = plans.fwd.n_nodes
-        wf = weight.detach().float().contiguous()
-        cp = None if comp is None else comp.detach().float().contiguous()
-        rt = None if root is None else root.detach().float().contiguous()
-        bs = None if bias is None else bias.detach().float().contiguous()
+        wf, cp, rt, bs = _operands(weight, comp, root, bias)
         out = torch.empty(n, _round4(dout), dtype=torch.float32, device=wf.device)
         _lib.featureless_fwd(_lib.plan_struct(plans.fwd), None if index is None else index[0], in_rows, wf, cp, rt, bs, out, dout)
         ctx.plans, ctx.index, ctx.in_rows, ctx.dout = plans, index, in_rows, dout
-        ctx.has_root, ctx.has_bias = root is not None, bias is not None
         ctx.save_for_backward(wf, cp)
         return out if out.shape[1] == dout else out[:, :dout]
 
     @staticmethod
     def backward(ctx, g: Tensor):
         wf, cp = ctx.saved_tensors
-        need_w, need_comp, need_root, need_bias = ctx.needs_input_grad[:4]
-        need_comp = need_comp and cp is not None
-        need_root = need_root and ctx.has_root
-        need_bias = need_bias and ctx.has_bias
+        need_w, need_comp, need_root, need_bias = ctx.needs_input_grad[:4]      # (False for an input that is None)
         dout, in_rows, dev = ctx.dout, ctx.in_rows, g.device
         dw = torch.empty_like(wf) if need_w else None
         dcomp = torch.empty_like(cp) if need_comp else None
@@ -596,8 +590,23 @@ def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: 
         num_rel, dout = int(weight.shape[0]), int(weight.shape[1] * weight.shape[3])
     else:
         num_rel, dout = int(weight.shape[0]), int(weight.shape[2])
+    if xwide:
+        if dctx is not None:
+            raise NotImplementedError("RGCNConv wider than 128 runs on one GPU: a dist context is not supported")
+        return _XwideFn.apply(x, weight, comp, root, bias, plans, _ACT_CODES[activation], bool(input_relu), bool(grad_premasked),
+                              num_relations or num_rel, out_channels or dout)
     return _RGCNLayerFn.apply(x, weight, comp, root, bias, plans, dctx, _ACT_CODES[activation], bool(input_relu),
-                              bool(grad_premasked), int(flags), num_relations or num_rel, out_channels or dout, bool(xwide))
+                              bool(grad_premasked), int(flags), num_relations or num_rel, out_channels or dout)
+
+
+def _paths(path):
+    """``RGCNConv.path`` as the routing and the plan cache key it: "auto" or a (forward, dX) pair"""
+    return path if path == "auto" else ((path, path) if isinstance(path, str) else tuple(path))
+
+
+# what RGCNConv._route decides: tile, chunk, plan layout (0, or 3: plan.compact_runs), d_weight on its own tile-major plan,
+# FLAG_SPLIT_PRODUCERS (the bf16 x 3 forms of 64 x 64 layers), paths ("auto" or a (forward, dX) pair of "ring" / "ep")
+_Route = namedtuple("_Route", "tile chunk layout dw_tiles split_producers paths")
 
 
 def glorot_(t: Tensor) -> Tensor:
@@ -663,7 +672,7 @@ class RGCNConv(nn.Module):
         self.dist: Optional[DistContext] = None
         self._dist_plans = None
         self.kernel_flags = 0     # RGCN_FLAG_* passed to every launch of this layer (tests pin kernel paths with it)
-        self.dw_tiles = True      # d_weight by the tile-major kernel where it applies (_plans); False: relation-major kernels
+        self.dw_tiles = True      # d_weight by the tile-major kernel where it applies (_route); False: relation-major kernels
         # forward / dX on the producer-split bf16 x 3 kernel where it applies (64 x 64, 128-slot chunks, single GPU): fp32-
         # equivalent arithmetic (24-bit operand significands, exact products, fp32 accumulation), 1 ms per step faster at
         # the headline config.  False (or RGCN_SPLIT_PRODUCERS=0): the exact-fp32 MFMA kernel everywhere
@@ -730,81 +739,72 @@ class RGCNConv(nn.Module):
             return w.reshape(self.num_relations, self.in_channels, self.out_channels)
         return self.weight
 
-    def _plans(self, x: Tensor, edge_index: Tensor, edge_type: Tensor) -> GraphPlans:
+    def _plans(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, route: Optional["_Route"] = None):
+        """the (cached) plans of this layer on the graph: GraphPlans, or with ``self.dist`` the rank's RankPlans"""
         n = x.shape[0]
-        e = int(edge_type.shape[0])
-        tile, chunk = self.layout(n, e)
-        # the tile-major weight-gradient kernel: 64 x 64 layers with few relations on graphs large enough to fill it
-        # (it gathers through buffer descriptors only: above 2^24 rows / 4 GiB the relation-major kernels run)
-        from .plan import padded_width
-        dw_tiles = (self.dw_tiles and padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64
-                    and self.num_relations <= 32 and e >= DW_TILES_MIN_EDGES and x.is_cuda
-                    and _lib.buffer_addressable(n, _round4(self.in_channels))
-                    and _lib.buffer_addressable(n, _round4(self.out_channels)))
-        # layout 3 only where nothing but rgcn_tile3p_kernel walks the forward / transposed plans: the split kernels unpinned
-        # (no kernel flags), d_weight on its own tile-major plan, d_root / d_bias on the plan-free streaming kernel
-        split = 3 if (self.merge_runs and dw_tiles and self.kernel_flags == 0 and
-                      (self._use_split_producers(chunk) or self._exact_merge(chunk))) else False
+        r = self._route(n, int(edge_type.shape[0]), x.is_cuda) if route is None else route
+        widths = (self.in_channels, self.out_channels)
         if self.dist is None:
-            paths = self.path if self.path == "auto" else ((self.path, self.path) if isinstance(self.path, str) else tuple(self.path))
-            if not x.is_cuda:
-                paths = ("ring", "ring")
-            return cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, split=split,
-                                      dw_tiles=dw_tiles, paths=paths, widths=(self.in_channels, self.out_channels))
-        # edge-partitioned: every piece on the kernels the whole graph would take per direction (+ its own tile-major
-        # weight-gradient plan where the forward runs tile kernels)
+            return cached_graph_plans(edge_index, edge_type, n, self.num_relations, r.tile, self.aggr, chunk=r.chunk, split=r.layout,
+                                      dw_tiles=r.dw_tiles, paths=r.paths, widths=widths)
         from .dist import cached_rank_plans
-        paths = ("ring", "ring")
-        if x.is_cuda:
-            paths = self.path if self.path == "auto" else ((self.path, self.path) if isinstance(self.path, str) else tuple(self.path))
-        return cached_rank_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, self.dist, chunk, split, dw_tiles,
-                                 paths=paths, widths=(self.in_channels, self.out_channels))
+        return cached_rank_plans(edge_index, edge_type, n, self.num_relations, r.tile, self.aggr, self.dist, r.chunk, r.layout,
+                                 r.dw_tiles, paths=r.paths, widths=widths)
+
+    @property
+    def _w64(self) -> bool:
+        """both sides pad to 64 columns: the layers of the producer-split kernel, layout 3 and the tile-major d_weight kernel"""
+        return padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64
 
     def _use_split_producers(self, chunk: int) -> bool:
-        """whether a plan of ``self.layout`` with that chunk runs on the bf16 x 3 kernel (layout() returns 128-slot chunks for a
-        64 x 64 layer with split_producers only where that kernel is the modelled choice, at a tile it has room for)"""
-        from .plan import padded_width
-        return (self.split_producers and chunk in (112, 128)
-                and padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64)
-
-    def _exact_merge(self, chunk: int) -> bool:
-        """the exact-fp32 kernel on layout-3 plans: 64 x 64 layers, 128-slot chunks, where the bf16 x 3 kernel is switched off"""
-        from .plan import padded_width
-        return (not self.split_producers and self.merge_runs and chunk == 128
-                and padded_width(self.in_channels) == 64 and padded_width(self.out_channels) == 64)
+        """whether a plan of this layer with that chunk runs on the bf16 x 3 kernel (FLAG_SPLIT_PRODUCERS, _route)"""
+        return self.split_producers and chunk in (112, 128) and self._w64
 
     @property
     def xwide(self) -> bool:
         """whether this layer runs on the kernels of csrc/rgcn_xwide.hip: ``wide`` and a side above 128"""
         return self.wide and max(self.in_channels, self.out_channels) > NARROW_MAX_WIDTH
 
-    def layout(self, n_nodes: int, n_edges: int) -> Tuple[int, int]:
-        """(tile, chunk) of this layer's plans on a graph of that size: ``layout_for``, capped at the producer-split kernel's
-        tile where that kernel will run (dist.attach aligns the ranks' node ranges to the same tile), or at the tile that leaves
-        the exact-fp32 kernel's chunks room for their shadow row tiles where it will walk layout-3 plans."""
+    def _route(self, n_nodes: int, n_edges: int, on_gpu: bool) -> "_Route":
+        """Every kernel choice of this layer on a graph of that size (``on_gpu``: its tensors are on the device).  The tile is
+        ``layout_for``'s, capped at the producer-split kernel's tile where that kernel will run (dist.attach aligns the ranks' node
+        ranges to it), or at the tile that leaves the exact-fp32 kernel room for shadow row tiles where it walks layout-3 plans."""
         if self.xwide:
             raise NotImplementedError("RGCNConv wider than 128 runs on one GPU only: no dist layout")
         tile, chunk = layout_for(self.in_channels, self.out_channels, n_nodes, n_edges, self.num_relations)
+        # the tile-major weight-gradient kernel: 64 x 64 layers with few relations on graphs large enough to fill it
+        dw_rule = self.dw_tiles and self._w64 and self.num_relations <= 32 and n_edges >= DW_TILES_MIN_EDGES
+        exact_merge = False
         if self._use_split_producers(128):
-            # 64 x 64 with the bf16 x 3 kernel available: its own layout (128-slot chunks, tiles up to 224, its own cycles per chunk
-            # and row tile) against the exact-fp32 kernel's, by modelled launch time -- round 4: on a 100k-node / 1M-edge graph the
-            # exact model's (400, 64) kept the layer off the faster kernel: 0.416 ms per step replayed against 0.333 at (208, 128)
-            from .plan import choose_layout
+            # the bf16 x 3 kernel's own layout (128-slot chunks, tiles up to 224, its own cycles per chunk and row tile) against the
+            # exact-fp32 kernel's, by modelled launch time -- round 4: on a 100k-node / 1M-edge graph the exact model's (400, 64)
+            # kept the layer off the faster kernel: 0.416 ms per step replayed against 0.333 at (208, 128)
             args = (n_nodes, n_edges, self.num_relations, self.in_channels, self.out_channels)
-            t0, c0, cost0 = choose_layout(*args, with_cost=True)
             t3, c3, cost3 = choose_layout(*args, kernel="bf16x3", with_cost=True)
-            if cost3 <= cost0:
-                return t3, c3
-            if c0 == 128:      # (the exact-fp32 kernel with 128-slot chunks would be taken for the other one: keep it on 64)
-                tile, chunk = layout_for(self.in_channels, self.out_channels, n_nodes, n_edges, self.num_relations)
-                return min(tile, SPLIT_PRODUCERS_TILE), chunk
-            return t0, c0
-        if self._use_split_producers(chunk):
-            tile = min(tile, SPLIT_PRODUCERS_TILE)
-        elif (self._exact_merge(chunk) and self.dw_tiles and self.kernel_flags == 0 and self.num_relations <= 32
-              and n_edges >= DW_TILES_MIN_EDGES):
-            tile = min(tile, EXACT_MERGE_TILE)
-        return tile, chunk
+            if cost3 <= choose_layout(*args, with_cost=True)[2]:
+                tile, chunk = t3, c3
+            elif chunk == 128:      # (the exact-fp32 kernel with 128-slot chunks would be taken for the other one: keep it on 64)
+                tile = min(tile, SPLIT_PRODUCERS_TILE)
+        else:
+            # the exact-fp32 kernel on layout-3 plans.  The cap asks the dW-tiles rule of the graph's size only, not whether the
+            # tile-major kernel can address x and g (dw_tiles below): the tile sets the summation order of every output, layout()
+            # and dist.attach ask without tensors, and past 2^24 rows / 4 GiB the capped tile stays on layout 0
+            exact_merge = self.merge_runs and chunk == 128 and self._w64
+            if exact_merge and dw_rule and self.kernel_flags == 0:
+                tile = min(tile, EXACT_MERGE_TILE)
+        split = self._use_split_producers(chunk)
+        # (the tile-major kernel gathers through buffer descriptors only: above 2^24 rows / 4 GiB the relation-major kernels run)
+        dw_tiles = (dw_rule and on_gpu and _lib.buffer_addressable(n_nodes, _round4(self.in_channels))
+                    and _lib.buffer_addressable(n_nodes, _round4(self.out_channels)))
+        # layout 3 only where nothing but rgcn_tile3p_kernel walks the forward / transposed plans: the split kernels unpinned
+        # (no kernel flags), d_weight on its own tile-major plan, d_root / d_bias on the plan-free streaming kernel
+        layout = 3 if self.merge_runs and dw_tiles and self.kernel_flags == 0 and (split or exact_merge) else 0
+        return _Route(tile, chunk, layout, dw_tiles, split, _paths(self.path) if on_gpu else ("ring", "ring"))
+
+    def layout(self, n_nodes: int, n_edges: int) -> Tuple[int, int]:
+        """(tile, chunk) of this layer's plans on a graph of that size (``_route``; they do not depend on the device)"""
+        r = self._route(n_nodes, n_edges, False)
+        return r.tile, r.chunk
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_type: Optional[Tensor] = None, *,
                 _activation: Optional[str] = None, _input_relu: bool = False,
@@ -824,14 +824,11 @@ class RGCNConv(nn.Module):
             raise ValueError(f"x must be [N, {self.in_channels}], got {tuple(x.shape)}")
         if self.xwide:
             return self._forward_xwide(x, edge_index, edge_type, _activation, _input_relu, _grad_premasked)
-        plans = self._plans(x, edge_index, edge_type)
-        flags = self.kernel_flags
-        # (the arithmetic mode follows the layer and the graph's size -- the chunk of self.layout -- not which path the other
-        # direction happened to take: an edge-parallel pair on a graph too small for 128-slot chunks stays on exact fp32)
-        if self._use_split_producers(self.layout(x.shape[0], int(edge_type.shape[0]))[1]):
-            # rgcn_fwd / rgcn_bwd_dx / rgcn_bwd_dw_tiles / rgcn_ep_transform: the bf16 x 3 (fp32-equivalent) forms of 64 x 64 layers;
-            # the library falls back where they do not fit
-            flags |= _lib.FLAG_SPLIT_PRODUCERS
+        route = self._route(x.shape[0], int(edge_type.shape[0]), x.is_cuda)
+        plans = self._plans(x, edge_index, edge_type, route)
+        # rgcn_fwd / rgcn_bwd_dx / rgcn_bwd_dw_tiles / rgcn_ep_transform: the bf16 x 3 (fp32-equivalent) forms of 64 x 64 layers
+        # where they fit.  (The mode follows the route's chunk, not which path the other direction happened to take.)
+        flags = self.kernel_flags | (_lib.FLAG_SPLIT_PRODUCERS if route.split_producers else 0)
         return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, self.dist,
                                   _activation, _input_relu, _grad_premasked and _activation == "relu", flags,
                                   comp=self.comp, num_relations=self.num_relations, out_channels=self.out_channels)
@@ -840,15 +837,14 @@ class RGCNConv(nn.Module):
                        grad_premasked: bool) -> Tensor:
         if self.dist is not None:
             raise NotImplementedError("RGCNConv wider than 128 runs on one GPU: a dist context is not supported")
-        paths = (self.path,) if isinstance(self.path, str) else tuple(self.path)
-        if "ep" in paths:
+        paths = _paths(self.path)
+        if paths != "auto" and "ep" in paths:
             raise ValueError("RGCNConv wider than 128 has no edge-parallel path: path must be 'auto' or 'ring'")
         if x.device.type != "cuda":
             raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
         n = int(x.shape[0])
         tile, chunk = _lib.xwide_geometry(max(n, 1), self.in_channels, self.out_channels)
-        plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, split=False,
-                                   dw_tiles=False, paths=("ring", "ring"), extra_key=("xwide",))
+        plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, extra_key=("xwide",))
         return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, None, activation, input_relu,
                                   grad_premasked and activation == "relu", 0, comp=self.comp, num_relations=self.num_relations,
                                   out_channels=self.out_channels, xwide=True)
@@ -868,8 +864,8 @@ class RGCNConv(nn.Module):
         index = None if x is None else _node_index(x, self.in_channels)
         nb = 0 if self.num_bases is None else int(self.num_bases)
         tile, chunk = _lib.featureless_geometry(max(n, 1), self.out_channels, nb)
-        plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, split=False,
-                                   dw_tiles=False, paths=("ring", "ring"), extra_key=("featureless",))
+        plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk,
+                                   extra_key=("featureless",))
         return _FeaturelessFn.apply(self.weight, self.comp, self.root, self.bias, plans, index, self.in_channels,
                                     self.out_channels)
 

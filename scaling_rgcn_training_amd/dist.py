@@ -256,6 +256,12 @@ class RankPlans:
         # the upstream gradient are replicated, so the weight gradients' cut is free: one launch per rank, not one per piece
         self.dw_rank = dw_rank
 
+    def nbytes(self) -> int:
+        extra = sum(q.nbytes() for q in (self.needed_fwd, self.needed_bwd) if q is not None)
+        if self.dw_rank is not None and self.dw_rank[0] is not None:
+            extra += self.dw_rank[0].nbytes()
+        return extra + sum(p.nbytes() for p in self.pieces)
+
 
 def dw_range(edge_index: Tensor, n_nodes: int, world: int, rank: int, tile: int = 320):
     """the contiguous node range whose in-edges rank ``rank`` sums into d_weight / d_root / d_bias: ``world`` ranges of about equal
@@ -335,15 +341,11 @@ def rank_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relation
 
 def cached_rank_plans(edge_index, edge_type, n_nodes, num_relations, tile, aggr, dctx: DistContext,
                       chunk: int = 64, split: bool = False, dw_tiles: bool = False, paths=("ring", "ring"), widths=None) -> RankPlans:
-    def build():
-        p = paths
-        if p == "auto":      # the whole graph's choice per direction (eplan.decide_paths): every rank decides alike
-            from .eplan import decide_paths
-            p = decide_paths(edge_index, n_nodes, num_relations, widths[0], widths[1], tile, chunk)
-        return rank_plans(edge_index, edge_type, n_nodes, num_relations, tile, aggr, dctx, chunk, split, dw_tiles, p)
+    # ("auto": the whole graph's choice per direction, eplan.resolve_paths -- every rank decides alike)
     return cached_graph_plans(
-        edge_index, edge_type, n_nodes, num_relations, tile, aggr, chunk=chunk, split=split, dw_tiles=dw_tiles,
-        paths=paths if isinstance(paths, str) else tuple(paths), widths=widths, builder=build,
+        edge_index, edge_type, n_nodes, num_relations, tile, aggr, chunk=chunk, split=split, dw_tiles=dw_tiles, paths=paths,
+        widths=widths, builder=lambda p: rank_plans(edge_index, edge_type, n_nodes, num_relations, tile, aggr, dctx, chunk, split,
+                                                    dw_tiles, p),
         extra_key=("rank", dctx.rank, dctx.world, dctx.pieces, tuple(dctx.bounds), dctx.exchange, dctx.split_hubs))
 
 
@@ -358,16 +360,13 @@ def attach(module: torch.nn.Module, n_nodes: int, n_edges: int, group=None, edge
     the same graph.  ``emulate=(world, rank)``: one process stands in for one rank, no collectives (bench.py).
     ``edge_type`` + ``split_hubs`` (default on): the cut leaves out the rows of heavy (node, relation) segments, which the
     edge-parallel path deals over all ranks (eplan.SharedHeavy)."""
+    from .eplan import resolve_paths
     for m in module.modules():
         if isinstance(m, RGCNConv):
-            tile, chunk = m.layout(n_nodes, n_edges)
+            # (on_gpu=True: r.paths is the layer's setting, not the CPU override; tile and chunk do not depend on it)
+            r = m._route(n_nodes, n_edges, on_gpu=True)
             paths = ("ring", "ring")
             if edge_type is not None and split_hubs and edge_index is not None:
                 # the path every rank will take per direction (the whole graph's choice: cached_rank_plans decides the same way)
-                paths = m.path
-                if paths == "auto":
-                    from .eplan import decide_paths
-                    paths = decide_paths(edge_index, n_nodes, m.num_relations, m.in_channels, m.out_channels, tile, chunk)
-                elif isinstance(paths, str):
-                    paths = (paths, paths)
-            m.dist = make_context(n_nodes, tile, group, pieces, edge_index, balance, exchange, emulate, edge_type, split_hubs, tuple(paths))
+                paths = resolve_paths(r.paths, edge_index, n_nodes, m.num_relations, (m.in_channels, m.out_channels), r.tile, r.chunk)
+            m.dist = make_context(n_nodes, r.tile, group, pieces, edge_index, balance, exchange, emulate, edge_type, split_hubs, tuple(paths))

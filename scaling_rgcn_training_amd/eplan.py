@@ -498,6 +498,14 @@ def choose_path(n_nodes: int, n_edges: int, num_relations: int, in_width: int, o
     return "ep" if ep < 0.9 * ring else "ring"
 
 
+def resolve_paths(paths, edge_index: Tensor, n_nodes: int, num_relations: int, widths: Tuple[int, int], tile: int, chunk: int):
+    """a layer's path setting per direction: a (forward, dX) pair as it is, "auto" decided once per graph (decide_paths) --
+    on a plan-cache miss, or by dist.attach for the cut"""
+    if paths != "auto":
+        return paths
+    return decide_paths(edge_index, n_nodes, num_relations, widths[0], widths[1], tile, chunk)
+
+
 def decide_paths(edge_index: Tensor, n_nodes: int, num_relations: int, in_channels: int, out_channels: int, tile: int,
                  chunk: int) -> Tuple[str, str]:
     """(forward path, dX path) for a layer on this graph.  One pass over the edge list per direction (rows per tile: a hub's

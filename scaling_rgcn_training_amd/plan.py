@@ -567,7 +567,7 @@ def _choose_layout(n_nodes: int, n_edges: int, num_relations: int, in_channels: 
                    with_cost: bool = False):
     """(tile, chunk) for a layer: output nodes per tile and edge slots per chunk.  ``kernel="bf16x3"``: the layout for
     rgcn_tile3p_kernel (64 x 64 layers: 128-slot chunks, tiles up to 224, its own per-chunk / per-row-tile cycles);
-    ``with_cost``: also the modelled time of one launch, comparable between the two kernels (conv.RGCNConv.layout picks with it).
+    ``with_cost``: also the modelled time of one launch, comparable between the two kernels (conv.RGCNConv._route picks with it).
 
     Cost model of the forward / dX kernel, calibrated on the 10M-node / 100M-edge graph (a cycle-stamp build): a
     chunk costs ~800 cycles whatever it holds (barrier, metadata, pipeline fill and drain) and every 16-row MFMA tile
@@ -660,6 +660,9 @@ class GraphPlans:
     def fwd_walk(self) -> TilePlan:
         """the plan whose 64-slot units the relation-major weight-gradient kernels walk"""
         return self.fwd if self.fwd is not None else self.ep_fwd.as_tile_plan()
+
+    def nbytes(self) -> int:
+        return sum(q.nbytes() for q in (self.fwd, self.bwd, self.dw, self.ep_fwd, self.ep_bwd) if q is not None)
 
 
 def build_graph_plans_torch(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int,
@@ -858,20 +861,12 @@ _CACHE_MAX = 16
 _CACHE_MAX_BYTES = int(float(_os.environ.get("RGCN_PLAN_CACHE_GB", "48")) * (1 << 30))   # read once at import
 
 
-def _plans_nbytes(plans) -> int:
-    pieces = getattr(plans, "pieces", None) or [plans]
-    extra = sum(q.nbytes() for q in (getattr(plans, "needed_fwd", None), getattr(plans, "needed_bwd", None)) if q is not None)
-    if getattr(plans, "dw_rank", None) is not None and plans.dw_rank[0] is not None:
-        extra += plans.dw_rank[0].nbytes()
-    return extra + sum(sum(q.nbytes() for q in (p.fwd, p.bwd, getattr(p, "dw", None), getattr(p, "ep_fwd", None), getattr(p, "ep_bwd", None))
-                           if q is not None) for p in pieces)
-
-
 def cached_graph_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int,
                        tile: int, aggr: str, builder=None, extra_key=(), chunk: int = CHUNK, split: bool = False,
                        dw_tiles: bool = False, paths=("ring", "ring"), widths: Optional[Tuple[int, int]] = None) -> GraphPlans:
     """LRU over (edge tensors' identity, layout): at most ``_CACHE_MAX`` entries and ``RGCN_PLAN_CACHE_GB`` (48) GiB of
-    plan arrays (4.3 GB per 100M edges), least recently used evicted first."""
+    plan arrays (4.3 GB per 100M edges), least recently used evicted first.  On a miss ``paths`` = "auto" is resolved
+    (eplan.resolve_paths; the key keeps "auto") and ``builder(paths)``, where given, builds instead (dist.cached_rank_plans)."""
     key = (edge_index.data_ptr(), edge_type.data_ptr(), tuple(edge_index.shape), edge_index._version,
            edge_type._version, str(edge_index.device), n_nodes, num_relations, tile, chunk, aggr, int(split), bool(dw_tiles),
            paths if isinstance(paths, str) else tuple(paths), widths) + tuple(extra_key)
@@ -879,15 +874,14 @@ def cached_graph_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_
     if hit is not None:
         _CACHE[key] = hit           # most recently used last
         return hit[0]
+    from .eplan import resolve_paths
+    paths = resolve_paths(paths, edge_index, n_nodes, num_relations, widths, tile, chunk)
     if builder is None:
-        if paths == "auto":      # per direction: tile kernels or the edge-parallel path (eplan.choose_path), decided once per graph
-            from .eplan import decide_paths
-            paths = decide_paths(edge_index, n_nodes, num_relations, widths[0], widths[1], tile, chunk)
         plans = build_graph_plans(edge_index, edge_type, n_nodes, num_relations, tile, aggr, chunk=chunk, split=split,
                                   dw_tiles=dw_tiles, paths=paths)
     else:
-        plans = builder()
-    nbytes = _plans_nbytes(plans)
+        plans = builder(paths)
+    nbytes = plans.nbytes()
     while _CACHE and (len(_CACHE) >= _CACHE_MAX or sum(v[3] for v in _CACHE.values()) + nbytes > _CACHE_MAX_BYTES):
         _CACHE.pop(next(iter(_CACHE)))
     # hold the key tensors so their storage (and data_ptr) cannot be recycled while cached
