@@ -307,6 +307,30 @@ int rgcn_ep_segment_sum(const float* in, int ldin, const int32_t* seg_ptr, const
                         int width, const float* bias, int act, const float* mask, int ldm, int final_level, float* out, int ldo,
                         void* stream);
 
+/* ---- max aggregation (RGCNConv(aggr="max"); scaling_rgcn_training_amd/csrc/rgcn_segmax.hip, eplan.py MaxPlan) ---------------
+ * PyG 2.3.1 with aggr="max": H_r[i] = max over the edges e into i of relation r of x[src_e] (torch scatter_reduce "amax",
+ * include_self = 0: all-negative rows give a negative max), out[i] = sum_r H_r[i] W_r + x[i] root + bias.  Every (destination,
+ * relation) segment is a heavy segment of the edge-parallel plan: its rows are reduced by rgcn_segment_max, its pseudo row goes
+ * through rgcn_ep_transform and rgcn_ep_segment_sum as a sum layer's would.
+ * rgcn_segment_max: out[i] = max of rows seg_idx[q] (q itself when seg_idx is NULL) of `in` over q in [seg_ptr[i], seg_ptr[i + 1]),
+ * per column; an empty segment gives 0.  out_t (may be NULL) [n_out, ldo]: the TIE WEIGHT of every column, the sum over the
+ * rows equal to the max (-0 == +0) of their weight -- seg_w[q] (1 when seg_w is NULL), times in_t[row] when in_t is given.  Long
+ * segments are reduced in levels as with rgcn_ep_segment_sum: level 0 over the gathered rows with in_t = NULL, each further
+ * level over the (out, out_t) of the level before (in_t = its out_t, seg_idx = seg_w = NULL); equal maxima add their weights, so
+ * both outputs are the same for every cut.  A NaN in a column makes its max NaN (its tie weight is unspecified).  in and in_t
+ * share the stride ldin, out and out_t the stride ldo.
+ * rgcn_segment_max_bwd: for q < n_rows, c[q] = (x[row_src[q]] == h[s]) * row_w[q] * dh[seg_dh[s]] / n[s] per column, s =
+ * row_seg[q], n = t + (h == 0 ? 1 : 0) (row_w NULL: 1; seg_dh NULL: dh[s]; n == 0: 0) -- the gradient of a max split evenly
+ * among the rows that attain it, as torch's scatter_reduce "amax" backward splits it: with include_self = 0 torch still counts
+ * the zero its output starts from as one more tie when the max is exactly 0.  rgcn_ep_segment_sum then adds c per source.  h
+ * and t share the stride ldh.
+ * Both: widths 1..128, no workspace, no atomics, fixed orders (bit-reproducible); rows addressed with 64-bit offsets. */
+int rgcn_segment_max(const float* in, const float* in_t, int ldin, const int32_t* seg_ptr, const int32_t* seg_idx,
+                     const float* seg_w, int n_out, int width, float* out, float* out_t, int ldo, void* stream);
+int rgcn_segment_max_bwd(const float* x, int ldx, const float* h, const float* t, int ldh, const float* dh, int lddh,
+                         const int32_t* row_src, const int32_t* row_seg, const int32_t* seg_dh, const float* row_w,
+                         int64_t n_rows, int width, float* c, int ldc, void* stream);
+
 /* ---- featureless layers (scaling_rgcn_training_amd/csrc/rgcn_featureless.hip) -----------------------------------------------
  * PyG's RGCNConv with x = None or an int64 node-index vector: the weight tables are per-node embeddings,
  *   out[i] = bias + root[x_i] + sum_{slots j -> i} w_e * W_{rel}[x_j]     (x_index NULL: x_j = j, and in_rows = plan->n_nodes)

@@ -25,6 +25,7 @@ EXPORTS = (
     "rgcn_pack_weights_basis", "rgcn_pack_weights_block", "rgcn_basis_backward", "rgcn_block_backward", "rgcn_eplan_segments",
     "rgcn_featureless_geometry", "rgcn_featureless_fwd", "rgcn_featureless_bwd_workspace_bytes", "rgcn_featureless_bwd",
     "rgcn_xwide_geometry", "rgcn_xwide_fwd", "rgcn_xwide_bwd_dx", "rgcn_xwide_bwd_dw_workspace_bytes", "rgcn_xwide_bwd_dw",
+    "rgcn_segment_max", "rgcn_segment_max_bwd",
 )
 XWIDE_MAX_WIDTH = 512  # RGCN_XWIDE_MAX_WIDTH
 
@@ -160,6 +161,10 @@ def load() -> C.CDLL:
     lib.rgcn_xwide_bwd_dw_workspace_bytes.argtypes = [C.POINTER(RgcnPlanStruct), i32, i32]
     lib.rgcn_xwide_bwd_dw.restype = i32
     lib.rgcn_xwide_bwd_dw.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, vp]
+    lib.rgcn_segment_max.restype = i32
+    lib.rgcn_segment_max.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.rgcn_segment_max_bwd.restype = i32
+    lib.rgcn_segment_max_bwd.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, vp, i32, vp]
     if lib.rgcn_abi_version() != ABI_VERSION:
         raise RgcnLibraryError(f"ABI version mismatch: library {lib.rgcn_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -329,7 +334,9 @@ def plan_workspace(num_edges: int, n_owned: int, num_relations: int, tile: int, 
 
 
 def edge_weights(graph: RgcnGraphStruct, aggr: str, ws: torch.Tensor) -> torch.Tensor:
-    if aggr not in ("mean", "sum", "add"):
+    """w_e of rgcn_edge_weights: 1 / max(1, c[dst_e, rel_e]) for "mean", 1 for "sum" / "add" and for "max" (an edge's
+    multiplicity: its weight in the tie count of a max)"""
+    if aggr not in ("mean", "sum", "add", "max"):
         raise ValueError(f"unsupported aggr {aggr!r}")
     w = torch.empty(max(int(graph.num_edges), 1), dtype=torch.float32, device=ws.device)
     with torch.cuda.device(ws.device):
@@ -504,6 +511,72 @@ def eplan_segments(slot_row: torch.Tensor, n_owned: int):
         check(lib.rgcn_eplan_segments(slot_row.data_ptr(), n_slots, int(n_owned), ws.data_ptr(), ws.numel(), seg_ptr.data_ptr(),
                                       seg_idx.data_ptr(), _stream(slot_row)), "rgcn_eplan_segments")
     return seg_ptr, seg_idx
+
+
+# ---- max aggregation (eplan.MaxPlan, csrc/rgcn_segmax.hip) -----------------------------------------------------------
+def segment_max(src: torch.Tensor, src_t: Optional[torch.Tensor], ptr: torch.Tensor, idx, w, n_out: int, width: int,
+                out: torch.Tensor, out_t: Optional[torch.Tensor]) -> None:
+    """one level of rgcn_segment_max: (src, src_t) and (out, out_t) share their strides"""
+    with torch.cuda.device(src.device):
+        check(load().rgcn_segment_max(src.data_ptr(), _ptr(src_t), src.stride(0), ptr.data_ptr(), _ptr(idx), _ptr(w), int(n_out),
+                                      int(width), out.data_ptr(), _ptr(out_t), out.stride(0), _stream(src)), "rgcn_segment_max")
+
+
+def _max_plan_on(mp, device) -> None:
+    """a max plan's arrays must live on the device of the operands: the kernels read them as device pointers"""
+    h = mp.ep.heavy
+    ts = [mp.ep.slot_src] + ([] if h is None else [h.slot_src] + [lv[0] for lv in h.levels]) + [lv[0] for lv in mp.bwd_levels]
+    if any(t.device != device for t in ts):
+        raise RgcnLibraryError(f"the max plan must live on {device} (plan tensors are on {ts[0].device})")
+
+
+def max_aggregate(mp, x: torch.Tensor, din: int, with_t: bool):
+    """(H, T) of a max plan's segments: rgcn_segment_max over x, level by level (T: None unless ``with_t``).  (None, None)
+    without an edge."""
+    _max_plan_on(mp, x.device)
+    h = mp.ep.heavy
+    if h is None:
+        return None, None
+    cur, cur_t = x, None
+    for ptr, idx, w, n_out in h.levels:
+        dst = torch.empty(max(n_out, 1), x.stride(0), dtype=torch.float32, device=x.device)
+        dst_t = torch.empty_like(dst) if with_t else None
+        segment_max(cur, cur_t, ptr, idx, w, n_out, din, dst, dst_t)
+        cur, cur_t = dst, dst_t
+    return cur, cur_t
+
+
+def max_layer_dx(mp, x: torch.Tensor, hmat: Optional[torch.Tensor], tmat: Optional[torch.Tensor], g: torch.Tensor, dout: int,
+                 packed_t: torch.Tensor, dx: torch.Tensor, din: int, mask: Optional[torch.Tensor] = None, flags: int = 0) -> None:
+    """dX of a max layer into ``dx`` [n, ld]: dH per pseudo slot (rgcn_ep_transform over g with W^T), C per segment row
+    (rgcn_segment_max_bwd), the root rows g root^T (rgcn_ep_transform over the light units), then rgcn_ep_segment_sum by source
+    in the levels of ``mp.bwd_levels`` with the ReLU mask of the layer input"""
+    lib = load()
+    _max_plan_on(mp, g.device)
+    ep, h = mp.ep, mp.ep.heavy
+    ldx = dx.stride(0)
+    st = _stream(g)
+    y = torch.empty(max(mp.n_hrows + ep.n_units * 64, 1), ldx, dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        if h is not None:
+            units = getattr(mp, "_bwd_cunits", None)
+            if units is None:
+                units = mp._bwd_cunits = _edge_units(ep.n_nodes, h.n_units, ep.num_relations, h.unit_rel, h.unit_cnt, mp.bwd_slot_src,
+                                                     h.slot_w)
+            dh = torch.empty(max(h.n_units * 64, 1), ldx, dtype=torch.float32, device=g.device)
+            check(lib.rgcn_ep_transform(C.byref(units), g.data_ptr(), g.stride(0), dout, packed_t.data_ptr(), dh.data_ptr(), ldx, din,
+                                        int(flags), st), "rgcn_ep_transform (max dH)")
+            check(lib.rgcn_segment_max_bwd(x.data_ptr(), x.stride(0), hmat.data_ptr(), tmat.data_ptr(), hmat.stride(0), dh.data_ptr(), ldx,
+                                           mp.row_src.data_ptr(), mp.row_seg.data_ptr(), mp.seg_dh.data_ptr(), _ptr(mp.row_w),
+                                           mp.n_hrows, din, y.data_ptr(), ldx, st), "rgcn_segment_max_bwd")
+        check(lib.rgcn_ep_transform(C.byref(edge_units_struct(ep)), g.data_ptr(), g.stride(0), dout, packed_t.data_ptr(),
+                                    y[mp.n_hrows:].data_ptr(), ldx, din, int(flags), st), "rgcn_ep_transform (max root rows)")
+    cur = y
+    for li, (ptr, idx, n_out) in enumerate(mp.bwd_levels):
+        final = li == len(mp.bwd_levels) - 1
+        dst = dx if final else torch.empty(max(n_out, 1), ldx, dtype=torch.float32, device=g.device)
+        ep_segment_sum(cur, ptr, idx, None, n_out, din, dst, None, ACT_NONE, mask if final else None, final)
+        cur = dst
 
 
 # ---- featureless layers (csrc/rgcn_featureless.hip) -----------------------------------------------------------------

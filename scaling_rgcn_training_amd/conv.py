@@ -471,6 +471,61 @@ class _RGCNLayerFn(torch.autograd.Function):
         return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None
 
 
+class _MaxLayerFn(torch.autograd.Function):
+    """a = act(sum_r max-aggregate_r(x) @ W_r + x @ root + bias) on an eplan.MaxPlan (one GPU): H (and the tie weights T when
+    x needs a gradient) by rgcn_segment_max, then the edge-parallel transform and sums with the activation fused (_lib.ep_layer);
+    backward: dX by _lib.max_layer_dx (the gradient of a max split evenly among the rows that attain it), d_W over the pseudo
+    rows of H, d_root / d_bias by the streaming kernel (above 64 columns: rgcn_bwd_dw over the light units, the root rows)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor], mp,
+                act: int, input_relu: bool, grad_premasked: bool, flags: int, num_rel: int, dout: int):
+        n, din = x.shape
+        xp = _rows16(x, din)
+        wf, cp, rt, bs = _operands(weight, comp, root, bias)
+        packed = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
+        hmat, tmat = _lib.max_aggregate(mp, xp, din, with_t=ctx.needs_input_grad[0])
+        ldo = _round4(dout)
+        out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
+        _lib.ep_layer(mp.ep, xp, din, packed, bs, out, dout, act, None, flags, hmat=hmat)
+        ctx.mp, ctx.dims, ctx.input_relu, ctx.flags = mp, (n, din, dout, num_rel), input_relu, flags
+        ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
+        ctx.save_for_backward(xp, wf, cp, rt, hmat, tmat, out if ctx.need_a else None)
+        return out if ldo == dout else out[:, :dout]
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        xp, wf, cp, rt, hmat, tmat, a_out = ctx.saved_tensors
+        mp, flags = ctx.mp, ctx.flags
+        n, din, dout, num_rel = ctx.dims
+        need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]      # (False for an input that is None)
+        gp = _rows16(g, dout)
+        if ctx.need_a:
+            gp = _lib.act_backward(a_out, gp, ctx.act)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        dx = dw = droot = dbias = dcomp = None
+        if need_x:
+            packed_t = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=True)
+            ldx = _round4(din)
+            dxp = torch.empty(n, ldx, **f32)
+            _lib.max_layer_dx(mp, xp, hmat, tmat, gp, dout, packed_t, dxp, din, xp if ctx.input_relu else None, flags)
+            dx = dxp if ldx == din else dxp[:, :din]
+        if need_wparam or need_comp:
+            dw = torch.zeros(num_rel, din, dout, **f32) if mp.ep.heavy is None else torch.empty(num_rel, din, dout, **f32)
+            if mp.ep.heavy is not None:
+                _lib.bwd_dw(_lib.plan_struct(mp.ep.heavy_tile_plan()), hmat, din, gp, dout, dw, None, None, flags)
+        if need_root or need_bias:
+            droot = torch.empty(din, dout, **f32) if need_root else None
+            dbias = torch.empty(dout, **f32) if need_bias else None
+            if max(din, dout) <= 64:
+                _lib.bwd_dw_root(xp, din, gp, dout, droot, dbias)
+            else:        # (the light units hold the root rows alone: their relation-major walk is the root-only walk)
+                _lib.bwd_dw(_lib.plan_struct(mp.ep.as_tile_plan()), xp, din, gp, dout, None, droot, dbias, flags)
+        if dw is not None and (cp is not None or wf.dim() == 4):
+            dw, dcomp = _lib.decomposed_weight_grads(dw, wf, cp, need_wparam, need_comp)
+        return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None
+
+
 class _XwideFn(torch.autograd.Function):
     """A layer with a side above 128 on csrc/rgcn_xwide.hip (one GPU, layout-0 plans): dX on the transposed plan, the weight
     gradients on the forward plan; a decomposition composed into / differentiated from a dense operand by torch ops."""
@@ -634,6 +689,13 @@ class RGCNConv(nn.Module):
     ``wide`` (opt-in; ``None``: ``RGCN_WIDE=1`` in the environment at import time switches it on): up to 512 features per side.
     A layer with both sides at most 128 runs exactly as without it; one with a side above 128 runs on the kernels of
     ``csrc/rgcn_xwide.hip`` (exact fp32) -- one GPU, no ``dist`` context, ``path`` not pinned to ``"ep"``.  Not with ``featureless``.
+
+    ``aggr="max"``: PyG's max aggregation -- ``H_r[i]`` = the column-wise max of ``x[src]`` over the edges of relation r into i
+    (no edge: 0), ``out[i] = sum_r H_r[i] W_r + x[i] root + bias``, in full, basis and block modes; the gradient of a max is split
+    evenly among the edges that attain it (torch ``scatter_reduce(..., "amax", include_self=False)``, duplicate edges counted).
+    It runs on its own kernels (``csrc/rgcn_segmax.hip`` with the edge-parallel transform and sums; plan: ``eplan.MaxPlan``) and
+    has one path: ``path`` and ``RGCN_PATH`` are ignored.  One GPU only (no ``dist`` context; ``edge_index`` / ``edge_type`` on
+    the device of ``x``), up to 128 features per side, not with ``featureless``.
     """
 
     def __init__(self, in_channels: int, out_channels: int, num_relations: int,
@@ -660,8 +722,13 @@ class RGCNConv(nn.Module):
             if in_channels[0] != in_channels[1]:
                 raise NotImplementedError("bipartite RGCNConv is not used by the reference and not built")
             in_channels = in_channels[0]
-        if aggr not in ("mean", "sum", "add"):
-            raise ValueError(f"unsupported aggr {aggr!r} (mean / sum)")
+        if aggr not in ("mean", "sum", "add", "max"):
+            raise ValueError(f"unsupported aggr {aggr!r} (mean / sum / max)")
+        if aggr == "max" and self.featureless:
+            raise ValueError("featureless RGCNConv has no max aggregation: aggr='max' takes float features x")
+        if aggr == "max" and self.wide and max(in_channels, out_channels) > NARROW_MAX_WIDTH:
+            raise NotImplementedError(f"RGCNConv(aggr='max') takes 1..{NARROW_MAX_WIDTH} features per side, got "
+                                      f"{in_channels}->{out_channels} (wide layers aggregate by mean / sum only)")
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.num_relations = num_relations
@@ -771,6 +838,8 @@ class RGCNConv(nn.Module):
         ranges to it), or at the tile that leaves the exact-fp32 kernel room for shadow row tiles where it walks layout-3 plans."""
         if self.xwide:
             raise NotImplementedError("RGCNConv wider than 128 runs on one GPU only: no dist layout")
+        if self.aggr == "max":
+            raise NotImplementedError("RGCNConv(aggr='max') runs on one GPU only: a dist context is not supported")
         tile, chunk = layout_for(self.in_channels, self.out_channels, n_nodes, n_edges, self.num_relations)
         # the tile-major weight-gradient kernel: 64 x 64 layers with few relations on graphs large enough to fill it
         dw_rule = self.dw_tiles and self._w64 and self.num_relations <= 32 and n_edges >= DW_TILES_MIN_EDGES
@@ -803,6 +872,8 @@ class RGCNConv(nn.Module):
 
     def layout(self, n_nodes: int, n_edges: int) -> Tuple[int, int]:
         """(tile, chunk) of this layer's plans on a graph of that size (``_route``; they do not depend on the device)"""
+        if self.aggr == "max":
+            raise NotImplementedError("RGCNConv(aggr='max') has no tile layout: it runs on its own edge-parallel plan (eplan.MaxPlan)")
         r = self._route(n_nodes, n_edges, False)
         return r.tile, r.chunk
 
@@ -822,6 +893,8 @@ class RGCNConv(nn.Module):
                                       "(x is always float: model/layers.py:21,62,108) and is not built")
         if x.dim() != 2 or x.shape[1] != self.in_channels:
             raise ValueError(f"x must be [N, {self.in_channels}], got {tuple(x.shape)}")
+        if self.aggr == "max":
+            return self._forward_max(x, edge_index, edge_type, _activation, _input_relu, _grad_premasked)
         if self.xwide:
             return self._forward_xwide(x, edge_index, edge_type, _activation, _input_relu, _grad_premasked)
         route = self._route(x.shape[0], int(edge_type.shape[0]), x.is_cuda)
@@ -848,6 +921,28 @@ class RGCNConv(nn.Module):
         return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, None, activation, input_relu,
                                   grad_premasked and activation == "relu", 0, comp=self.comp, num_relations=self.num_relations,
                                   out_channels=self.out_channels, xwide=True)
+
+    def _forward_max(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, activation: Optional[str], input_relu: bool,
+                     grad_premasked: bool) -> Tensor:
+        if self.dist is not None:
+            raise NotImplementedError("RGCNConv(aggr='max') runs on one GPU: a dist context is not supported")
+        if x.device.type != "cuda":
+            raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+        if edge_index.device != x.device or edge_type.device != x.device:
+            # (the plan is built where the edges live: a CPU plan's index arrays must never reach a kernel)
+            raise RuntimeError(f"RGCNConv(aggr='max'): edge_index ({edge_index.device}) and edge_type ({edge_type.device}) must be on "
+                               f"the device of x ({x.device})")
+        if activation not in _ACT_CODES:
+            raise ValueError(f"fused activation must be one of {list(_ACT_CODES)}")
+        _lib.load()
+        from .eplan import build_max_plan
+        n, r = int(x.shape[0]), self.num_relations
+        mp = cached_graph_plans(edge_index, edge_type, n, r, 0, "max", paths=("ep", "ep"), extra_key=("max",),
+                                builder=lambda paths: build_max_plan(edge_index, edge_type, n, r))
+        # the bf16 x 3 (fp32-equivalent) transform of 64 x 64 layers, as on the edge-parallel path
+        flags = self.kernel_flags | (_lib.FLAG_SPLIT_PRODUCERS if self.split_producers and self._w64 else 0)
+        return _MaxLayerFn.apply(x, self.weight, self.comp, self.root, self.bias, mp, _ACT_CODES[activation], bool(input_relu),
+                                 bool(grad_premasked and activation == "relu"), int(flags), r, self.out_channels)
 
     def _forward_featureless(self, x: Optional[Tensor], edge_index: Tensor, edge_type: Tensor) -> Tensor:
         if self.dist is not None:

@@ -361,12 +361,13 @@ def attach(module: torch.nn.Module, n_nodes: int, n_edges: int, group=None, edge
     ``edge_type`` + ``split_hubs`` (default on): the cut leaves out the rows of heavy (node, relation) segments, which the
     edge-parallel path deals over all ranks (eplan.SharedHeavy)."""
     from .eplan import resolve_paths
-    for m in module.modules():
-        if isinstance(m, RGCNConv):
-            # (on_gpu=True: r.paths is the layer's setting, not the CPU override; tile and chunk do not depend on it)
-            r = m._route(n_nodes, n_edges, on_gpu=True)
-            paths = ("ring", "ring")
-            if edge_type is not None and split_hubs and edge_index is not None:
-                # the path every rank will take per direction (the whole graph's choice: cached_rank_plans decides the same way)
-                paths = resolve_paths(r.paths, edge_index, n_nodes, m.num_relations, (m.in_channels, m.out_channels), r.tile, r.chunk)
-            m.dist = make_context(n_nodes, r.tile, group, pieces, edge_index, balance, exchange, emulate, edge_type, split_hubs, tuple(paths))
+    convs = [m for m in module.modules() if isinstance(m, RGCNConv)]
+    # (on_gpu=True: r.paths is the layer's setting, not the CPU override; tile and chunk do not depend on it.  Every layer is routed
+    # before any is attached: a layer without a dist layout -- wider than 128, max aggregation -- refuses the whole module)
+    routes = [m._route(n_nodes, n_edges, on_gpu=True) for m in convs]
+    for m, r in zip(convs, routes):
+        paths = ("ring", "ring")
+        if edge_type is not None and split_hubs and edge_index is not None:
+            # the path every rank will take per direction (the whole graph's choice: cached_rank_plans decides the same way)
+            paths = resolve_paths(r.paths, edge_index, n_nodes, m.num_relations, (m.in_channels, m.out_channels), r.tile, r.chunk)
+        m.dist = make_context(n_nodes, r.tile, group, pieces, edge_index, balance, exchange, emulate, edge_type, split_hubs, tuple(paths))

@@ -458,6 +458,89 @@ def build_edge_plan_device(graph, w: Tensor, transposed: bool, n_nodes: int, num
     return ep
 
 
+# ---- max aggregation (RGCNConv(aggr="max"), csrc/rgcn_segmax.hip) ------------------------------------------------------
+@dataclass
+class MaxPlan:
+    """The plan of a max layer (one GPU, the whole node range).  PyG aggregates before the transform, so every (destination,
+    relation) segment is a heavy segment of the forward edge plan (``build_edge_plan(..., heavy=1)``, every edge weight 1):
+    rgcn_segment_max reduces the rows of ``ep.heavy`` level by level into H (and the tie weights T), the segments' pseudo rows
+    and the light units -- the root rows alone -- go through rgcn_ep_transform and rgcn_ep_segment_sum as a sum layer's would.
+    Backward: the pseudo units again, gathering g at the segment's destination (``bwd_slot_src``), give dH per pseudo slot
+    (rgcn_ep_transform with W^T); rgcn_segment_max_bwd writes one row C[q] per segment row; ``bwd_levels`` index
+    Y = [C; the light units' slots over g with root^T] source by source for rgcn_ep_segment_sum.  d_W: the pseudo rows over H
+    (EdgePlan.heavy_tile_plan)."""
+    ep: EdgePlan
+    n_hrows: int                     # rows of the segments: the edges, duplicates counted (0: no edge, ep.heavy is None)
+    row_src: Optional[Tensor]        # int32 [n_hrows]: gathered row of every segment row (ep.heavy's level-0 seg_idx)
+    row_w: Optional[Tensor]          # float32 [n_hrows]: its weight, 1 (its level-0 seg_w)
+    row_seg: Optional[Tensor]        # int32 [n_hrows]: its segment (row of H and T)
+    seg_dh: Optional[Tensor]         # int32 [n_seg]: the segment's pseudo slot (row of dH)
+    bwd_slot_src: Optional[Tensor]   # int32 [heavy.n_units * 64]: the pseudo slots gather g[destination] (padding: n_nodes)
+    bwd_levels: list                 # [(seg_ptr int32, seg_idx int32 or None, n_out)]: Y by source, level 0 over the rows of Y
+
+    @property
+    def n_nodes(self) -> int:
+        return self.ep.n_nodes
+
+    @property
+    def n_seg(self) -> int:
+        return 0 if self.ep.heavy is None else self.ep.heavy.n_seg
+
+    def nbytes(self) -> int:
+        ts = [t for t in (self.row_seg, self.seg_dh, self.bwd_slot_src) if t is not None]
+        ts += [t for lv in self.bwd_levels for t in lv[:2] if t is not None]
+        return self.ep.nbytes() + sum(t.numel() * t.element_size() for t in ts)
+
+
+def _max_backward(ep: EdgePlan, piece: int, on_device: bool) -> MaxPlan:
+    """the backward arrays of a max plan from its forward edge plan -- the same torch ops on either device, the source-major sort
+    by rgcn_eplan_segments on the GPU (as _finish_levels)"""
+    h, n = ep.heavy, ep.n_nodes
+    if h is None:              # no edge: the root rows alone
+        levels, _, _ = _finish_levels(ep.slot_src, None, n, piece, on_device)
+        return MaxPlan(ep=ep, n_hrows=0, row_src=None, row_w=None, row_seg=None, seg_dh=None, bwd_slot_src=None, bwd_levels=levels)
+    dev = ep.device
+    _, row_src, row_w, _ = h.levels[0]
+    n_hrows = int(row_src.numel())
+    seg = torch.arange(n_hrows, device=dev)
+    for ptr, _, _, n_out in h.levels:          # a row's piece, the piece's piece, ...: its segment
+        seg = torch.repeat_interleave(torch.arange(n_out, device=dev), (ptr[1:] - ptr[:-1]).to(torch.int64))[seg]
+    real = torch.nonzero(h.slot_src < h.n_seg).squeeze(1)
+    seg_dh = torch.empty(h.n_seg, dtype=torch.int32, device=dev)
+    seg_dh[h.slot_src[real].to(torch.int64)] = real.to(torch.int32)
+    bwd_slot_src = torch.where(h.slot_row < ep.n_owned, h.slot_row + ep.node_begin, torch.full_like(h.slot_row, n)).to(torch.int32)
+    # Y = [C (one row per segment row, summed into its gathered row); light slots (root rows: into the node itself)]
+    levels, _, _ = _finish_levels(torch.cat([row_src, ep.slot_src]), None, n, piece, on_device)
+    return MaxPlan(ep=ep, n_hrows=n_hrows, row_src=row_src, row_w=row_w, row_seg=seg.to(torch.int32), seg_dh=seg_dh,
+                   bwd_slot_src=bwd_slot_src, bwd_levels=levels)
+
+
+def build_max_plan(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int, piece: int = PIECE) -> MaxPlan:
+    """The max plan of a graph: on the GPU by the library's builder (build_edge_plan_device with every segment heavy), on the
+    CPU by its torch twin (build_edge_plan) -- identical arrays.  ValueError past EP_MAX_OWNED nodes, before anything is built."""
+    if n_nodes > EP_MAX_OWNED:
+        raise ValueError(f"RGCNConv(aggr='max') on {n_nodes} nodes: its edge-parallel plan holds at most EP_MAX_OWNED = 2^24 = "
+                         f"{EP_MAX_OWNED} nodes, and a max layer has no other plan")
+    e = int(edge_type.shape[0])
+    if edge_type.device.type == "cuda":
+        from . import _lib
+        graph, keep = _lib.graph_struct(edge_index, edge_type, n_nodes, num_relations)
+        ws = _lib.plan_workspace(e, n_nodes, num_relations, 16, edge_type.device)
+        try:
+            w = _lib.edge_weights(graph, "max", ws)
+        except _lib.RgcnLibraryError as err:
+            if "out of range" in str(err):
+                raise ValueError("edge_index / edge_type out of range [0, num_nodes) / [0, num_relations)") from err
+            raise
+        ep = build_edge_plan_device(graph, w, False, n_nodes, num_relations, ws, piece=piece, heavy=1, edge_index=edge_index,
+                                    edge_type=edge_type)
+        del keep
+        return _max_backward(ep, piece, True)
+    w = torch.ones(e, dtype=torch.float32)
+    ep = build_edge_plan(edge_index[0], edge_index[1], edge_type, w, n_nodes, num_relations, piece=piece, heavy=1)
+    return _max_backward(ep, piece, False)
+
+
 # ---- which path: cost model of one forward / dX launch ---------------------------------------------------------------
 def ring_launch_us(n_nodes: int, n_edges: int, num_relations: int, width: int, tile: int, chunk: int,
                    max_tile_rows: int) -> float:

@@ -99,8 +99,9 @@ class TilePlan:
 
 
 def edge_weights(src: Tensor, dst: Tensor, rel: Tensor, num_relations: int, aggr: str = "mean") -> Tensor:
-    """w_e = 1 / max(1, c[dst_e, rel_e]) (duplicates counted), float32, in input edge order."""
-    if aggr in ("sum", "add"):
+    """w_e = 1 / max(1, c[dst_e, rel_e]) (duplicates counted), float32, in input edge order; 1 for "sum" / "add" and for "max"
+    (an edge's multiplicity: its weight in the tie count of a max, eplan.MaxPlan)."""
+    if aggr in ("sum", "add", "max"):
         return torch.ones(dst.shape[0], dtype=torch.float32, device=dst.device)
     if aggr != "mean":
         raise ValueError(f"unsupported aggr {aggr!r}")

@@ -1,0 +1,254 @@
+"""Max aggregation, host side (eplan.MaxPlan, RGCNConv(aggr="max")): the plan walked by a float64 numpy twin of the contracts of
+rgcn_segment_max / rgcn_segment_max_bwd and of the edge-parallel transform and sums reproduces the float64 torch reference
+(tests/max_reference.py) -- output and every gradient; the refusals; the argument checks of the two entry points.  CPU only."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from scaling_rgcn_training_amd import _lib, eplan as E
+from scaling_rgcn_training_amd.conv import RGCNConv
+from tests import max_reference as M
+
+
+def _transform(n_units, unit_rel, unit_cnt, slot_src, slot_w, rows, w_all):
+    """rgcn_ep_transform: z[slot] = w_slot * (rows[src_slot] @ W_rel) on the used row tiles (padding gathers zeros)"""
+    z = np.full((n_units * 64, w_all.shape[2]), np.nan)
+    src, sw = slot_src.numpy(), slot_w.numpy().astype(np.float64)
+    rr = np.concatenate([rows, np.zeros((1, rows.shape[1]))], 0)[np.minimum(src, rows.shape[0])]
+    rel = np.repeat(unit_rel.numpy(), 64)
+    used = (np.arange(64)[None, :] < unit_cnt.numpy()[:, None]).reshape(-1)
+    for r in range(w_all.shape[0]):
+        m = (rel == r) & used
+        z[m] = (rr[m] @ w_all[r]) * sw[m][:, None]
+    return z
+
+
+def _sums(levels, rows):
+    """rgcn_ep_segment_sum, level by level"""
+    cur = rows
+    for ptr, idx, n_out in levels:
+        ptr = ptr.numpy()
+        ii = idx.numpy() if idx is not None else np.arange(int(ptr[-1]))
+        cur = np.stack([cur[ii[ptr[i]:ptr[i + 1]]].sum(0) for i in range(n_out)]) if n_out else np.zeros((0, cur.shape[1]))
+    return cur
+
+
+def segment_max_twin(levels, x, with_t=True):
+    """rgcn_segment_max level by level: (H, T).  Level 0 gathers rows of x with their weights as tie weights; a further level
+    combines (max, T) pairs: the larger max, or the sum of T for equal maxima"""
+    cur, cur_t = x, None
+    for ptr, idx, w, n_out in levels:
+        ptr = ptr.numpy()
+        ii = idx.numpy() if idx is not None else np.arange(int(ptr[-1]))
+        ww = w.numpy().astype(np.float64) if w is not None else np.ones(ii.shape[0])
+        vals = cur[ii]
+        ties = (cur_t[ii] if cur_t is not None else np.ones_like(vals)) * ww[:, None]
+        out, out_t = np.zeros((n_out, x.shape[1])), np.zeros((n_out, x.shape[1]))
+        for i in range(n_out):
+            v, t = vals[ptr[i]:ptr[i + 1]], ties[ptr[i]:ptr[i + 1]]
+            if v.shape[0]:
+                out[i] = v.max(0)
+                out_t[i] = np.where(v == out[i], t, 0).sum(0)
+        cur, cur_t = out, out_t
+    return cur, cur_t
+
+
+def emulate_max_layer(mp, x, w_all, bias, g):
+    """float64 twin of conv._MaxLayerFn on the plan: (out, dx, dW [R], d_root, d_bias).  w_all: [R + 1, in, out], root last."""
+    ep, h = mp.ep, mp.ep.heavy
+    n, r = x.shape[0], w_all.shape[0] - 1
+    wt = np.ascontiguousarray(np.transpose(w_all, (0, 2, 1)))
+    z = _transform(ep.n_units, ep.unit_rel, ep.unit_cnt, ep.slot_src, ep.slot_w, x, w_all)
+    hm = tm = None
+    if h is not None:
+        hm, tm = segment_max_twin(h.levels, x)
+        z = np.concatenate([z, _transform(h.n_units, h.unit_rel, h.unit_cnt, h.slot_src, h.slot_w, hm, w_all)], 0)
+    out = _sums(ep.levels, z) + bias
+    # backward
+    zr = _transform(ep.n_units, ep.unit_rel, ep.unit_cnt, ep.slot_src, ep.slot_w, g, wt)
+    dw = np.zeros((r,) + w_all.shape[1:])
+    if h is not None:
+        dh = _transform(h.n_units, h.unit_rel, h.unit_cnt, mp.bwd_slot_src, h.slot_w, g, wt)
+        src, seg = mp.row_src.numpy(), mp.row_seg.numpy()
+        d = mp.seg_dh.numpy()[seg]
+        nt = tm[seg] + (hm[seg] == 0)          # torch's amax backward counts its zero start as a tie when the max is 0
+        c = np.where(x[src] == hm[seg], mp.row_w.numpy()[:, None] * dh[d] / nt, 0.0)
+        y = np.concatenate([c, zr], 0)
+        # d_W_r = sum over the pseudo rows of H[seg]^T g[dst]
+        real = h.slot_src.numpy() < h.n_seg
+        rel = np.repeat(h.unit_rel.numpy(), 64)[real]
+        hs, dst = h.slot_src.numpy()[real], h.slot_row.numpy()[real]
+        for q in range(r):
+            m = rel == q
+            dw[q] = hm[hs[m]].T @ g[dst[m]]
+    else:
+        y = zr
+    dx = _sums(mp.bwd_levels, y)
+    return out, dx, dw, x.T @ g, g.sum(0)
+
+
+def _torch_reference(x, ei, et, w_all, bias, r):
+    """float64 reference with dense weights: out and the gradients of x, W, root, bias under upstream gradient g"""
+    xt = torch.from_numpy(x).requires_grad_(True)
+    w = torch.from_numpy(w_all[:r].copy()).requires_grad_(True)
+    root = torch.from_numpy(w_all[r].copy()).requires_grad_(True)
+    b = torch.from_numpy(bias.copy()).requires_grad_(True)
+    out = M.max_layer(xt, ei, et, w, None, root, b, r)
+    return out, (xt, w, root, b)
+
+
+CASES = [("plain", "normal"), ("plain", "ties"), ("plain", "negative"), ("hubs", "ties"), ("hubs", "normal"), ("empty", "normal")]
+
+
+@pytest.mark.parametrize("piece", [E.PIECE, 8])
+@pytest.mark.parametrize("graph,feat", CASES)
+def test_max_plan_walk_matches_torch_reference(graph, feat, piece):
+    n, r, din, dout = 300, 5, 6, 3
+    ei, et = M.graph_case(graph, n=n, r=r)
+    x = M.features(feat, n, din).double().numpy()
+    rng = np.random.default_rng(7)
+    w_all = rng.standard_normal((r + 1, din, dout))
+    bias = rng.standard_normal(dout)
+    g = rng.standard_normal((n, dout))
+    mp = E.build_max_plan(ei, et, n, r, piece=piece)
+    if graph == "hubs":      # a destination hub walked in levels forward, a source hub in levels backward
+        assert len(mp.ep.heavy.levels) >= 2 and len(mp.bwd_levels) >= 2
+    if graph == "empty":
+        assert mp.ep.heavy is None and mp.n_hrows == 0
+    else:
+        assert mp.n_hrows == ei.shape[1] and mp.ep.n_rows == n      # every edge in a segment; the light units: the root rows
+    out, dx, dw, droot, dbias = emulate_max_layer(mp, x, w_all, bias, g)
+    ref, (xt, w, root, b) = _torch_reference(x, ei, et, w_all, bias, r)
+    ref.backward(torch.from_numpy(g))
+    tol = dict(rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(out, ref.detach().numpy(), **tol)
+    np.testing.assert_allclose(dx, xt.grad.numpy(), **tol)
+    np.testing.assert_allclose(dw, w.grad.numpy(), **tol)
+    np.testing.assert_allclose(droot, root.grad.numpy(), **tol)
+    np.testing.assert_allclose(dbias, b.grad.numpy(), **tol)
+
+
+def test_tie_weights_count_duplicates_and_signed_zeros():
+    """T counts every edge that attains the max, duplicate triples included; -0 ties with +0; a NaN makes the max NaN"""
+    ei = torch.tensor([[1, 1, 2, 3, 4, 5], [0, 0, 0, 0, 0, 0]])
+    et = torch.zeros(6, dtype=torch.int64)
+    x = np.array([[0.], [2.], [2.], [1.], [-0.], [0.]])
+    mp = E.build_max_plan(ei, et, 6, 1)
+    h, t = segment_max_twin(mp.ep.heavy.levels, x)
+    assert h[0, 0] == 2.0 and t[0, 0] == 3.0                # rows 1, 1 (a duplicate) and 2
+    x2 = np.array([[0.], [-1.], [-2.], [-1.], [-0.], [0.]])
+    h, t = segment_max_twin(mp.ep.heavy.levels, x2)
+    assert h[0, 0] == 0.0 and t[0, 0] == 2.0                # -0 and +0
+    x3 = np.array([[0.], [-1.], [np.nan], [-1.], [-0.], [0.]])
+    h, _ = segment_max_twin(mp.ep.heavy.levels, x3)
+    assert np.isnan(h[0, 0])
+
+
+def test_max_plan_layout():
+    """the plan arrays: every segment heavy, a segment's rows contiguous, seg_dh the inverse of the pseudo slots, the backward
+    pseudo slots gathering the destination"""
+    ei, et = M.graph_case("hubs", n=300, r=5)
+    mp = E.build_max_plan(ei, et, 300, 5)
+    h = mp.ep.heavy
+    seg = mp.row_seg.long()
+    assert torch.all(seg[1:] >= seg[:-1]) and int(seg.max()) == h.n_seg - 1
+    assert torch.equal(h.slot_src[mp.seg_dh.long()], torch.arange(h.n_seg, dtype=torch.int32))
+    assert torch.equal(mp.bwd_slot_src[mp.seg_dh.long()], h.slot_row[mp.seg_dh.long()])
+    pad = h.slot_src == h.n_seg
+    assert torch.all(mp.bwd_slot_src[pad] == 300)
+    # the segment keys: (relation, destination) of every pseudo row against the edges
+    rel = h.unit_rel.repeat_interleave(64)[mp.seg_dh.long()].long()
+    keys = torch.unique(et * 300 + ei[1])
+    assert torch.equal(rel * 300 + h.slot_row[mp.seg_dh.long()].long(), keys)
+    assert mp.nbytes() > mp.ep.nbytes()
+
+
+def test_owned_range_past_2_24_is_refused_before_any_build():
+    ei = torch.zeros(2, 3, dtype=torch.int64)
+    et = torch.zeros(3, dtype=torch.int64)
+    with pytest.raises(ValueError, match="EP_MAX_OWNED") as err:
+        E.build_max_plan(ei, et, E.EP_MAX_OWNED + 1, 2)
+    assert "aggr='max'" in str(err.value) and "path" not in str(err.value)      # a max layer has no other path to advise
+
+
+def test_layout_of_a_max_layer_is_refused_with_its_own_message():
+    conv = RGCNConv(8, 4, 3, aggr="max")
+    with pytest.raises(NotImplementedError, match="no tile layout") as err:
+        conv.layout(100, 1000)
+    assert "dist" not in str(err.value)
+
+
+def test_a_plan_off_the_operands_device_never_reaches_a_kernel():
+    """_lib.max_aggregate / max_layer_dx refuse a max plan whose arrays live on another device than the operands (a CPU plan
+    with GPU features: its host pointers would reach the kernels) before anything is launched"""
+    ei, et = M.graph_case("plain", n=50, e=200, r=3)
+    for graph in ((ei, et), M.graph_case("empty")):
+        mp = E.build_max_plan(*graph, 50, 3)
+        with pytest.raises(_lib.RgcnLibraryError, match="max plan must live on cuda"):
+            _lib._max_plan_on(mp, torch.device("cuda:0"))
+        _lib._max_plan_on(mp, torch.device("cpu"))
+
+
+def test_constructor_refusals(monkeypatch):
+    from scaling_rgcn_training_amd import conv as CV
+    RGCNConv(8, 4, 3, aggr="max")
+    RGCNConv(128, 128, 3, aggr="max", num_bases=2)
+    RGCNConv(128, 64, 3, aggr="max", num_blocks=4, wide=True)        # at <= 128 per side wide is a no-op
+    for bad in ("min", "mul", "std", "maximum"):
+        with pytest.raises(ValueError, match="unsupported aggr"):
+            RGCNConv(8, 4, 3, aggr=bad)
+    with pytest.raises(ValueError, match="featureless"):
+        RGCNConv(10, 4, 3, aggr="max", featureless=True)
+    with pytest.raises(NotImplementedError, match="aggr='max'"):
+        RGCNConv(200, 64, 3, aggr="max", wide=True)
+    with pytest.raises(ValueError):                                   # above 128 without wide: refused as for every aggr
+        RGCNConv(200, 64, 3, aggr="max")
+    monkeypatch.setattr(CV, "_WIDE_DEFAULT", True)                    # RGCN_WIDE=1 at import time
+    with pytest.raises(NotImplementedError, match="aggr='max'"):
+        RGCNConv(64, 300, 3, aggr="max")
+    assert RGCNConv(64, 64, 3, aggr="max").aggr == "max"
+
+
+def test_dist_attach_refuses_a_max_layer():
+    from scaling_rgcn_training_amd import dist
+    from scaling_rgcn_training_amd.layers import Emb_Layers
+    model = Emb_Layers(3, 8, 2, 50, 8, None)
+    model.rgcn2 = RGCNConv(8, 2, 3, aggr="max")
+    with pytest.raises(NotImplementedError, match="aggr='max'"):
+        dist.attach(model, 50, 200, emulate=(2, 0))
+    assert model.rgcn1.dist is None and model.rgcn2.dist is None    # nothing was attached
+
+
+def test_max_layer_refuses_cpu_tensors():
+    conv = RGCNConv(8, 4, 3, aggr="max")
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        conv(torch.randn(5, 8), torch.tensor([[0, 1], [1, 2]]), torch.tensor([0, 1]))
+
+
+_DUMMY = (ctypes.c_float * 64)()
+NULL, WIDTH, STRIDE, PLAN = -1, -2, -3, -4
+
+
+def test_segment_max_argument_refusals():
+    """every refusal of rgcn_segment_max / rgcn_segment_max_bwd comes back as a status code before anything touches a device"""
+    lib = _lib.load()
+    d = ctypes.addressof(_DUMMY)
+
+    def fwd(src=d, src_t=None, ldin=16, ptr=d, idx=None, w=None, n_out=4, width=16, out=d, out_t=None, ldo=16):
+        return lib.rgcn_segment_max(src, src_t, ldin, ptr, idx, w, n_out, width, out, out_t, ldo, None)
+
+    def bwd(x=d, ldx=16, h=d, t=d, ldh=16, dh=d, lddh=16, rs=d, rg=d, sd=None, rw=None, n=4, width=16, c=d, ldc=16):
+        return lib.rgcn_segment_max_bwd(x, ldx, h, t, ldh, dh, lddh, rs, rg, sd, rw, n, width, c, ldc, None)
+
+    assert fwd(src=None) == NULL and fwd(ptr=None) == NULL and fwd(out=None) == NULL
+    for k in ("x", "h", "t", "dh", "rs", "rg", "c"):
+        assert bwd(**{k: None}) == NULL, k
+    assert fwd(n_out=-1) == PLAN and bwd(n=-1) == PLAN and bwd(n=1 << 31) == PLAN
+    for w in (0, 129, -1):
+        assert fwd(width=w, ldin=256, ldo=256) == WIDTH and bwd(width=w, ldx=256, ldh=256, lddh=256, ldc=256) == WIDTH
+    for width, ld in ((16, 12), (16, 18), (5, 4), (5, 6), (1, 2), (128, 124), (16, 0)):
+        assert fwd(width=width, ldin=ld) == STRIDE and fwd(width=width, ldo=ld) == STRIDE, (width, ld)
+        for k in ("ldx", "ldh", "lddh", "ldc"):
+            assert bwd(width=width, **{k: ld}) == STRIDE, (width, ld, k)
