@@ -324,7 +324,9 @@ int rgcn_ep_segment_sum(const float* in, int ldin, const int32_t* seg_ptr, const
  * among the rows that attain it, as torch's scatter_reduce "amax" backward splits it: with include_self = 0 torch still counts
  * the zero its output starts from as one more tie when the max is exactly 0.  rgcn_ep_segment_sum then adds c per source.  h
  * and t share the stride ldh.
- * Both: widths 1..128, no workspace, no atomics, fixed orders (bit-reproducible); rows addressed with 64-bit offsets. */
+ * Both: widths 1..128, no workspace, no atomics, fixed orders (bit-reproducible); rows addressed with 64-bit offsets.  Inputs
+ * hold zeros in their pad columns [width, roundup4(width)) (the rule of every operand); out, out_t and c are written as +0.0
+ * there (out_t too: the zeros of the inputs' pad columns all tie, and their count is not part of the tie weights). */
 int rgcn_segment_max(const float* in, const float* in_t, int ldin, const int32_t* seg_ptr, const int32_t* seg_idx,
                      const float* seg_w, int n_out, int width, float* out, float* out_t, int ldo, void* stream);
 int rgcn_segment_max_bwd(const float* x, int ldx, const float* h, const float* t, int ldh, const float* dh, int lddh,

@@ -29,7 +29,7 @@ struct SegMaxArgs {
     const float* seg_w;
     float* out;
     float* out_t;            // NULL: T is not written
-    int ldin, ldo, width4, n_out;
+    int ldin, ldo, width, width4, n_out;
 };
 
 // (m, t) <- (m, t) combined with (v, w): a larger value (or a NaN, which then stays: torch's amax propagates it) replaces the
@@ -86,7 +86,14 @@ __global__ void __launch_bounds__(256) rgcn_segment_max_kernel(const SegMaxArgs 
     }
     const size_t oo = (size_t)seg * a.ldo + 4 * piece;
     *(f32x4*)(a.out + oo) = m;
-    if (a.out_t != nullptr) *(f32x4*)(a.out_t + oo) = t;
+    if (a.out_t != nullptr) {
+        // the pad columns [width, round4(width)) hold +0.0 as every output's do (x's pad columns are zeros that all tie: their
+        // count is not part of T)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (4 * piece + c >= a.width) t[c] = 0.f;
+        *(f32x4*)(a.out_t + oo) = t;
+    }
 }
 
 struct SegMaxBwdArgs {
@@ -152,6 +159,7 @@ extern "C" int rgcn_segment_max(const float* in, const float* in_t, int ldin, co
     a.out_t = out_t;
     a.ldin = ldin;
     a.ldo = ldo;
+    a.width = width;
     a.width4 = (width + 3) / 4;
     a.n_out = n_out;
     const int G = lanes_per_row(a.width4);

@@ -136,3 +136,86 @@ def conditions(conv, x: torch.Tensor, ei: torch.Tensor, et: torch.Tensor, g: tor
 def num_blocks_for(din: int, dout: int) -> int:
     """the largest of 4, 2, 1 that divides both widths"""
     return max(b for b in (4, 2, 1) if din % b == 0 and dout % b == 0 and math.gcd(din, dout) % b == 0)
+
+
+# ---- at scale: a graph with an exact segment count, and the layer relation by relation in row blocks (any device) ------------
+def exact_segment_graph(n: int, r: int, n_seg: int, extra: int, device, seed: int, hub: int = 70_000, dup: int = 50_000):
+    """A graph of exactly ``n_seg`` distinct (destination, relation) pairs over relations 0 .. r - 2 (relation r - 1 stays dead):
+    pair k is ``(m - 1 + k a) mod m`` of the m = n (r - 1) pairs ``dst * (r - 1) + rel``, a coprime to m, so the pairs are
+    distinct and pair 0 is (n - 1, r - 2): the last node is a destination and the last segment is not empty.  Then, into
+    existing pairs only (the count does not move): ``extra`` more rows, ``hub`` rows into pair 1 (one long segment), ``hub``
+    out-edges of node 7 (one long source), the last node as a source, and the first ``dup`` edges once more (duplicate
+    triples).  Returns the dict of tests/test_gpu_past_4gib.py make_graph (without its mean weights): n, r, ei, et and the
+    edges sorted by relation (src_s, dst_s, bounds)."""
+    live = r - 1
+    m = n * live
+    assert 2 <= n_seg <= m and live >= 1
+    a = 2654435761 % m
+    while math.gcd(a, m) != 1:
+        a += 1
+    g = torch.Generator(device=device).manual_seed(seed)
+    p = (m - 1 + torch.arange(n_seg, device=device) * a) % m
+    more = lambda k: p[torch.randint(0, n_seg, (k,), generator=g, device=device)]
+    p = torch.cat([p, more(extra), p[1].expand(hub), more(hub)])
+    src = torch.randint(0, n, (p.numel(),), generator=g, device=device)
+    src[0] = n - 1
+    src[-hub:] = 7
+    p, src = torch.cat([p, p[:dup]]), torch.cat([src, src[:dup]])
+    dst, et = p // live, p % live
+    ei = torch.stack([src, dst]).contiguous()
+    perm = torch.argsort(et, stable=True)
+    counts = torch.bincount(et, minlength=r).tolist()
+    bounds, lo = [], 0
+    for c in counts:
+        bounds.append((lo, lo + c))
+        lo += c
+    assert counts[r - 1] == 0
+    return dict(n=n, r=r, ei=ei, et=et.contiguous(), src_s=src[perm], dst_s=dst[perm], bounds=bounds)
+
+
+def blocked_layer(G, x, g, w, root, bias, dtype, absval: bool = False, blk: int = 1 << 22):
+    """(out, d_x, d_weight, d_root, d_bias) of the max layer on the device of x in ``dtype``, sharing nothing with the plans:
+    per relation ``h = zeros.scatter_reduce(0, dst, x[src], "amax", include_self=False)``, ``o_r = h @ W_r`` added to the output
+    and ``torch.autograd.grad(o_r, [x, W_r], g)`` to the gradients -- torch's own tie rule; root and bias in row blocks.  With
+    ``absval`` the condition sums of oracle/tolerance.py bound (1): the same passes with |W|, |root|, |g|, |bias| and |h|, |x| as
+    factors, the maxima and the tie masks still from x itself (the rule of ``conditions``).  G: exact_segment_graph / make_graph."""
+    f = (lambda t: t.abs()) if absval else (lambda t: t)
+    n, din = x.shape
+    dout = w.shape[2]
+    xd = x.detach().to(dtype).requires_grad_(True)      # (detach: never the caller's own tensor)
+    gd = f(g.to(dtype))
+    out = torch.zeros(n, dout, dtype=dtype, device=x.device)
+    dx = torch.zeros(n, din, dtype=dtype, device=x.device)
+    dw = torch.zeros(G["r"], din, dout, dtype=dtype, device=x.device)
+    for rel, (lo, hi) in enumerate(G["bounds"]):
+        if hi == lo:
+            continue
+        src, dst = G["src_s"][lo:hi], G["dst_s"][lo:hi]
+        wr = f(w[rel].to(dtype)).requires_grad_(True)
+        h = xd.new_zeros(n, din).scatter_reduce(0, dst[:, None].expand(-1, din), xd[src], "amax", include_self=False)
+        o = h @ wr
+        gx, gw = torch.autograd.grad(o, [xd, wr], gd)
+        dx += gx
+        with torch.no_grad():
+            if absval:                      # |h| is a factor of out and d_weight; d_x has no factor h (the masks alone)
+                ha = h.abs()
+                out += ha @ wr
+                dw[rel] = ha.t() @ gd
+                del ha
+            else:
+                out += o
+                dw[rel] = gw
+        del h, o, gx, gw
+    xd = xd.detach()
+    rm = f(root.to(dtype))
+    dr = torch.zeros(din, dout, dtype=dtype, device=x.device)
+    db = torch.zeros(dout, dtype=dtype, device=x.device)
+    for lo in range(0, n, blk):
+        xb, gb = f(xd[lo:lo + blk]), gd[lo:lo + blk]
+        out[lo:lo + blk] += xb @ rm
+        dx[lo:lo + blk] += gb @ rm.t()
+        dr += xb.t() @ gb
+        db += gb.sum(0)
+    if bias is not None:
+        out += f(bias.to(dtype))
+    return out, dx, dw, dr, db

@@ -1002,3 +1002,158 @@ def test_featureless_out_of_range_index_reads_zeros(dev, nb):
     ref, cond = _fl_ref(z, dout, x=xr)
     assert_close(out.out(dout, "featureless out-of-range x"), ref["out"].numpy(), cond["out"].numpy(),
                  "abi featureless out, x out of range")
+
+
+# ---- max aggregation: rgcn_segment_max / rgcn_segment_max_bwd on guarded operands ---------------------------------------------
+MAX_WIDTHS = [1, 7, 20, 64, 100, 128]       # lane groups of 4 / 8 / 16 / 32 per row; 1, 7 and 100 are not multiples of 4
+
+
+def _max_inputs(w, seed):
+    """700 rows of width w (even columns integers in -2 .. 2: ties and maxima of 0; odd columns normal), 40 segments of 0 .. 699
+    gathered rows (one empty, one of a single row) with integer tie weights, cut into pieces of at most 256 rows"""
+    gen = torch.Generator().manual_seed(seed)
+    n_out = 40
+    x = torch.randn(N, w, generator=gen)
+    x[:, ::2] = torch.randint(-2, 3, (N, (w + 1) // 2), generator=gen).float()
+    lens = torch.randint(0, 700, (n_out,), generator=gen)
+    lens[3], lens[7] = 0, 1
+    idx = torch.randint(0, N, (int(lens.sum()),), generator=gen)
+    sw = torch.randint(1, 4, (idx.shape[0],), generator=gen).float()
+    starts = np.concatenate([[0], np.cumsum(lens.numpy())])
+    p1, seg_of_piece = [0], []
+    for s in range(n_out):
+        for a in range(starts[s], starts[s + 1], 256):
+            p1.append(min(a + 256, starts[s + 1]))
+            seg_of_piece.append(s)
+    p2 = np.searchsorted(np.array(seg_of_piece), np.arange(n_out + 1), side="left")
+    return x, idx, sw, starts, np.array(p1), p2
+
+
+def _segmax_ref(vals, ties, ptr):
+    """(max, tie weight) per segment of consecutive rows, float64 (every value an fp32 number, every tie weight a small integer)"""
+    n = len(ptr) - 1
+    out, out_t = np.zeros((n, vals.shape[1])), np.zeros((n, vals.shape[1]))
+    for i in range(n):
+        v, t = vals[ptr[i]:ptr[i + 1]], ties[ptr[i]:ptr[i + 1]]
+        if v.shape[0]:
+            out[i] = v.max(0)
+            out_t[i] = np.where(v == out[i], t, 0).sum(0)
+    return out, out_t
+
+
+def _three_lds(w, k):
+    """three row strides of width w, rotated by k, pairwise different"""
+    a, b, c = (_strides(w)[(k + j) % 3] for j in range(3))
+    b = b if b != a else b + 4
+    while c in (a, b):
+        c += 4
+    return a, b, c
+
+
+@pytest.mark.parametrize("k", range(3), ids=["round4", "round4+4", "padded+4"])
+@pytest.mark.parametrize("w", MAX_WIDTHS)
+def test_segment_max_guarded(dev, w, k):
+    """rgcn_segment_max, two levels with seg_idx / seg_w / out_t and one level without any of them: sentinels intact, inputs
+    unchanged, pad columns of out AND out_t +0.0, max and tie weight exact; an empty segment gives (0, 0); n_out = 0 writes
+    nothing"""
+    lib = _lib().load()
+    x, idx, sw, starts, p1, p2 = _max_inputs(w, 100 * w + k)
+    n_pc, n_out = len(p1) - 1, len(p2) - 1
+    ld_in, ld_mid, ld_out = _three_lds(w, k)
+    i32 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.int32, device=dev)
+    ptr1, ptr2, idx1, w1 = i32(p1), i32(p2), i32(idx.numpy()), sw.to(dev)
+    keep = [t.clone() for t in (ptr1, ptr2, idx1, w1)]
+    ins = Guarded(N, ld_in, dev).fill(x)
+    mid, mid_t = Guarded(n_pc, ld_mid, dev, g1=G_OUT), Guarded(n_pc, ld_mid, dev, g1=G_OUT)
+    assert lib.rgcn_segment_max(ins.ptr, None, ld_in, ptr1.data_ptr(), idx1.data_ptr(), w1.data_ptr(), n_pc, w, mid.ptr, mid_t.ptr,
+                                ld_mid, _stream()) == OK
+    torch.cuda.synchronize()
+    ins.unchanged("segment_max in")
+    vals, ties = x.double().numpy()[idx.numpy()], np.repeat(sw.double().numpy()[:, None], w, 1)
+    r1, t1 = _segmax_ref(vals, ties, p1)
+    assert np.array_equal(mid.out(w, "segment_max level 1 out"), r1)
+    assert np.array_equal(mid_t.out(w, "segment_max level 1 out_t"), t1)
+    mid.snap, mid_t.snap = mid.buf.clone(), mid_t.buf.clone()
+    out, out_t = Guarded(n_out, ld_out, dev, g1=G_OUT), Guarded(n_out, ld_out, dev, g1=G_OUT)
+    assert lib.rgcn_segment_max(mid.ptr, mid_t.ptr, ld_mid, ptr2.data_ptr(), None, None, n_out, w, out.ptr, out_t.ptr, ld_out,
+                                _stream()) == OK
+    torch.cuda.synchronize()
+    mid.unchanged("segment_max level-2 in")
+    mid_t.unchanged("segment_max level-2 in_t")
+    r2, t2 = _segmax_ref(vals, ties, starts)
+    assert (starts[4] == starts[3]) and not r2[3].any() and not t2[3].any()                  # the empty segment
+    got, got_t = out.out(w, "segment_max level 2 out"), out_t.out(w, "segment_max level 2 out_t")
+    assert np.array_equal(got, r2) and np.array_equal(got_t, t2)
+    assert np.array_equal(r2, _segmax_ref(r1, t1, p2)[0]) and np.array_equal(t2, _segmax_ref(r1, t1, p2)[1])      # any cut
+    # one level over consecutive rows of the input itself: no seg_idx, no seg_w, and no out_t (nothing but out is written)
+    rows_ptr = np.minimum(starts, N)
+    ptr3 = i32(rows_ptr)
+    out1 = Guarded(n_out, ld_out, dev, g1=G_OUT)
+    assert lib.rgcn_segment_max(ins.ptr, None, ld_in, ptr3.data_ptr(), None, None, n_out, w, out1.ptr, None, ld_out, _stream()) == OK
+    torch.cuda.synchronize()
+    assert np.array_equal(out1.out(w, "segment_max one level out"), _segmax_ref(x.double().numpy(), np.ones((N, w)), rows_ptr)[0])
+    # ... with seg_idx alone and out_t: every weight 1
+    out2, out2_t = Guarded(n_out, ld_mid, dev, g1=G_OUT), Guarded(n_out, ld_mid, dev, g1=G_OUT)
+    ptr4 = i32(starts)
+    assert lib.rgcn_segment_max(ins.ptr, None, ld_in, ptr4.data_ptr(), idx1.data_ptr(), None, n_out, w, out2.ptr, out2_t.ptr, ld_mid,
+                                _stream()) == OK
+    torch.cuda.synchronize()
+    r4, t4 = _segmax_ref(vals, np.ones_like(vals), starts)
+    assert np.array_equal(out2.out(w, "segment_max one level (seg_idx) out"), r4)
+    assert np.array_equal(out2_t.out(w, "segment_max one level (seg_idx) out_t"), t4)
+    # n_out = 0: accepted, nothing written
+    none, none_t = Guarded(4, ld_out, dev), Guarded(4, ld_out, dev)
+    assert lib.rgcn_segment_max(ins.ptr, None, ld_in, ptr1.data_ptr(), None, None, 0, w, none.ptr, none_t.ptr, ld_out, _stream()) == OK
+    torch.cuda.synchronize()
+    none.out(w, "segment_max n_out = 0", rows=0)
+    none_t.out(w, "segment_max n_out = 0 (out_t)", rows=0)
+    ins.unchanged("segment_max in")
+    assert all(torch.equal(a, b) for a, b in zip(keep, (ptr1, ptr2, idx1, w1)))
+
+
+@pytest.mark.parametrize("k", range(3), ids=["round4", "round4+4", "padded+4"])
+@pytest.mark.parametrize("w", MAX_WIDTHS)
+def test_segment_max_bwd_guarded(dev, w, k):
+    """rgcn_segment_max_bwd with and without seg_dh and row_w, x / h, t / dh / c each with its own stride: sentinels intact,
+    inputs unchanged, pad columns of c +0.0, and c equal to where(x[src] == h[s], (w dh[d]) / (t[s] + (h[s] == 0)), 0) in fp32
+    by torch on the CPU (both sides one correctly rounded product and quotient); n_rows = 0 writes nothing"""
+    lib = _lib().load()
+    x, idx, sw, starts, _, _ = _max_inputs(w, 100 * w + k + 50)
+    n_seg, n_rows = len(starts) - 1, int(starts[-1])
+    gen = torch.Generator().manual_seed(w + k)
+    seg = torch.repeat_interleave(torch.arange(n_seg), torch.as_tensor(np.diff(starts)))
+    hv, tv = _segmax_ref(x.double().numpy()[idx.numpy()], np.repeat(sw.double().numpy()[:, None], w, 1), starts)
+    hv, tv = torch.from_numpy(hv).float(), torch.from_numpy(tv).float()
+    assert bool((hv == 0).any()) and bool((tv > 1).any())
+    n_dh = 64
+    dhv = torch.randn(n_dh, w, generator=gen)
+    seg_dh = torch.randperm(n_dh, generator=gen)[:n_seg]
+    rw = torch.rand(n_rows, generator=gen) + 0.5
+    ldx, ldh, ldc = _three_lds(w, k)
+    lddh = ldc + 4
+    i32 = lambda a: a.to(dev, torch.int32)
+    src_d, seg_d, sdh_d, rw_d = i32(idx), i32(seg), i32(seg_dh), rw.to(dev)
+    keep = [t.clone() for t in (src_d, seg_d, sdh_d, rw_d)]
+    xg, hg, tg, dg = (Guarded(N, ldx, dev).fill(x), Guarded(n_seg, ldh, dev).fill(hv), Guarded(n_seg, ldh, dev).fill(tv),
+                      Guarded(n_dh, lddh, dev).fill(dhv))
+    for with_dh in (True, False):
+        for with_w in (True, False):
+            c = Guarded(n_rows, ldc, dev, g1=G_OUT)
+            st = lib.rgcn_segment_max_bwd(xg.ptr, ldx, hg.ptr, tg.ptr, ldh, dg.ptr, lddh, src_d.data_ptr(), seg_d.data_ptr(),
+                                          sdh_d.data_ptr() if with_dh else None, rw_d.data_ptr() if with_w else None, n_rows, w,
+                                          c.ptr, ldc, _stream())
+            torch.cuda.synchronize()
+            assert st == OK
+            d = dhv[seg_dh[seg] if with_dh else seg]
+            num = rw[:, None] * d if with_w else d
+            want = torch.where(x[idx] == hv[seg], num / (tv[seg] + (hv[seg] == 0)), torch.zeros_like(num))
+            got = c.out(w, f"segment_max_bwd c [seg_dh {with_dh} row_w {with_w}]")
+            assert np.array_equal(got, want.double().numpy()), int((got != want.double().numpy()).sum())
+            for gd, name in ((xg, "x"), (hg, "h"), (tg, "t"), (dg, "dh")):
+                gd.unchanged("segment_max_bwd " + name)
+    none = Guarded(4, ldc, dev)
+    assert lib.rgcn_segment_max_bwd(xg.ptr, ldx, hg.ptr, tg.ptr, ldh, dg.ptr, lddh, src_d.data_ptr(), seg_d.data_ptr(), None, None, 0, w,
+                                    none.ptr, ldc, _stream()) == OK
+    torch.cuda.synchronize()
+    none.out(w, "segment_max_bwd n_rows = 0", rows=0)
+    assert all(torch.equal(a, b) for a, b in zip(keep, (src_d, seg_d, sdh_d, rw_d)))

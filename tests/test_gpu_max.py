@@ -1,5 +1,5 @@
 """RGCNConv(aggr="max") on the GPU (csrc/rgcn_segmax.hip + the edge-parallel transform and sums, eplan.MaxPlan): the raw C ABI
-(H and T bit-identical to torch), the module's output and all five gradients against the float64 reference of
+(H and T bit-identical to torch, C of rgcn_segment_max_bwd equal to the same fp32 operations by torch), the module's output and all five gradients against the float64 reference of
 tests/max_reference.py at every width class, weight mode and graph case, a two-layer model fused and unfused, hipGraph-replayed
 training, bit-reproducibility, and the device-built plan against the CPU-built one."""
 import copy
@@ -129,6 +129,28 @@ def test_segment_max_abi_bit_identical_to_torch(dev, graphs, piece, feat):
     assert torch.equal(t[:, :din], tref)
     h2, t2 = _lib.max_aggregate(mp, xp.contiguous(), din, with_t=False)
     assert t2 is None and torch.equal(h2, h)
+
+
+@pytest.mark.parametrize("piece", [8, 256])
+@pytest.mark.parametrize("feat", ["normal", "ties"])
+def test_segment_max_bwd_abi_equal_to_torch(dev, graphs, piece, feat):
+    """rgcn_segment_max_bwd on its own: C of every segment row on a random dH against where(x[src] == H[s], (w dH[seg_dh[s]]) /
+    (T[s] + (H[s] == 0)), 0) by torch ops in fp32 -- one correctly rounded product and quotient on either side, so equal as values
+    (check_c of tests/test_gpu_max_past_4gib.py, which runs the same comparison past 2^24 segments); with and without seg_dh and
+    row_w; 18 columns: the pad columns of C are +0.0"""
+    from scaling_rgcn_training_amd import _lib, eplan as E
+    from tests.test_gpu_max_past_4gib import check_c
+    ei, et, eid, etd = graphs["hubs"]
+    din = 18
+    mp = E.build_max_plan(eid, etd, N, R, piece=piece)
+    xp = torch.nn.functional.pad(M.features(feat, N, din).to(dev), (0, 2)).contiguous()
+    h, t = _lib.max_aggregate(mp, xp, din, with_t=True)
+    if feat == "ties":
+        assert int((h[:, :din] == 0).sum()) > 0 and int((t[:, :din] > 1).sum()) > 0        # N = T + 1 and N = T > 1 both occur
+    assert bool((t[:, din:].view(torch.int32) == 0).all()) and bool((h[:, din:].view(torch.int32) == 0).all())
+    for k, (seg_dh, row_w) in enumerate(((True, True), (False, True), (True, False), (False, False))):
+        c = check_c(mp, xp, din, h, t, seed=20 + k, seg_dh=seg_dh, row_w=row_w)
+        assert int((c[:, :din] != 0).sum()) >= mp.n_seg * din
 
 
 @pytest.mark.parametrize("piece", [8, 256])

@@ -252,3 +252,63 @@ def test_segment_max_argument_refusals():
         assert fwd(width=width, ldin=ld) == STRIDE and fwd(width=width, ldo=ld) == STRIDE, (width, ld)
         for k in ("ldx", "ldh", "lddh", "ldc"):
             assert bwd(width=width, **{k: ld}) == STRIDE, (width, ld, k)
+
+
+# ---- the helpers of tests/test_gpu_max_past_4gib.py, pinned where no GPU is needed -------------------------------------------
+@pytest.mark.parametrize("n,r,n_seg", [(5000, 8, 20001), (300, 9, 2400), (64, 3, 2)])
+def test_exact_segment_graph_has_exactly_that_many_segments(n, r, n_seg):
+    """the recipe of the at-scale cases: S exact to the row, the last node as source and destination, the last segment not empty,
+    relation r - 1 dead, duplicate triples, and -- at a piece scaled down with the hubs (70 > 8 * 8 as 70,000 > 256 * 256) --
+    three levels forward and backward"""
+    G = M.exact_segment_graph(n, r, n_seg, extra=1000, device="cpu", seed=n_seg, hub=70, dup=50)
+    ei, et = G["ei"], G["et"]
+    assert ei.shape[1] == n_seg + 1000 + 70 + 70 + 50
+    assert int(torch.unique(ei[1] * r + et).numel()) == n_seg
+    assert int(et.max()) == r - 2 and G["bounds"][r - 1] == (et.numel(), et.numel())
+    assert bool((ei[0] == n - 1).any()) and bool(((ei[1] == n - 1) & (et == r - 2)).any())
+    assert int(torch.unique(torch.stack([ei[0], ei[1], et]), dim=1).shape[1]) < ei.shape[1]          # duplicate triples
+    assert int(torch.bincount(ei[0], minlength=n)[7]) >= 70
+    assert int(torch.unique(ei[1] * r + et, return_counts=True)[1].max()) >= 70
+    # the relation-sorted view holds the same edges
+    perm = torch.argsort(et, stable=True)
+    assert torch.equal(G["src_s"], ei[0][perm]) and torch.equal(G["dst_s"], ei[1][perm])
+    mp = E.build_max_plan(ei, et, n, r, piece=8)
+    assert mp.n_seg == n_seg and mp.n_hrows == ei.shape[1]
+    assert len(mp.ep.heavy.levels) >= 3 and len(mp.bwd_levels) >= 3
+    h = mp.ep.heavy
+    last = int(mp.seg_dh[n_seg - 1])              # segments are sorted by (relation, destination): the last one is (r - 2, n - 1)
+    assert int(h.slot_row[last]) == n - 1 and int(h.unit_rel[last // 64]) == r - 2
+    assert E.build_max_plan(ei, et, n, r).n_seg == n_seg
+
+
+@pytest.mark.parametrize("graph,feat", [("hubs", "ties"), ("hubs", "normal"), ("plain", "negative")])
+def test_blocked_reference_equals_the_reference(graph, feat):
+    """max_reference.blocked_layer (per relation, torch autograd, row blocks: what the at-scale cases compare against) against
+    reference() / conditions() on the same graph: equal to float64 rounding, the condition sums too"""
+    n, r, din, dout = 300, 5, 6, 3
+    ei, et = M.graph_case(graph, n=n, r=r)
+    torch.manual_seed(4)
+    conv = RGCNConv(din, dout, r, aggr="max")
+    with torch.no_grad():
+        conv.bias.uniform_(-1, 1)
+    x = M.features(feat, n, din)
+    g = torch.randn(n, dout, generator=torch.Generator().manual_seed(9))
+    perm = torch.argsort(et, stable=True)
+    bounds, lo = [], 0
+    for c in torch.bincount(et, minlength=r).tolist():
+        bounds.append((lo, lo + c))
+        lo += c
+    G = dict(n=n, r=r, ei=ei, et=et, src_s=ei[0][perm], dst_s=ei[1][perm], bounds=bounds)
+    w, root, bias = conv.weight.detach(), conv.root.detach(), conv.bias.detach()
+    ref, grads = M.reference(conv, x, ei, et, g)
+    c_out, conds = M.conditions(conv, x, ei, et, g)
+    tol = dict(rtol=1e-12, atol=1e-13)
+    for absval, want_out, want in ((False, ref, grads), (True, c_out, conds)):
+        got = M.blocked_layer(G, x, g, w, root, bias, torch.float64, absval, blk=128)      # (three row blocks)
+        assert not x.requires_grad
+        for name, a, b in zip(("out", "x", "weight", "root", "bias"), got, (want_out, want["x"], want["weight"], want["root"], want["bias"])):
+            np.testing.assert_allclose(a.numpy(), b, err_msg=f"{name} abs={absval}", **tol)
+    # the stock fp32 evaluation is the same code in fp32: close to the float64 one, and x keeps no autograd state
+    got32 = M.blocked_layer(G, x, g, w, root, bias, torch.float32)
+    assert not x.requires_grad and got32[0].dtype == torch.float32
+    np.testing.assert_allclose(got32[0].double().numpy(), ref, rtol=1e-4, atol=1e-4)
