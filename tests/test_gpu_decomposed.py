@@ -19,15 +19,36 @@ def dev():
     return torch.device("cuda:0")
 
 
+def unpack_fragments(packed, r, kp, np_):
+    """the fp32 section of a weight pack as [R + 1, KP, NP] (csrc/rgcn_abi.hip: packed[((rel * NT + s) * KT + j) * 256 + lane * 4 + t]
+    = B_rel[k = 16 j + 4 (lane >> 4) + t][col = 16 s + (lane & 15)])"""
+    a = packed[:(r + 1) * kp * np_].view(r + 1, np_ // 16, kp // 16, 4, 16, 4)       # rel, s, j, lane >> 4, lane & 15, t
+    return a.permute(0, 2, 3, 5, 1, 4).reshape(r + 1, kp, np_)
+
+
+def unpack_planes(packed, r):
+    """the bf16 x 3 section of a 64 x 64 pack as three float32 arrays h, m, l [R + 1, 64, 64] (csrc/rgcn_abi.hip: packed3[((((rel * 2
+    + c) * 3 + pl) * 2 + ct) * 2 + s) * 64 + lane], 8 bf16 each: element j = plane pl of B_rel[k = 32 s + 8 (lane >> 4) + j][col =
+    32 c + 16 ct + (lane & 15)])"""
+    a = packed[(r + 1) * 64 * 64:].view(torch.bfloat16).float().view(r + 1, 2, 3, 2, 2, 4, 16, 8)    # rel, c, pl, ct, s, lane >> 4, lane & 15, j
+    assert a.numel() == (r + 1) * 3 * 64 * 64
+    return a.permute(2, 0, 4, 5, 7, 1, 3, 6).reshape(3, r + 1, 64, 64)
+
+
 @pytest.mark.parametrize("mode,din,dout", [("basis", 32, 32), ("basis", 63, 16), ("basis", 64, 64), ("block", 32, 32), ("block", 64, 64),
-                                           ("block", 24, 12)])
+                                           ("block", 24, 12), ("basis", 63, 50), ("block", 60, 50), ("dense", 64, 64), ("dense", 63, 50)])
 @pytest.mark.parametrize("transpose", [False, True])
 def test_decomposed_pack_equals_pack_of_the_composed_weights(dev, mode, din, dout, transpose):
+    """The pack of a basis / block / dense layer, decoded: the fp32 fragments ``v`` against the dense packer's and against the
+    float64 composition, and -- 64 x 64 class -- the bf16 x 3 planes against the pack's own ``v``: h + m + l = v within
+    2^-27 |v| (three round-to-nearest cuts of 8 bits each hold all 24; tests/test_layer_options.py checks the bound on an
+    emulation), so a wrong, missing or misplaced plane fails.  Padding and off-diagonal blocks are exactly 0 everywhere."""
     from scaling_rgcn_training_amd import _lib
     from scaling_rgcn_training_amd.conv import RGCNConv
     torch.manual_seed(3)
-    r = 11
-    conv = RGCNConv(din, dout, r, **({"num_bases": 5} if mode == "basis" else {"num_blocks": 4})).to(dev)
+    r, nbases = 11, 5
+    nblocks = 4 if din % 4 == 0 and dout % 4 == 0 else 10       # (60 -> 50: blocks of 6 x 5)
+    conv = RGCNConv(din, dout, r, **{"basis": {"num_bases": nbases}, "block": {"num_blocks": nblocks}, "dense": {}}[mode]).to(dev)
     dense = conv.effective_weight().detach().contiguous()
     a = _lib.pack_weights(dense, conv.root.detach(), transpose)
     b = _lib.pack_weights_decomposed(conv.weight.detach(), None if conv.comp is None else conv.comp.detach(), conv.root.detach(), r, din, dout, transpose)
@@ -35,9 +56,49 @@ def test_decomposed_pack_equals_pack_of_the_composed_weights(dev, mode, din, dou
     n32 = (r + 1) * _lib.padded_width(din) * _lib.padded_width(dout)
     # fp32 fragments: the packer sums b = 0 .. B - 1 with fused multiply-adds where torch runs a GEMM (block: exact copies)
     np.testing.assert_allclose(b[:n32].cpu().numpy(), a[:n32].cpu().numpy(), rtol=2e-6, atol=2e-7)
-    if b.numel() > n32:      # bf16 x 3 planes of 64 x 64 layers: pieces of values that may differ in the last bit
-        pa, pb = a[n32:].view(torch.bfloat16).float(), b[n32:].view(torch.bfloat16).float()      # (-0.0 == +0.0: torch's block form multiplies by zeros)
-        assert float((pa != pb).float().mean()) < (0.5 if mode == "basis" else 1e-9)
+    # ---- the fragments decoded, against float64
+    kin, nout = (dout, din) if transpose else (din, dout)
+    kp, np_ = _lib.padded_width(kin), _lib.padded_width(nout)
+    v = unpack_fragments(b.cpu(), r, kp, np_).double()
+    w64 = conv.weight.detach().cpu().double()
+    comp64 = None if conv.comp is None else conv.comp.detach().cpu().double()
+    want = torch.cat([O.effective_weight(w64, comp64, r, conv.num_blocks, din, dout), conv.root.detach().cpu().double()[None]])
+    slack = torch.zeros_like(want)
+    if mode == "basis":      # a chain of B fused multiply-adds: B u sum_b |comp[r, b]| |bases[b]|, u = 2^-24
+        slack[:r] = nbases * 2.0 ** -24 * (comp64.abs() @ w64.abs().view(nbases, -1)).view(r, din, dout)
+    if transpose:
+        want, slack = want.transpose(1, 2), slack.transpose(1, 2)
+    err = (v[:, :kin, :nout] - want).abs()
+    assert bool((err <= slack).all()), (mode, float((err - slack).max()))        # (block, dense and the root: slack 0 -- exact)
+    inside = torch.zeros(kp, np_, dtype=torch.bool)
+    inside[:kin, :nout] = True
+    live = inside[None].expand(r + 1, kp, np_).clone()
+    if mode == "block":      # off-diagonal blocks of the relations (the root is dense)
+        bk, bn = kin // nblocks, nout // nblocks
+        diag = torch.zeros(kp, np_, dtype=torch.bool)
+        for q in range(nblocks):
+            diag[q * bk:(q + 1) * bk, q * bn:(q + 1) * bn] = True
+        live[:r] &= diag[None]
+    assert bool((v[~live] == 0).all()), "padding rows / columns and off-diagonal blocks"
+    assert bool((v[live] != 0).float().mean() > 0.99), "the decoding is not vacuous: live elements hold values"
+    if b.numel() == n32:
+        assert (kp, np_) != (64, 64)
+        return
+    # ---- bf16 x 3 planes of 64 x 64 layers
+    assert (kp, np_) == (64, 64) and b.numel() == n32 + (r + 1) * 3 * 64 * 64 // 2
+    planes = unpack_planes(b.cpu(), r).double()
+    total = planes[0] + planes[1] + planes[2]
+    assert bool(((total - v).abs() <= 2.0 ** -27 * v.abs()).all()), float((total - v).abs().max())
+    for q in range(3):
+        assert bool((planes[q][~live] == 0).all()), f"plane {q}: padding rows / columns and off-diagonal blocks"
+    # the planes are a split, not three copies: h is v cut to bf16, the others shrink by 2^-8 each
+    assert bool(((planes[0] - v).abs() <= 2.0 ** -8 * v.abs()).all()) and bool((planes[1].abs() <= 2.0 ** -8 * v.abs()).all())
+    assert bool((planes[2].abs() <= 2.0 ** -16 * v.abs()).all())
+    assert bool((planes[1][live] != 0).float().mean() > 0.9) and bool((planes[2][live] != 0).float().mean() > 0.9)
+    # and the same planes as the dense packer makes of the same fp32 values (-0.0 == +0.0: torch's block form multiplies by zeros)
+    if mode != "basis":
+        pa, pb = a[n32:].view(torch.bfloat16).float(), b[n32:].view(torch.bfloat16).float()
+        assert bool((pa == pb).all())
 
 
 @pytest.mark.parametrize("mode", ["basis", "block"])

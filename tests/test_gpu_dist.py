@@ -40,7 +40,11 @@ def _worker(rank, world, port, ret, dw_direct):
     # "skew-ep": the hub graph with the path choice left to the layer -- every piece's forward on the edge-parallel kernels
     # "needed": the opt-in exchange in which a rank receives only the rows its plans read (all_to_all_single with split sizes);
     # unread rows are poisoned with NaN here and the read ones must be bit-identical to the single-rank layer
-    if dw_direct in ("tiles", "skew", "skew-ep", "needed", "needed-skew"):
+    # "options": the tile path with a basis decomposition, sum aggregation and no bias -- the dense d_W is all-reduced BEFORE
+    # rgcn_basis_backward turns it into d_bases / d_comp (taken from a rank's partial d_W and never reduced, they would be that
+    # rank's share alone); with sum aggregation every slot weight of the layout-3 and pair plans is a small integer
+    options = dw_direct == "options"
+    if dw_direct in ("tiles", "skew", "skew-ep", "needed", "needed-skew", "options"):
         C.DW_TILES_MIN_EDGES = 1
     skew = "skew" in dw_direct
     needed = dw_direct.startswith("needed")
@@ -51,15 +55,20 @@ def _worker(rank, world, port, ret, dw_direct):
     x = torch.randn(n, din, generator=g)
     dg = torch.randn(n, dout, generator=g)
 
+    def make_options_layer():
+        torch.manual_seed(17)       # the layer's own glorot parameters, the same in every run and on every rank
+        return RGCNConv(din, dout, r, num_bases=3, aggr="sum", bias=False)
+
     def run(partitioned):
-        conv = RGCNConv(din, dout, r).to(dev)
+        conv = (make_options_layer() if options else RGCNConv(din, dout, r)).to(dev)
         conv.kernel_flags = flags
         if dw_direct != "skew-ep":
             conv.path = "ring"      # tile kernels in both runs: a rank's tiles are the single-rank tiles, bit for bit
-        with torch.no_grad():
-            conv.weight.copy_(w)
-            conv.root.copy_(root)
-            conv.bias.copy_(bias + 0.25)
+        if not options:
+            with torch.no_grad():
+                conv.weight.copy_(w)
+                conv.root.copy_(root)
+                conv.bias.copy_(bias + 0.25)
         if partitioned:
             rdist.attach(conv, n, e, edge_index=ei, exchange="needed" if needed else "full", edge_type=et)
             assert conv.dist is not None and conv.dist.world == world
@@ -69,7 +78,7 @@ def _worker(rank, world, port, ret, dw_direct):
         out = conv(xd, ei.to(dev), et.to(dev))
         out.backward(dg.to(dev))
         torch.cuda.synchronize()
-        if partitioned and dw_direct in ("tiles", "skew"):
+        if partitioned and dw_direct in ("tiles", "skew", "options"):
             # full exchange: x and g are replicated, so a rank's d_weight is ONE tile-major launch over a contiguous range of its own
             assert conv.dist.stats.get("dw_tiles_rank", 0) == 1 and conv.dist.stats.get("dw_tiles_pieces", 0) == 0
         if partitioned and needed:
@@ -101,6 +110,13 @@ def _worker(rank, world, port, ret, dw_direct):
                 assert conv.dist.stats.get("shared_heavy_rows", 0) >= sh.row_hi - sh.row_lo
                 bc = conv.dist.block_costs.sum(0) + conv.dist.shared_rows_per_rank
                 assert float(bc.max() / bc.mean()) <= 1.3, "rows walked per rank max / mean with the hubs split across the ranks"
+        if options:
+            pl = conv._plans(xd, ei.to(dev), et.to(dev))
+            assert all(pc.fwd.layout == 3 for pc in (pl.pieces if partitioned else [pl])), "the tile path: layout-3 plans"
+            assert (pl.dw_rank[0] if partitioned else pl.dw) is not None, "d_weight on the tile-major kernel's own plan"
+            assert conv.comp.grad is not None and conv.bias is None
+            return (out.detach().cpu().numpy(), xd.grad.cpu().numpy(), conv.weight.grad.cpu().numpy(), conv.comp.grad.cpu().numpy(),
+                    conv.root.grad.cpu().numpy())
         return (out.detach().cpu().numpy(), xd.grad.cpu().numpy(), conv.weight.grad.cpu().numpy(),
                 conv.root.grad.cpu().numpy(), conv.bias.grad.cpu().numpy())
 
@@ -117,6 +133,20 @@ def _worker(rank, world, port, ret, dw_direct):
         else:
             assert np.array_equal(single[0], part[0]), "partitioned forward must be bit-identical (tile-aligned ranges)"
             assert np.array_equal(single[1], part[1]), "partitioned dX must be bit-identical"
+        if options:
+            # the gradients of the layer's own parameters (bases, comp, root) of both runs against float64, both bounds of
+            # oracle/tolerance.py (tests/layer_options.py); the output and d_x of the single-rank run too
+            from tests import layer_options as L
+            ref = L.Reference(make_options_layer(), x, ei, et, dg)
+            ref.check("out", single[0], "options single")
+            ref.check("x", single[1], "options single")
+            for tag, res in (("options single", single), ("options 2 ranks", part)):
+                ref.check("weight", res[2], tag)
+                ref.check("comp", res[3], tag)
+                ref.check("root", res[4], tag)
+            ret.put("ok")
+            dist.destroy_process_group()
+            return
         # weight grads: per-rank partial sums all-reduced -> summation order differs; both must meet the
         # parity criterion against the float64 oracle
         from oracle.tolerance import abs_condition, assert_close
@@ -131,7 +161,7 @@ def _worker(rank, world, port, ret, dw_direct):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("dw_direct", ["0", "2", "tiles", "skew", "skew-ep", "needed", "needed-skew"])
+@pytest.mark.parametrize("dw_direct", ["0", "2", "tiles", "skew", "skew-ep", "needed", "needed-skew", "options"])
 def test_two_ranks_one_gpu_partitioned_layer_equals_single_rank(dw_direct):
     ctx = mp.get_context("spawn")
     ret = ctx.Queue()
