@@ -16,17 +16,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RGCN_LIB") or os.path.join(_HERE, "librgcn_mi355x.so")
 ABI_VERSION = 19
 
-EXPORTS = (
-    "rgcn_abi_version", "rgcn_status_string", "rgcn_padded_width", "rgcn_packed_weight_floats",
-    "rgcn_pack_weights", "rgcn_fwd", "rgcn_bwd_dx", "rgcn_act_backward", "rgcn_bwd_dw_workspace_bytes", "rgcn_bwd_dw",
-    "rgcn_plan_workspace_bytes", "rgcn_edge_weights", "rgcn_plan_build_begin", "rgcn_plan_build_finish",
-    "rgcn_dw_tiles_geometry", "rgcn_dw_tiles_walk", "rgcn_bwd_dw_tiles_workspace_bytes", "rgcn_bwd_dw_tiles",
-    "rgcn_bwd_dw_root_workspace_bytes", "rgcn_bwd_dw_root", "rgcn_ep_transform", "rgcn_ep_segment_sum",
-    "rgcn_pack_weights_basis", "rgcn_pack_weights_block", "rgcn_basis_backward", "rgcn_block_backward", "rgcn_eplan_segments",
-    "rgcn_featureless_geometry", "rgcn_featureless_fwd", "rgcn_featureless_bwd_workspace_bytes", "rgcn_featureless_bwd",
-    "rgcn_xwide_geometry", "rgcn_xwide_fwd", "rgcn_xwide_bwd_dx", "rgcn_xwide_bwd_dw_workspace_bytes", "rgcn_xwide_bwd_dw",
-    "rgcn_segment_max", "rgcn_segment_max_bwd",
-)
 XWIDE_MAX_WIDTH = 512  # RGCN_XWIDE_MAX_WIDTH
 
 # enum rgcn_act / RGCN_FLAG_* of include/rgcn_mi355x.h
@@ -67,6 +56,57 @@ class RgcnPlanSizes(C.Structure):
                 ("n_slots", C.c_int64), ("n_edges", C.c_int64), ("opaque", C.c_uint64 * 16)]
 
 
+def _prototypes() -> dict:
+    """name -> (restype, [argtypes]) of every entry point of include/rgcn_mi355x.h, as load() installs them"""
+    vp, i32, u32, i64, sz, lng = C.c_void_p, C.c_int, C.c_uint, C.c_int64, C.c_size_t, C.c_long
+    plan, units, graph, sizes, pint = (C.POINTER(RgcnPlanStruct), C.POINTER(RgcnEdgeUnits), C.POINTER(RgcnGraphStruct),
+                                       C.POINTER(RgcnPlanSizes), C.POINTER(C.c_int))
+    return {
+        "rgcn_abi_version": (i32, []),
+        "rgcn_status_string": (C.c_char_p, [i32]),
+        "rgcn_padded_width": (i32, [i32]),
+        "rgcn_packed_weight_floats": (sz, [i32, i32, i32]),
+        "rgcn_pack_weights": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+        "rgcn_fwd": (i32, [plan, vp, i32, i32, vp, vp, vp, i32, i32, i32, u32, vp]),
+        "rgcn_bwd_dx": (i32, [plan, vp, i32, i32, vp, vp, i32, i32, vp, i32, u32, vp]),
+        "rgcn_act_backward": (i32, [vp, vp, vp, lng, i32, i32, vp]),
+        "rgcn_bwd_dw_workspace_bytes": (sz, [plan, i32, i32]),
+        "rgcn_bwd_dw": (i32, [plan, vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, u32, vp]),
+        "rgcn_plan_workspace_bytes": (sz, [i64, i32, i32, i32]),
+        "rgcn_edge_weights": (i32, [graph, i32, vp, vp, sz, vp]),
+        "rgcn_plan_build_begin": (i32, [graph, vp, i32, i32, i32, i32, i32, i32, vp, sz, sizes, vp]),
+        "rgcn_plan_build_finish": (i32, [sizes, vp, sz, plan, vp]),
+        "rgcn_dw_tiles_geometry": (i32, [pint, pint, pint]),
+        "rgcn_dw_tiles_walk": (i32, [plan, vp, vp]),
+        "rgcn_bwd_dw_tiles_workspace_bytes": (sz, [i32]),
+        "rgcn_bwd_dw_tiles": (i32, [plan, vp, vp, i32, i32, vp, i32, i32, vp, sz, vp, u32, vp]),
+        "rgcn_bwd_dw_root_workspace_bytes": (sz, []),
+        "rgcn_bwd_dw_root": (i32, [vp, i32, i32, vp, i32, i32, lng, vp, sz, vp, vp, vp]),
+        "rgcn_pack_weights_basis": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "rgcn_pack_weights_block": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+        "rgcn_basis_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "rgcn_block_backward": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+        "rgcn_eplan_segments": (i32, [vp, i64, i32, vp, sz, vp, vp, vp]),
+        "rgcn_ep_transform": (i32, [units, vp, i32, i32, vp, vp, i32, i32, u32, vp]),
+        "rgcn_ep_segment_sum": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]),
+        "rgcn_featureless_geometry": (i32, [i32, i32, i32, pint, pint]),
+        "rgcn_featureless_fwd": (i32, [plan, vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
+        "rgcn_featureless_bwd_workspace_bytes": (sz, [plan, i32, i32, i32]),
+        "rgcn_featureless_bwd": (i32, [plan, vp, vp, vp, i64, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp]),
+        "rgcn_xwide_geometry": (i32, [i32, i32, i32, pint, pint]),
+        "rgcn_xwide_fwd": (i32, [plan, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
+        "rgcn_xwide_bwd_dx": (i32, [plan, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
+        "rgcn_xwide_bwd_dw_workspace_bytes": (sz, [plan, i32, i32]),
+        "rgcn_xwide_bwd_dw": (i32, [plan, vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, vp]),
+        "rgcn_segment_max": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp]),
+        "rgcn_segment_max_bwd": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
+    }
+
+
+_PROTOTYPES = _prototypes()
+EXPORTS = tuple(_PROTOTYPES)      # (tests/test_abi.py compares it with the header's declarations)
+
+
 class RgcnLibraryError(RuntimeError):
     pass
 
@@ -84,87 +124,9 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the R-GCN layer.")
     lib = C.CDLL(LIB_PATH)
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    lib.rgcn_abi_version.restype = i32
-    lib.rgcn_abi_version.argtypes = []
-    lib.rgcn_status_string.restype = C.c_char_p
-    lib.rgcn_status_string.argtypes = [i32]
-    lib.rgcn_padded_width.restype = i32
-    lib.rgcn_padded_width.argtypes = [i32]
-    lib.rgcn_packed_weight_floats.restype = sz
-    lib.rgcn_packed_weight_floats.argtypes = [i32, i32, i32]
-    lib.rgcn_pack_weights.restype = i32
-    lib.rgcn_pack_weights.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.rgcn_fwd.restype = i32
-    u32 = C.c_uint
-    lib.rgcn_fwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, vp, vp, i32, i32, i32, u32, vp]
-    lib.rgcn_bwd_dx.restype = i32
-    lib.rgcn_bwd_dx.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, vp, i32, i32, vp, i32, u32, vp]
-    lib.rgcn_act_backward.restype = i32
-    lib.rgcn_act_backward.argtypes = [vp, vp, vp, C.c_long, i32, i32, vp]
-    lib.rgcn_bwd_dw_workspace_bytes.restype = sz
-    lib.rgcn_bwd_dw_workspace_bytes.argtypes = [C.POINTER(RgcnPlanStruct), i32, i32]
-    lib.rgcn_bwd_dw.restype = i32
-    lib.rgcn_bwd_dw.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, u32, vp]
-    i64 = C.c_int64
-    lib.rgcn_plan_workspace_bytes.restype = sz
-    lib.rgcn_plan_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    lib.rgcn_edge_weights.restype = i32
-    lib.rgcn_edge_weights.argtypes = [C.POINTER(RgcnGraphStruct), i32, vp, vp, sz, vp]
-    lib.rgcn_plan_build_begin.restype = i32
-    lib.rgcn_plan_build_begin.argtypes = [C.POINTER(RgcnGraphStruct), vp, i32, i32, i32, i32, i32, i32, vp, sz,
-                                          C.POINTER(RgcnPlanSizes), vp]
-    lib.rgcn_plan_build_finish.restype = i32
-    lib.rgcn_plan_build_finish.argtypes = [C.POINTER(RgcnPlanSizes), vp, sz, C.POINTER(RgcnPlanStruct), vp]
-    lib.rgcn_dw_tiles_geometry.restype = i32
-    lib.rgcn_dw_tiles_geometry.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.rgcn_dw_tiles_walk.restype = i32
-    lib.rgcn_dw_tiles_walk.argtypes = [C.POINTER(RgcnPlanStruct), vp, vp]
-    lib.rgcn_bwd_dw_tiles_workspace_bytes.restype = sz
-    lib.rgcn_bwd_dw_tiles_workspace_bytes.argtypes = [i32]
-    lib.rgcn_bwd_dw_tiles.restype = i32
-    lib.rgcn_bwd_dw_tiles.argtypes = [C.POINTER(RgcnPlanStruct), vp, vp, i32, i32, vp, i32, i32, vp, sz, vp, u32, vp]
-    lib.rgcn_bwd_dw_root_workspace_bytes.restype = sz
-    lib.rgcn_bwd_dw_root_workspace_bytes.argtypes = []
-    lib.rgcn_bwd_dw_root.restype = i32
-    lib.rgcn_bwd_dw_root.argtypes = [vp, i32, i32, vp, i32, i32, C.c_long, vp, sz, vp, vp, vp]
-    lib.rgcn_pack_weights_basis.restype = i32
-    lib.rgcn_pack_weights_basis.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.rgcn_pack_weights_block.restype = i32
-    lib.rgcn_pack_weights_block.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.rgcn_basis_backward.restype = i32
-    lib.rgcn_basis_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.rgcn_block_backward.restype = i32
-    lib.rgcn_block_backward.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.rgcn_eplan_segments.restype = i32
-    lib.rgcn_eplan_segments.argtypes = [vp, i64, i32, vp, sz, vp, vp, vp]
-    lib.rgcn_ep_transform.restype = i32
-    lib.rgcn_ep_transform.argtypes = [C.POINTER(RgcnEdgeUnits), vp, i32, i32, vp, vp, i32, i32, u32, vp]
-    lib.rgcn_ep_segment_sum.restype = i32
-    lib.rgcn_ep_segment_sum.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]
-    lib.rgcn_featureless_geometry.restype = i32
-    lib.rgcn_featureless_geometry.argtypes = [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.rgcn_featureless_fwd.restype = i32
-    lib.rgcn_featureless_fwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]
-    lib.rgcn_featureless_bwd_workspace_bytes.restype = sz
-    lib.rgcn_featureless_bwd_workspace_bytes.argtypes = [C.POINTER(RgcnPlanStruct), i32, i32, i32]
-    lib.rgcn_featureless_bwd.restype = i32
-    lib.rgcn_featureless_bwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, vp, vp, i64, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
-                                         vp, vp, vp]
-    lib.rgcn_xwide_geometry.restype = i32
-    lib.rgcn_xwide_geometry.argtypes = [i32, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.rgcn_xwide_fwd.restype = i32
-    lib.rgcn_xwide_fwd.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, vp, vp, i32, i32, i32, vp]
-    lib.rgcn_xwide_bwd_dx.restype = i32
-    lib.rgcn_xwide_bwd_dx.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, vp, i32, i32, vp, i32, vp]
-    lib.rgcn_xwide_bwd_dw_workspace_bytes.restype = sz
-    lib.rgcn_xwide_bwd_dw_workspace_bytes.argtypes = [C.POINTER(RgcnPlanStruct), i32, i32]
-    lib.rgcn_xwide_bwd_dw.restype = i32
-    lib.rgcn_xwide_bwd_dw.argtypes = [C.POINTER(RgcnPlanStruct), vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, vp]
-    lib.rgcn_segment_max.restype = i32
-    lib.rgcn_segment_max.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp]
-    lib.rgcn_segment_max_bwd.restype = i32
-    lib.rgcn_segment_max_bwd.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, vp, i32, vp]
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.rgcn_abi_version() != ABI_VERSION:
         raise RgcnLibraryError(f"ABI version mismatch: library {lib.rgcn_abi_version()} != binding {ABI_VERSION}")
     _lib = lib
@@ -414,19 +376,23 @@ def bwd_dw_root(x: torch.Tensor, din: int, g: torch.Tensor, dout: int, d_root: O
 
 
 # ---- edge-parallel path (eplan.EdgePlan) ----------------------------------------------------------------------------
-def edge_units_struct(ep) -> RgcnEdgeUnits:
-    cached = getattr(ep, "_cunits", None)
+def _units_struct(owner, attr: str, units, n_gathered: int, slot_src: torch.Tensor, num_relations: int) -> RgcnEdgeUnits:
+    """The struct rgcn_edge_units of ``units`` (an eplan.EdgePlan or HeavyPart: unit_rel, unit_cnt, slot_w) gathering the rows
+    ``slot_src`` of a matrix of ``n_gathered`` rows, built once and kept on ``owner`` under ``attr`` (the plan's tensors never
+    change)."""
+    cached = getattr(owner, attr, None)
     if cached is None:
-        if ep.slot_src.device.type != "cuda":
-            raise RgcnLibraryError("the edge plan must live on the GPU (plan tensors are on %s)" % ep.slot_src.device)
-        cached = ep._cunits = RgcnEdgeUnits(ep.n_nodes, ep.n_units, ep.num_relations, 0, ep.unit_rel.data_ptr(),
-                                            ep.unit_cnt.data_ptr(), ep.slot_src.data_ptr(), ep.slot_w.data_ptr())
+        if slot_src.device.type != "cuda":
+            raise RgcnLibraryError("the edge plan must live on the GPU (plan tensors are on %s)" % slot_src.device)
+        cached = RgcnEdgeUnits(n_gathered, units.n_units, num_relations, 0, units.unit_rel.data_ptr(), units.unit_cnt.data_ptr(),
+                               slot_src.data_ptr(), units.slot_w.data_ptr())
+        setattr(owner, attr, cached)
     return cached
 
 
-def _edge_units(n_rows_gathered: int, n_units: int, num_relations: int, unit_rel, unit_cnt, slot_src, slot_w) -> RgcnEdgeUnits:
-    return RgcnEdgeUnits(n_rows_gathered, n_units, num_relations, 0, unit_rel.data_ptr(), unit_cnt.data_ptr(), slot_src.data_ptr(),
-                         slot_w.data_ptr())
+def edge_units_struct(ep) -> RgcnEdgeUnits:
+    """the light units of an eplan.EdgePlan: they gather rows of the layer's input"""
+    return _units_struct(ep, "_cunits", ep, ep.n_nodes, ep.slot_src, ep.num_relations)
 
 
 def ep_segment_sum(src: torch.Tensor, ptr: torch.Tensor, idx, w, n_out: int, width: int, out: torch.Tensor, bias=None,
@@ -437,6 +403,25 @@ def ep_segment_sum(src: torch.Tensor, ptr: torch.Tensor, idx, w, n_out: int, wid
                                          out.data_ptr(), out.stride(0), _stream(src)), "rgcn_ep_segment_sum")
 
 
+def _sum_levels(levels, src: torch.Tensor, width: int, ld: int, out: Optional[torch.Tensor] = None, bias=None, act: int = ACT_NONE,
+                mask=None, final: bool = False) -> torch.Tensor:
+    """``src`` through one rgcn_ep_segment_sum per entry of ``levels`` -- (seg_ptr, seg_idx, seg_w, n_out), or (seg_ptr, seg_idx,
+    n_out) unweighted -- each level reading the one before it.  Intermediate levels go to fresh [max(n_out, 1), ld] buffers; the
+    last level goes to ``out`` where the caller gives one, and it alone takes bias, activation, mask and the ``final`` flag.
+    Returns what the last level wrote (``src`` itself without a level)."""
+    cur = src
+    for li, lv in enumerate(levels):
+        ptr, idx, w, n_out = lv if len(lv) == 4 else (lv[0], lv[1], None, lv[2])
+        last = li == len(levels) - 1
+        dst = out if last and out is not None else torch.empty(max(n_out, 1), ld, dtype=torch.float32, device=src.device)
+        if last:
+            ep_segment_sum(cur, ptr, idx, w, n_out, width, dst, bias, act, mask, final)
+        else:
+            ep_segment_sum(cur, ptr, idx, w, n_out, width, dst)
+        cur = dst
+    return cur
+
+
 def ep_aggregate_heavy(ep, x: torch.Tensor, din: int) -> Optional[torch.Tensor]:
     """H[seg] = sum_e w_e x[src_e] over the rows of every heavy (destination, relation) segment of the plan (eplan.HeavyPart):
     rgcn_ep_segment_sum over x itself, weighted, in levels.  None when the plan has no heavy part."""
@@ -445,24 +430,15 @@ def ep_aggregate_heavy(ep, x: torch.Tensor, din: int) -> Optional[torch.Tensor]:
         return None
     if h.shared is not None:
         raise RgcnLibraryError("this plan's heavy segments are shared across ranks: H comes from ep_aggregate_shared + all-reduce")
-    cur = x
-    for ptr, idx, w, n_out in h.levels:
-        dst = torch.empty(max(n_out, 1), x.stride(0), dtype=torch.float32, device=x.device)
-        ep_segment_sum(cur, ptr, idx, w, n_out, din, dst)
-        cur = dst
-    return cur
+    return _sum_levels(h.levels, x, din, x.stride(0))
 
 
 def ep_aggregate_shared(shared, x: torch.Tensor, din: int) -> torch.Tensor:
     """this rank's share of H[seg] = sum_e w_e x[src_e] over the heavy segments of the whole graph (eplan.SharedHeavy): zeros but
     for the segments its rows belong to; the all-reduce over the ranks (conv.py) completes it"""
     hmat = torch.zeros(max(shared.n_seg, 1), x.stride(0), dtype=torch.float32, device=x.device)
-    cur = x
-    for li, (ptr, idx, w, n_out) in enumerate(shared.levels):
-        last = li == len(shared.levels) - 1
-        dst = hmat[shared.seg_lo:shared.seg_lo + n_out] if last else torch.empty(max(n_out, 1), x.stride(0), dtype=torch.float32, device=x.device)
-        ep_segment_sum(cur, ptr, idx, w, n_out, din, dst)
-        cur = dst
+    if shared.levels:      # (the last level's n_out segments start at seg_lo)
+        _sum_levels(shared.levels, x, din, x.stride(0), out=hmat[shared.seg_lo:shared.seg_lo + shared.levels[-1][3]])
     return hmat
 
 
@@ -484,18 +460,10 @@ def ep_layer(ep, x: torch.Tensor, din: int, packed: torch.Tensor, bias: Optional
         check(lib.rgcn_ep_transform(C.byref(edge_units_struct(ep)), x.data_ptr(), x.stride(0), din, packed.data_ptr(),
                                     z.data_ptr(), ldz, dout, int(flags), st), "rgcn_ep_transform")
         if h is not None:
-            hu = getattr(h, "_cunits", None)
-            if hu is None:
-                hu = h._cunits = _edge_units(h.n_seg, h.n_units, ep.num_relations, h.unit_rel, h.unit_cnt, h.slot_src, h.slot_w)
+            hu = _units_struct(h, "_cunits", h, h.n_seg, h.slot_src, ep.num_relations)      # (the pseudo rows gather rows of H)
             check(lib.rgcn_ep_transform(C.byref(hu), hmat.data_ptr(), hmat.stride(0), din, packed.data_ptr(),
                                         z[n_light:].data_ptr(), ldz, dout, int(flags), st), "rgcn_ep_transform (heavy part)")
-    cur = z
-    for li, (ptr, idx, n_out) in enumerate(ep.levels):
-        final = li == len(ep.levels) - 1
-        dst = out if final else torch.empty(max(n_out, 1), ldz, dtype=torch.float32, device=x.device)
-        ep_segment_sum(cur, ptr, idx, None, n_out, dout, dst, bias if final else None, act if final else ACT_NONE,
-                       mask if final else None, final)
-        cur = dst
+    _sum_levels(ep.levels, z, dout, ldz, out, bias, act, mask, final=True)
     return hmat
 
 
@@ -559,10 +527,7 @@ def max_layer_dx(mp, x: torch.Tensor, hmat: Optional[torch.Tensor], tmat: Option
     y = torch.empty(max(mp.n_hrows + ep.n_units * 64, 1), ldx, dtype=torch.float32, device=g.device)
     with torch.cuda.device(g.device):
         if h is not None:
-            units = getattr(mp, "_bwd_cunits", None)
-            if units is None:
-                units = mp._bwd_cunits = _edge_units(ep.n_nodes, h.n_units, ep.num_relations, h.unit_rel, h.unit_cnt, mp.bwd_slot_src,
-                                                     h.slot_w)
+            units = _units_struct(mp, "_bwd_cunits", h, ep.n_nodes, mp.bwd_slot_src, ep.num_relations)      # (they gather g[destination])
             dh = torch.empty(max(h.n_units * 64, 1), ldx, dtype=torch.float32, device=g.device)
             check(lib.rgcn_ep_transform(C.byref(units), g.data_ptr(), g.stride(0), dout, packed_t.data_ptr(), dh.data_ptr(), ldx, din,
                                         int(flags), st), "rgcn_ep_transform (max dH)")
@@ -571,12 +536,7 @@ def max_layer_dx(mp, x: torch.Tensor, hmat: Optional[torch.Tensor], tmat: Option
                                            mp.n_hrows, din, y.data_ptr(), ldx, st), "rgcn_segment_max_bwd")
         check(lib.rgcn_ep_transform(C.byref(edge_units_struct(ep)), g.data_ptr(), g.stride(0), dout, packed_t.data_ptr(),
                                     y[mp.n_hrows:].data_ptr(), ldx, din, int(flags), st), "rgcn_ep_transform (max root rows)")
-    cur = y
-    for li, (ptr, idx, n_out) in enumerate(mp.bwd_levels):
-        final = li == len(mp.bwd_levels) - 1
-        dst = dx if final else torch.empty(max(n_out, 1), ldx, dtype=torch.float32, device=g.device)
-        ep_segment_sum(cur, ptr, idx, None, n_out, din, dst, None, ACT_NONE, mask if final else None, final)
-        cur = dst
+    _sum_levels(mp.bwd_levels, y, din, ldx, dx, mask=mask, final=True)
 
 
 # ---- featureless layers (csrc/rgcn_featureless.hip) -----------------------------------------------------------------

@@ -287,6 +287,38 @@ def _operands(*params):
     return [None if p is None else p.detach().float().contiguous() for p in params]
 
 
+def _padded_rows(n: int, width: int, device) -> Tensor:
+    """an uninitialised float32 [n, width rounded up to 4] row buffer: what a kernel stores an output into (C ABI rule)"""
+    return torch.empty(n, _round4(width), dtype=torch.float32, device=device)
+
+
+def _trim(rows: Tensor, width: int) -> Tensor:
+    """a padded row buffer without its padding columns"""
+    return rows if rows.shape[1] == width else rows[:, :width]
+
+
+def _keep_activated(ctx, act: int, grad_premasked: bool, out: Tensor) -> Optional[Tensor]:
+    """Records on ``ctx`` whether the backward needs the activated output and returns what to save for it.  The activated output
+    is only needed to differentiate the activation; a ReLU whose consumer folds the mask into its dX store (grad_premasked)
+    needs nothing."""
+    ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
+    return out if ctx.need_a else None
+
+
+def _grad_z(ctx, g: Tensor, dout: int, a_out: Optional[Tensor]) -> Tensor:
+    """dL/dz = dL/da * act'(a) in padded rows, from the gradient ``g`` of the activated output (_keep_activated)"""
+    gp = _rows16(g, dout)
+    return _lib.act_backward(a_out, gp, ctx.act) if ctx.need_a else gp
+
+
+def _own_param_grads(dw: Optional[Tensor], wf: Tensor, cp: Optional[Tensor], need_weight: bool, need_comp: bool, xwide: bool = False):
+    """(d_weight, d_comp) of the layer's own parameters from the dense d_W [R, in, out] the weight-gradient kernels wrote: d_W
+    itself for a dense layer, else the decomposition's gradients (rgcn_basis_backward / rgcn_block_backward; ``xwide``: torch ops)"""
+    if dw is None or (cp is None and wf.dim() != 4):
+        return dw, None
+    return (_xwide_decomposed_grads if xwide else _lib.decomposed_weight_grads)(dw, wf, cp, need_weight, need_comp)
+
+
 def _launch_fwd(pl, xp: Tensor, din: int, packed: Tensor, bs: Optional[Tensor], rows: Tensor, dout: int, act: int, flags: int,
                 hmat: Optional[Tensor] = None) -> Optional[Tensor]:
     """forward of one plan into ``rows``: rgcn_fwd, or the edge-parallel path for an eplan.EdgePlan (returns its H)"""
@@ -301,6 +333,24 @@ def _launch_dx(pl, gp: Tensor, dout: int, packed_t: Tensor, rows: Tensor, din: i
     if not isinstance(pl, TilePlan):
         return _lib.ep_layer(pl, gp, dout, packed_t, None, rows, din, _lib.ACT_NONE, mask, flags, hmat=hmat)
     _lib.bwd_dx(_lib.plan_struct(pl), gp, dout, packed_t, rows, din, mask, flags)
+
+
+def _flat_grads(need_w: bool, need_root: bool, need_bias: bool, num_rel: int, din: int, dout: int, device):
+    """ONE flat buffer for the three weight gradients (a single all-reduce in the distributed case): (new, views) -- ``new()``
+    allocates one, ``views(flat)`` are its (d_weight, d_root, d_bias) parts, None for a gradient nobody needs"""
+    o0 = num_rel * din * dout if need_w else 0
+    o1 = o0 + (din * dout if need_root else 0)
+    numel = o1 + (dout if need_bias else 0)
+
+    def new(zeros: bool = False) -> Tensor:
+        return (torch.zeros if zeros else torch.empty)(numel, dtype=torch.float32, device=device)
+
+    def views(flat: Tensor):
+        return (flat[:o0].view(num_rel, din, dout) if need_w else None,
+                flat[o0:o1].view(din, dout) if need_root else None,
+                flat[o1:].view(dout) if need_bias else None)
+
+    return new, views
 
 
 def _dw_tiles(dwp: TilePlan, walk: Tensor, xp: Tensor, din: int, gp: Tensor, dout: int, parts, flags: int) -> None:
@@ -330,6 +380,73 @@ def _dw_walk(pc: GraphPlans, xp: Tensor, din: int, gp: Tensor, dout: int, parts,
         pw.add_(pw2)
 
 
+def _dw_on_tiles(pc: GraphPlans, tiles_ok: bool, need_w: bool, gp: Tensor) -> bool:
+    """Which kernel takes the weight gradients of a piece (one GPU: the graph).  One with a tile-major d_weight plan takes that
+    plan (layout-3 forward plans always: the relation-major kernels refuse them) unless the flags pin other kernels
+    (``tiles_ok``: _RGCNLayerFn.backward); the tile-major kernel gathers x and g through buffer descriptors only."""
+    return (tiles_ok and pc.dw is not None and (need_w or pc.fwd.layout == 3)
+            and _lib.buffer_addressable(pc.fwd.n_owned, gp.shape[1]))
+
+
+def _dw_one_gpu_root(plans: GraphPlans, parts, overlap: bool, xp: Tensor, din: int, gp: Tensor, dout: int, flags: int):
+    """One GPU on the tile-major plan, the part enqueued BEFORE the dX launch: d_root / d_bias by the streaming kernel, on a side
+    stream where ``overlap`` (a dX launch follows on a graph of at least _SIDE_STREAM_MIN_ROWS nodes).  Returns that stream, or
+    None; _dw_one_gpu_tiles joins it."""
+    _, pr, pb = parts
+    side = None
+    if overlap and (pr is not None or pb is not None):
+        # d_root / d_bias on a SIDE stream, enqueued before the dX launch: the streaming kernel is HBM-bound with a tenth
+        # of a launch's MFMAs, uses no LDS and few registers, so its workgroups share the CUs with the MFMA-bound dX
+        # kernel instead of adding their ~1 ms behind it (DESIGN.md 4.3).  The join is a stream wait, never a host sync.
+        side = _side_stream(gp.device)
+        side.wait_stream(torch.cuda.current_stream(gp.device))      # gp (and xp) are produced on the current stream
+    with torch.cuda.stream(side):
+        _dw_tiles(plans.dw, plans.dw_walk, xp, din, gp, dout, (None, pr, pb), flags)
+    return side
+
+
+def _dw_one_gpu_tiles(plans: GraphPlans, parts, side, xp: Tensor, din: int, gp: Tensor, dout: int, flags: int) -> None:
+    """One GPU on the tile-major plan, the part enqueued AFTER the dX launch: d_weight, then the join with ``side``"""
+    _dw_tiles(plans.dw, plans.dw_walk, xp, din, gp, dout, (parts[0], None, None), flags)
+    if side is not None:
+        torch.cuda.current_stream(gp.device).wait_stream(side)
+
+
+def _dw_rank_range(dw_rank, new, views, stats: dict, xp: Tensor, din: int, gp: Tensor, dout: int, flags: int) -> Optional[Tensor]:
+    """Full exchange: x and g are replicated, so this rank's share of the weight gradients is ONE contiguous node range of its own
+    (dist.dw_range) -- one tile-major launch + the streaming root part, whatever the pieces.  Returns the flat buffer (zeros for
+    an empty range), or None where the kernel cannot address the range's rows of g: the pieces take the gradients then."""
+    dwp, walk = dw_rank
+    if dwp is None:
+        return new(zeros=True)
+    if not _lib.buffer_addressable(dwp.n_owned, gp.shape[1]):
+        return None
+    acc = new()
+    _dw_tiles(dwp, walk, xp, din, gp, dout, views(acc), flags)
+    stats["dw_tiles_rank"] = stats.get("dw_tiles_rank", 0) + 1
+    return acc
+
+
+def _dw_pieces(pieces, dctx: Optional[DistContext], new, views, on_tiles, hmat: Optional[Tensor], xp: Tensor, din: int, gp: Tensor,
+               dout: int, flags: int) -> Tensor:
+    """Piece by piece (one GPU off the tile-major plan: the graph is the one piece): each piece's gradients into a flat buffer
+    of its own, by the tile-major kernel (a rank's pieces only) or the relation-major ones, and the buffers added up.  Zeros
+    without a piece that owns a row."""
+    acc = None
+    for pc in pieces:
+        if pc.fwd_walk.n_owned <= 0:
+            continue
+        part = new()
+        if dctx is not None and on_tiles(pc):
+            # a rank's piece on the tile-major kernel, as the single-GPU step (its root part: the piece's own rows)
+            _dw_tiles(pc.dw, pc.dw_walk, xp, din, gp, dout, views(part), flags)
+            dctx.stats["dw_tiles_pieces"] = dctx.stats.get("dw_tiles_pieces", 0) + 1
+        else:
+            _dw_walk(pc, xp, din, gp, dout, views(part), flags, hmat)
+        acc = part if acc is None else acc.add_(part)
+    return new(zeros=True) if acc is None else acc
+
+
 class _RGCNLayerFn(torch.autograd.Function):
     """a = act(sum_r mean-aggregate_r(x) @ W_r + x @ root + bias)   (forward: rgcn_fwd with the activation fused
     into its store; backward: rgcn_bwd_dx on the transposed plan + the weight-gradient kernels)."""
@@ -346,9 +463,8 @@ class _RGCNLayerFn(torch.autograd.Function):
         xp = _rows16(x, din)
         wf, cp, rt, bs = _operands(weight, comp, root, bias)
         packed = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
-        ldo = _round4(dout)
         if dctx is None:
-            out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
+            out = _padded_rows(n, dout, x.device)
             ctx.ep_heavy = _launch_fwd(plans.fwd or plans.ep_fwd, xp, din, packed, bs, out, dout, act, flags)
         else:
             # every rank computes its own blocks straight into the gathered buffer; with destination-range
@@ -359,15 +475,12 @@ class _RGCNLayerFn(torch.autograd.Function):
             # of the [segments, in] sums, then the owners' pseudo rows go through the transform)
             hm_f = ctx.ep_heavy = _shared_heavy_sums(plans.shared_fwd, xp, din, dctx)
             out = _gather_pieces(dctx, [p.fwd or p.ep_fwd for p in plans.pieces],
-                                 lambda pl, rows: _launch_fwd(pl, xp, din, packed, bs, rows, dout, act, flags, hm_f), ldo, n,
-                                 x.device, needed=plans.needed_fwd if dctx.exchange == "needed" else None)
+                                 lambda pl, rows: _launch_fwd(pl, xp, din, packed, bs, rows, dout, act, flags, hm_f),
+                                 _round4(dout), n, x.device, needed=plans.needed_fwd if dctx.exchange == "needed" else None)
         ctx.plans, ctx.dctx, ctx.dims = plans, dctx, (n, din, dout, num_rel)
         ctx.input_relu, ctx.flags = input_relu, flags
-        # the activated output is only needed to differentiate the activation; a ReLU whose consumer folds the mask
-        # into its dX store (grad_premasked) needs nothing
-        ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
-        ctx.save_for_backward(xp, wf, cp, rt, out if ctx.need_a else None)
-        return out if ldo == dout else out[:, :dout]
+        ctx.save_for_backward(xp, wf, cp, rt, _keep_activated(ctx, act, grad_premasked, out))
+        return _trim(out, dout)
 
     @staticmethod
     def backward(ctx, g: Tensor):
@@ -376,47 +489,26 @@ class _RGCNLayerFn(torch.autograd.Function):
         n, din, dout, num_rel = ctx.dims
         need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]      # (False for an input that is None)
         need_w = need_wparam or need_comp              # the dense d_W[R, in, out] (for a decomposition: scratch)
-        gp = _rows16(g, dout)
-        if ctx.need_a:
-            gp = _lib.act_backward(a_out, gp, ctx.act)       # dL/dz = dL/da * act'(a)
+        need_any = need_w or need_root or need_bias
         dev = g.device
-        dx = acc = finish_dx = side = None
-        # ONE flat buffer for the three weight gradients (a single all-reduce in the distributed case)
-        sizes = [num_rel * din * dout if need_w else 0, din * dout if need_root else 0, dout if need_bias else 0]
-
-        def views(flat):
-            o0, o1 = sizes[0], sizes[0] + sizes[1]
-            return (flat[:o0].view(num_rel, din, dout) if need_w else None,
-                    flat[o0:o1].view(din, dout) if need_root else None,
-                    flat[o1:].view(dout) if need_bias else None)
-
-        # a piece (one GPU: the graph) with a tile-major d_weight plan takes it (layout-3 forward plans always: the relation-major
-        # kernels refuse them) unless the flags pin other kernels; that kernel gathers x and g through buffer descriptors only
+        gp = _grad_z(ctx, g, dout, a_out)
+        new, views = _flat_grads(need_w, need_root, need_bias, num_rel, din, dout, dev)
+        dw_ops = (xp, din, gp, dout, flags)            # what every weight-gradient launch takes
+        # the flags leave the tile-major d_weight kernel open to this layer (_dw_on_tiles then asks piece by piece)
         tiles_ok = (not flags & (_lib.FLAG_DW_RING | _lib.FLAG_DW_DIRECT | _lib.FLAG_POINTER_GATHER)
                     and _lib.buffer_addressable(n, xp.shape[1]))
-
-        def on_tiles(pc):
-            return (tiles_ok and pc.dw is not None and (need_w or pc.fwd.layout == 3)
-                    and _lib.buffer_addressable(pc.fwd.n_owned, gp.shape[1]))
-
-        tiles = dctx is None and (need_w or need_root or need_bias) and on_tiles(plans)
-        if tiles:
-            acc = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            pw, pr, pb = views(acc)
-            if need_x and n >= _SIDE_STREAM_MIN_ROWS and (pr is not None or pb is not None):
-                # d_root / d_bias on a SIDE stream, enqueued before the dX launch: the streaming kernel is HBM-bound with a tenth
-                # of a launch's MFMAs, uses no LDS and few registers, so its workgroups share the CUs with the MFMA-bound dX
-                # kernel instead of adding their ~1 ms behind it.  The join is a stream wait, never a host sync.
-                side = _side_stream(dev)
-                side.wait_stream(torch.cuda.current_stream(dev))      # gp (and xp) are produced on the current stream
-            with torch.cuda.stream(side):
-                _dw_tiles(plans.dw, plans.dw_walk, xp, din, gp, dout, (None, pr, pb), flags)
+        one_gpu_tiles = dctx is None and need_any and _dw_on_tiles(plans, tiles_ok, need_w, gp)
+        dx = acc = finish_dx = None
+        # d_root / d_bias of one GPU on the tile-major plan: enqueued before the dX launch
+        if one_gpu_tiles:
+            acc = new()
+            side = _dw_one_gpu_root(plans, views(acc), need_x and n >= _SIDE_STREAM_MIN_ROWS, *dw_ops)
+        # dX
         if need_x:
             packed_t = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=True)
-            ldx = _round4(din)
             mask = xp if ctx.input_relu else None            # x = relu(z_prev): store dL/dz_prev = dx * (x > 0)
             if dctx is None:
-                dxp = torch.empty(n, ldx, dtype=torch.float32, device=dev)
+                dxp = _padded_rows(n, din, dev)
                 _launch_dx(plans.bwd or plans.ep_bwd, gp, dout, packed_t, dxp, din, mask, flags)
             else:
                 hm_b = _shared_heavy_sums(plans.shared_bwd, gp, dout, dctx)
@@ -426,37 +518,17 @@ class _RGCNLayerFn(torch.autograd.Function):
                     dctx, [p.bwd or p.ep_bwd for p in plans.pieces],
                     lambda pl, rows: _launch_dx(pl, gp, dout, packed_t, rows, din,
                                                 None if mask is None else mask[pl.node_begin:pl.node_end], flags, hm_b),
-                    ldx, n, dev, needed=plans.needed_bwd if dctx.exchange == "needed" else None, defer=True)
-            dx = dxp if ldx == din else dxp[:, :din]
-        if tiles:
-            _dw_tiles(plans.dw, plans.dw_walk, xp, din, gp, dout, (pw, None, None), flags)
-            if side is not None:
-                torch.cuda.current_stream(dev).wait_stream(side)
-        elif need_w or need_root or need_bias:
-            pieces = [plans] if dctx is None else plans.pieces
+                    _round4(din), n, dev, needed=plans.needed_bwd if dctx.exchange == "needed" else None, defer=True)
+            dx = _trim(dxp, din)
+        # the weight gradients, and across ranks their all-reduce
+        if one_gpu_tiles:
+            _dw_one_gpu_tiles(plans, views(acc), side, *dw_ops)
+        elif need_any:
             if dctx is not None and plans.dw_rank is not None and tiles_ok:
-                # full exchange: x and g are replicated, so this rank's share of the weight gradients is ONE contiguous node
-                # range of its own (dist.dw_range) -- one tile-major launch + the streaming root part, whatever the pieces
-                dwp, walk = plans.dw_rank
-                if dwp is None:        # an empty range: zeros below
-                    pieces = []
-                elif _lib.buffer_addressable(dwp.n_owned, gp.shape[1]):
-                    acc, pieces = torch.empty(sum(sizes), dtype=torch.float32, device=dev), []
-                    _dw_tiles(dwp, walk, xp, din, gp, dout, views(acc), flags)
-                    dctx.stats["dw_tiles_rank"] = dctx.stats.get("dw_tiles_rank", 0) + 1
-            for pc in pieces:
-                if pc.fwd_walk.n_owned <= 0:
-                    continue
-                part = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-                if dctx is not None and on_tiles(pc):
-                    # a rank's piece on the tile-major kernel, as the single-GPU step (its root part: the piece's own rows)
-                    _dw_tiles(pc.dw, pc.dw_walk, xp, din, gp, dout, views(part), flags)
-                    dctx.stats["dw_tiles_pieces"] = dctx.stats.get("dw_tiles_pieces", 0) + 1
-                else:
-                    _dw_walk(pc, xp, din, gp, dout, views(part), flags, ctx.ep_heavy)
-                acc = part if acc is None else acc.add_(part)
+                acc = _dw_rank_range(plans.dw_rank, new, views, dctx.stats, *dw_ops)
             if acc is None:
-                acc = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+                acc = _dw_pieces([plans] if dctx is None else plans.pieces, dctx, new, views,
+                                 lambda pc: _dw_on_tiles(pc, tiles_ok, need_w, gp), ctx.ep_heavy, *dw_ops)
             if dctx is not None:
                 if not dctx.emulate:
                     torch.distributed.all_reduce(acc, group=dctx.group)
@@ -465,9 +537,7 @@ class _RGCNLayerFn(torch.autograd.Function):
         dw, droot, dbias = (None, None, None) if acc is None else views(acc)
         if finish_dx is not None:
             finish_dx()
-        dcomp = None
-        if dw is not None and (cp is not None or wf.dim() == 4):
-            dw, dcomp = _lib.decomposed_weight_grads(dw.contiguous(), wf, cp, need_wparam, need_comp)
+        dw, dcomp = _own_param_grads(dw, wf, cp, need_wparam, need_comp)      # a decomposition's own gradients from the dense d_W
         return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None, None
 
 
@@ -485,13 +555,11 @@ class _MaxLayerFn(torch.autograd.Function):
         wf, cp, rt, bs = _operands(weight, comp, root, bias)
         packed = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
         hmat, tmat = _lib.max_aggregate(mp, xp, din, with_t=ctx.needs_input_grad[0])
-        ldo = _round4(dout)
-        out = torch.empty(n, ldo, dtype=torch.float32, device=x.device)
+        out = _padded_rows(n, dout, x.device)
         _lib.ep_layer(mp.ep, xp, din, packed, bs, out, dout, act, None, flags, hmat=hmat)
         ctx.mp, ctx.dims, ctx.input_relu, ctx.flags = mp, (n, din, dout, num_rel), input_relu, flags
-        ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
-        ctx.save_for_backward(xp, wf, cp, rt, hmat, tmat, out if ctx.need_a else None)
-        return out if ldo == dout else out[:, :dout]
+        ctx.save_for_backward(xp, wf, cp, rt, hmat, tmat, _keep_activated(ctx, act, grad_premasked, out))
+        return _trim(out, dout)
 
     @staticmethod
     def backward(ctx, g: Tensor):
@@ -499,17 +567,14 @@ class _MaxLayerFn(torch.autograd.Function):
         mp, flags = ctx.mp, ctx.flags
         n, din, dout, num_rel = ctx.dims
         need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]      # (False for an input that is None)
-        gp = _rows16(g, dout)
-        if ctx.need_a:
-            gp = _lib.act_backward(a_out, gp, ctx.act)
+        gp = _grad_z(ctx, g, dout, a_out)
         f32 = dict(dtype=torch.float32, device=g.device)
-        dx = dw = droot = dbias = dcomp = None
+        dx = dw = droot = dbias = None
         if need_x:
             packed_t = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=True)
-            ldx = _round4(din)
-            dxp = torch.empty(n, ldx, **f32)
+            dxp = _padded_rows(n, din, g.device)
             _lib.max_layer_dx(mp, xp, hmat, tmat, gp, dout, packed_t, dxp, din, xp if ctx.input_relu else None, flags)
-            dx = dxp if ldx == din else dxp[:, :din]
+            dx = _trim(dxp, din)
         if need_wparam or need_comp:
             dw = torch.zeros(num_rel, din, dout, **f32) if mp.ep.heavy is None else torch.empty(num_rel, din, dout, **f32)
             if mp.ep.heavy is not None:
@@ -521,8 +586,7 @@ class _MaxLayerFn(torch.autograd.Function):
                 _lib.bwd_dw_root(xp, din, gp, dout, droot, dbias)
             else:        # (the light units hold the root rows alone: their relation-major walk is the root-only walk)
                 _lib.bwd_dw(_lib.plan_struct(mp.ep.as_tile_plan()), xp, din, gp, dout, None, droot, dbias, flags)
-        if dw is not None and (cp is not None or wf.dim() == 4):
-            dw, dcomp = _lib.decomposed_weight_grads(dw, wf, cp, need_wparam, need_comp)
+        dw, dcomp = _own_param_grads(dw, wf, cp, need_wparam, need_comp)
         return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None, None
 
 
@@ -536,39 +600,34 @@ class _XwideFn(torch.autograd.Function):
         n, din = x.shape
         xp = _rows16(x, din)
         wf, cp, rt, bs = _operands(weight, comp, root, bias)
-        out = torch.empty(n, _round4(dout), dtype=torch.float32, device=x.device)
+        out = _padded_rows(n, dout, x.device)
         op = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=False)
         _lib.xwide_fwd(_lib.plan_struct(plans.fwd), xp, din, op, bs, out, dout, act)
         del op
         ctx.plans, ctx.dims, ctx.input_relu = plans, (n, din, dout, num_rel), input_relu
-        ctx.act, ctx.need_a = act, act == _lib.ACT_SIGMOID or (act == _lib.ACT_RELU and not grad_premasked)
-        ctx.save_for_backward(xp, wf, cp, rt, out if ctx.need_a else None)
-        return out if out.shape[1] == dout else out[:, :dout]
+        ctx.save_for_backward(xp, wf, cp, rt, _keep_activated(ctx, act, grad_premasked, out))
+        return _trim(out, dout)
 
     @staticmethod
     def backward(ctx, g: Tensor):
         xp, wf, cp, rt, a_out = ctx.saved_tensors
         n, din, dout, num_rel = ctx.dims
         need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]
-        gp = _rows16(g, dout)
-        if ctx.need_a:
-            gp = _lib.act_backward(a_out, gp, ctx.act)
-        dx = dw = droot = dbias = dcomp = None
+        gp = _grad_z(ctx, g, dout, a_out)
+        dx = dw = droot = dbias = None
         if need_x:
             opt = _xwide_operand(wf, cp, rt, num_rel, din, dout, transpose=True)
-            ldx = _round4(din)
-            dxp = torch.empty(n, ldx, dtype=torch.float32, device=g.device)
+            dxp = _padded_rows(n, din, g.device)
             _lib.xwide_bwd_dx(_lib.plan_struct(ctx.plans.bwd), gp, dout, opt, dxp, din, xp if ctx.input_relu else None)
             del opt
-            dx = dxp if ldx == din else dxp[:, :din]
+            dx = _trim(dxp, din)
         if need_wparam or need_comp or need_root or need_bias:
             f32 = dict(dtype=torch.float32, device=g.device)
             dw = torch.empty(num_rel, din, dout, **f32) if need_wparam or need_comp else None
             droot = torch.empty(din, dout, **f32) if need_root else None
             dbias = torch.empty(dout, **f32) if need_bias else None
             _lib.xwide_bwd_dw(_lib.plan_struct(ctx.plans.fwd), xp, din, gp, dout, dw, droot, dbias)
-        if dw is not None and (cp is not None or wf.dim() == 4):
-            dw, dcomp = _xwide_decomposed_grads(dw, wf, cp, need_wparam, need_comp)
+        dw, dcomp = _own_param_grads(dw, wf, cp, need_wparam, need_comp, xwide=True)
         return dx, dw, dcomp, droot, dbias, None, None, None, None, None, None
 
 
@@ -580,13 +639,12 @@ class _FeaturelessFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor], plans: GraphPlans,
                 index, in_rows: int, dout: int):
-        n = plans.fwd.n_nodes
         wf, cp, rt, bs = _operands(weight, comp, root, bias)
-        out = torch.empty(n, _round4(dout), dtype=torch.float32, device=wf.device)
+        out = _padded_rows(plans.fwd.n_nodes, dout, wf.device)
         _lib.featureless_fwd(_lib.plan_struct(plans.fwd), None if index is None else index[0], in_rows, wf, cp, rt, bs, out, dout)
         ctx.plans, ctx.index, ctx.in_rows, ctx.dout = plans, index, in_rows, dout
         ctx.save_for_backward(wf, cp)
-        return out if out.shape[1] == dout else out[:, :dout]
+        return _trim(out, dout)
 
     @staticmethod
     def backward(ctx, g: Tensor):
@@ -626,6 +684,20 @@ def _node_index(x: Tensor, in_rows: int):
     return hit[0]
 
 
+def _require_gpu(*tensors: Optional[Tensor]) -> None:
+    """there is no CPU path: every tensor given (None: skipped) must live on the GPU"""
+    if any(t is not None and t.device.type != "cuda" for t in tensors):
+        raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+
+
+def _fused(activation: Optional[str], grad_premasked: bool) -> Tuple[int, bool]:
+    """(the rgcn_act code of the activation fused into the forward store, whether its backward is left to the consumers of the
+    output: only a ReLU's mask can be folded into their dX stores)"""
+    if activation not in _ACT_CODES:
+        raise ValueError(f"fused activation must be one of {list(_ACT_CODES)}")
+    return _ACT_CODES[activation], bool(grad_premasked and activation == "relu")
+
+
 def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: Optional[Tensor],
                        plans: GraphPlans, dctx: Optional[DistContext] = None, activation: Optional[str] = None,
                        input_relu: bool = False, grad_premasked: bool = False, flags: int = 0,
@@ -634,10 +706,8 @@ def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: 
     """weight: dense [R, in, out]; or, with ``comp [R, B]``, the bases [B, in, out]; or blocks [R, nb, in / nb, out / nb]
     (then ``out_channels`` = nb * weight.shape[3]).  ``xwide``: the kernels of csrc/rgcn_xwide.hip (1..512 per side; ``plans``
     at rgcn_xwide_geometry, layout 0, single GPU)."""
-    if x.device.type != "cuda":
-        raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
-    if activation not in _ACT_CODES:
-        raise ValueError(f"fused activation must be one of {list(_ACT_CODES)}")
+    _require_gpu(x)
+    act, premasked = _fused(activation, grad_premasked)
     _lib.load()
     if comp is not None:
         num_rel, dout = int(comp.shape[0]), int(weight.shape[2])
@@ -648,10 +718,10 @@ def rgcn_conv_function(x: Tensor, weight: Tensor, root: Optional[Tensor], bias: 
     if xwide:
         if dctx is not None:
             raise NotImplementedError("RGCNConv wider than 128 runs on one GPU: a dist context is not supported")
-        return _XwideFn.apply(x, weight, comp, root, bias, plans, _ACT_CODES[activation], bool(input_relu), bool(grad_premasked),
+        return _XwideFn.apply(x, weight, comp, root, bias, plans, act, bool(input_relu), premasked, num_relations or num_rel,
+                              out_channels or dout)
+    return _RGCNLayerFn.apply(x, weight, comp, root, bias, plans, dctx, act, bool(input_relu), premasked, int(flags),
                               num_relations or num_rel, out_channels or dout)
-    return _RGCNLayerFn.apply(x, weight, comp, root, bias, plans, dctx, _ACT_CODES[activation], bool(input_relu),
-                              bool(grad_premasked), int(flags), num_relations or num_rel, out_channels or dout)
 
 
 def _paths(path):
@@ -902,8 +972,7 @@ class RGCNConv(nn.Module):
         # rgcn_fwd / rgcn_bwd_dx / rgcn_bwd_dw_tiles / rgcn_ep_transform: the bf16 x 3 (fp32-equivalent) forms of 64 x 64 layers
         # where they fit.  (The mode follows the route's chunk, not which path the other direction happened to take.)
         flags = self.kernel_flags | (_lib.FLAG_SPLIT_PRODUCERS if route.split_producers else 0)
-        return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, self.dist,
-                                  _activation, _input_relu, _grad_premasked and _activation == "relu", flags,
+        return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, self.dist, _activation, _input_relu, _grad_premasked, flags,
                                   comp=self.comp, num_relations=self.num_relations, out_channels=self.out_channels)
 
     def _forward_xwide(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, activation: Optional[str], input_relu: bool,
@@ -913,27 +982,23 @@ class RGCNConv(nn.Module):
         paths = _paths(self.path)
         if paths != "auto" and "ep" in paths:
             raise ValueError("RGCNConv wider than 128 has no edge-parallel path: path must be 'auto' or 'ring'")
-        if x.device.type != "cuda":
-            raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+        _require_gpu(x)
         n = int(x.shape[0])
         tile, chunk = _lib.xwide_geometry(max(n, 1), self.in_channels, self.out_channels)
         plans = cached_graph_plans(edge_index, edge_type, n, self.num_relations, tile, self.aggr, chunk=chunk, extra_key=("xwide",))
-        return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, None, activation, input_relu,
-                                  grad_premasked and activation == "relu", 0, comp=self.comp, num_relations=self.num_relations,
-                                  out_channels=self.out_channels, xwide=True)
+        return rgcn_conv_function(x, self.weight, self.root, self.bias, plans, None, activation, input_relu, grad_premasked, 0,
+                                  comp=self.comp, num_relations=self.num_relations, out_channels=self.out_channels, xwide=True)
 
     def _forward_max(self, x: Tensor, edge_index: Tensor, edge_type: Tensor, activation: Optional[str], input_relu: bool,
                      grad_premasked: bool) -> Tensor:
         if self.dist is not None:
             raise NotImplementedError("RGCNConv(aggr='max') runs on one GPU: a dist context is not supported")
-        if x.device.type != "cuda":
-            raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+        _require_gpu(x)
         if edge_index.device != x.device or edge_type.device != x.device:
             # (the plan is built where the edges live: a CPU plan's index arrays must never reach a kernel)
             raise RuntimeError(f"RGCNConv(aggr='max'): edge_index ({edge_index.device}) and edge_type ({edge_type.device}) must be on "
                                f"the device of x ({x.device})")
-        if activation not in _ACT_CODES:
-            raise ValueError(f"fused activation must be one of {list(_ACT_CODES)}")
+        act, premasked = _fused(activation, grad_premasked)
         _lib.load()
         from .eplan import build_max_plan
         n, r = int(x.shape[0]), self.num_relations
@@ -941,8 +1006,8 @@ class RGCNConv(nn.Module):
                                 builder=lambda paths: build_max_plan(edge_index, edge_type, n, r))
         # the bf16 x 3 (fp32-equivalent) transform of 64 x 64 layers, as on the edge-parallel path
         flags = self.kernel_flags | (_lib.FLAG_SPLIT_PRODUCERS if self.split_producers and self._w64 else 0)
-        return _MaxLayerFn.apply(x, self.weight, self.comp, self.root, self.bias, mp, _ACT_CODES[activation], bool(input_relu),
-                                 bool(grad_premasked and activation == "relu"), int(flags), r, self.out_channels)
+        return _MaxLayerFn.apply(x, self.weight, self.comp, self.root, self.bias, mp, act, bool(input_relu), premasked, int(flags), r,
+                                 self.out_channels)
 
     def _forward_featureless(self, x: Optional[Tensor], edge_index: Tensor, edge_type: Tensor) -> Tensor:
         if self.dist is not None:
@@ -952,8 +1017,7 @@ class RGCNConv(nn.Module):
                 raise ValueError("featureless RGCNConv takes x = None or an integer node-index tensor, not float features")
             if x.dim() != 1:
                 raise ValueError(f"featureless RGCNConv: x must be a [N] node-index tensor, got {tuple(x.shape)}")
-        if edge_index.device.type != "cuda" or (x is not None and x.device.type != "cuda"):
-            raise RuntimeError("RGCNConv runs only on an MI355X (ROCm 'cuda' device); there is no CPU fallback")
+        _require_gpu(edge_index, x)
         _lib.load()
         n = self.in_channels if x is None else int(x.shape[0])
         index = None if x is None else _node_index(x, self.in_channels)

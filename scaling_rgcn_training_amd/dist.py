@@ -322,16 +322,12 @@ def rank_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relation
     for s, (b, e) in enumerate(ranges):
         fm, bm = fpiece == s, bpiece == s
         gp = GraphPlans(fwd=None, bwd=None, num_edges=int(fm.sum()))
-        if e <= b:
-            gp.fwd = build_plan(fg[fm], fs[fm], fr[fm], fw[fm], n_nodes, num_relations, tile, b, e, chunk, split)
-            gp.bwd = build_plan(bg[bm], bs[bm], br[bm], bw[bm], n_nodes, num_relations, tile, b, e, chunk, split)
-            out.append(gp)
-            continue
-        if paths[0] == "ep":
+        # (an empty block takes both tile plans, whatever ``paths`` says)
+        if paths[0] == "ep" and e > b:
             gp.ep_fwd = build_edge_plan(src, dst, rel, w, n_nodes, num_relations, b, e, heavy=HEAVY, shared=sh_f)
         else:
             gp.fwd = build_plan(fg[fm], fs[fm], fr[fm], fw[fm], n_nodes, num_relations, tile, b, e, chunk, split)
-        if paths[1] == "ep":
+        if paths[1] == "ep" and e > b:
             gp.ep_bwd = build_edge_plan(dst, src, rel, w, n_nodes, num_relations, b, e, heavy=HEAVY, shared=sh_b)
         else:
             gp.bwd = build_plan(bg[bm], bs[bm], br[bm], bw[bm], n_nodes, num_relations, tile, b, e, chunk, split)

@@ -212,22 +212,27 @@ class EdgePlan:
             ts += [h.unit_rel, h.unit_cnt, h.slot_src, h.slot_w, h.slot_row] + [t for lv in h.levels for t in lv[:3] if t is not None]
         return sum(t.numel() * t.element_size() for t in ts)
 
+    def _layout2_plan(self, units, n_gathered: int, n_edges: int):
+        """``units`` (this plan or its heavy part: unit_rel, unit_cnt and the slot arrays) as a layout-2 plan.TilePlan over the
+        owned range, gathering a matrix of ``n_gathered`` rows"""
+        from .plan import TilePlan
+        dev = self.device
+        n_own = self.n_owned
+        tile = min(32768, (n_own + 15) // 16 * 16)
+        n_tiles = (n_own + tile - 1) // tile
+        z = torch.zeros(units.n_units, dtype=torch.int32, device=dev)
+        return TilePlan(
+            n_nodes=n_gathered, node_begin=self.node_begin, node_end=self.node_end, num_relations=self.num_relations, tile=tile,
+            chunk=UNIT, n_tiles=n_tiles, n_chunks=units.n_units, n_edges=n_edges,
+            tile_ptr=torch.zeros(n_tiles + 1, dtype=torch.int32, device=dev), chunk_rel=units.unit_rel, chunk_cnt=units.unit_cnt,
+            chunk_tile=z, chunk_flags=z, rel_order=torch.arange(units.n_units, dtype=torch.int32, device=dev),
+            slot_src=units.slot_src, slot_w=units.slot_w, slot_dstl=None, slot_row=units.slot_row, slot_acc=units.slot_row, layout=2)
+
     def heavy_tile_plan(self):
         """the heavy part's pseudo rows as a layout-2 plan for rgcn_bwd_dw (its gathered matrix is the aggregated H)"""
         h = self.heavy
         if h._tile_plan is None:
-            from .plan import TilePlan
-            dev = self.device
-            n_own = self.n_owned
-            tile = min(32768, (n_own + 15) // 16 * 16)
-            n_tiles = (n_own + tile - 1) // tile
-            z = torch.zeros(h.n_units, dtype=torch.int32, device=dev)
-            h._tile_plan = TilePlan(
-                n_nodes=h.n_seg, node_begin=self.node_begin, node_end=self.node_end, num_relations=self.num_relations, tile=tile,
-                chunk=UNIT, n_tiles=n_tiles, n_chunks=h.n_units, n_edges=h.n_seg,
-                tile_ptr=torch.zeros(n_tiles + 1, dtype=torch.int32, device=dev), chunk_rel=h.unit_rel, chunk_cnt=h.unit_cnt,
-                chunk_tile=z, chunk_flags=z, rel_order=torch.arange(h.n_units, dtype=torch.int32, device=dev), slot_src=h.slot_src,
-                slot_w=h.slot_w, slot_dstl=None, slot_row=h.slot_row, slot_acc=h.slot_row, layout=2)
+            h._tile_plan = self._layout2_plan(h, h.n_seg, h.n_seg)
         return h._tile_plan
 
     def as_tile_plan(self):
@@ -235,19 +240,7 @@ class EdgePlan:
         rel_order, chunk_rel, chunk_cnt and the slot arrays only; there are no tiles to walk -- rgcn_fwd / rgcn_bwd_dx
         refuse such a plan)."""
         if self._tile_plan is None:
-            from .plan import TilePlan
-            dev = self.device
-            n_own = self.n_owned
-            tile = min(32768, (n_own + 15) // 16 * 16)
-            n_tiles = (n_own + tile - 1) // tile
-            z = torch.zeros(self.n_units, dtype=torch.int32, device=dev)
-            self._tile_plan = TilePlan(
-                n_nodes=self.n_nodes, node_begin=self.node_begin, node_end=self.node_end, num_relations=self.num_relations,
-                tile=tile, chunk=UNIT, n_tiles=n_tiles, n_chunks=self.n_units, n_edges=self.n_rows - n_own,
-                tile_ptr=torch.zeros(n_tiles + 1, dtype=torch.int32, device=dev), chunk_rel=self.unit_rel,
-                chunk_cnt=self.unit_cnt, chunk_tile=z, chunk_flags=z,
-                rel_order=torch.arange(self.n_units, dtype=torch.int32, device=dev), slot_src=self.slot_src,
-                slot_w=self.slot_w, slot_dstl=None, slot_row=self.slot_row, slot_acc=self.slot_row, layout=2)
+            self._tile_plan = self._layout2_plan(self, self.n_nodes, self.n_rows - self.n_owned)
         return self._tile_plan
 
 
