@@ -380,6 +380,30 @@ size_t rgcn_xwide_bwd_dw_workspace_bytes(const rgcn_plan_t* plan, int din, int d
 int rgcn_xwide_bwd_dw(const rgcn_plan_t* plan, const float* x, int ldx, int din, const float* g, int ldg, int dout, void* workspace,
                       size_t workspace_bytes, float* d_weight, float* d_root, float* d_bias, void* stream);
 
+/* ---- bipartite layers: the root term (csrc/rgcn_rows.hip) ------------------------------------------------------
+ * RGCNConv with x = (x_src, x_dst) (PyG 2.3.1): `root` is [in_dst, out] and multiplies x_dst, whose rows pair up one to one
+ * with the output rows -- a different matrix of a different width than the rows the plans gather, so the plans' root relation
+ * is packed as zeros and the term and its two gradients are dense, plan-free products over rows.  Widths 1..128 per side
+ * (RGCN_ERR_WIDTH), strides multiples of 4 and at least the width rounded up to 4 (RGCN_ERR_STRIDE), pad columns of the inputs
+ * zero; every argument check is answered without a device.  Exact fp32, no atomics, fixed summation orders: bit-reproducible.
+ * Row offsets are 64-bit: rows x ld may pass 2^31.
+ *
+ * rgcn_rows_transform: y[i, :] = add[i, :] + x[i, :] @ W + bias, i < rows.
+ *   x [rows, ldx], din columns.
+ *   transpose == 0: w is row-major [din, dout] and W = w.
+ *   transpose != 0: w is row-major [dout, din] and W = w^T (d_x = g @ root^T reads root itself).
+ *   add: NULL (zeros), or [rows, lda]; add may alias y.
+ *   bias: NULL or [dout].
+ *   Columns dout..roundup4(dout) of y are written as +0.0.  rows == 0 touches nothing.
+ * rgcn_rows_dw: d_w [din, dout] (dense, no padding) = x^T g over rows [0, rows).  rows == 0 writes zeros (x and g may then be NULL).
+ *   Per-wave partial slabs in `workspace` (the query answers 0 on bad widths), summed in a fixed order.  A row count whose
+ *   share per wave cannot be addressed with 32-bit offsets (beyond 2^31 rows at 128 columns) is RGCN_ERR_STRIDE. */
+int rgcn_rows_transform(const float* x, int ldx, int din, const float* w, int transpose, const float* add, int lda,
+                        const float* bias, float* y, int ldy, int dout, long rows, void* stream);
+size_t rgcn_rows_dw_workspace_bytes(int din, int dout);
+int rgcn_rows_dw(const float* x, int ldx, int din, const float* g, int ldg, int dout, long rows, void* workspace,
+                 size_t workspace_bytes, float* d_w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ from .plan import CHUNK, TilePlan, GraphPlans, build_plan, build_graph_plans, ed
 
 def __getattr__(name):
     # lazy: these need torch.nn / the HIP library, keep `import scaling_rgcn_training_amd` light
-    if name in ("RGCNConv", "rgcn_conv_function"):
+    if name in ("RGCNConv", "rgcn_conv_function", "target_block"):
         from . import conv
         return getattr(conv, name)
     if name == "Data":

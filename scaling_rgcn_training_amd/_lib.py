@@ -100,6 +100,9 @@ def _prototypes() -> dict:
         "rgcn_xwide_bwd_dw": (i32, [plan, vp, i32, i32, vp, i32, i32, vp, sz, vp, vp, vp, vp]),
         "rgcn_segment_max": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp]),
         "rgcn_segment_max_bwd": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, i64, i32, vp, i32, vp]),
+        "rgcn_rows_transform": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, lng, vp]),
+        "rgcn_rows_dw_workspace_bytes": (sz, [i32, i32]),
+        "rgcn_rows_dw": (i32, [vp, i32, i32, vp, i32, i32, lng, vp, sz, vp, vp]),
     }
 
 
@@ -373,6 +376,40 @@ def bwd_dw_root(x: torch.Tensor, din: int, g: torch.Tensor, dout: int, d_root: O
         ws = torch.empty(lib.rgcn_bwd_dw_root_workspace_bytes(), dtype=torch.uint8, device=x.device)
         check(lib.rgcn_bwd_dw_root(x.data_ptr(), x.stride(0), din, g.data_ptr(), g.stride(0), dout, x.shape[0],
                                    ws.data_ptr(), ws.numel(), _ptr(d_root), _ptr(d_bias), _stream(x)), "rgcn_bwd_dw_root")
+
+
+# ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------
+def rows_transform(x: torch.Tensor, din: int, w: torch.Tensor, dout: int, transpose: bool = False,
+                   add: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                   y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = add + x @ W + bias over the rows of x (rgcn_rows_transform): W = ``w [din, dout]``, or with ``transpose`` the
+    transpose of ``w [dout, din]``.  ``add`` may be ``y`` itself; without ``y`` a padded [rows, dout rounded up to 4] buffer
+    is allocated.  Returns y."""
+    rows = int(x.shape[0])
+    if y is None:
+        y = torch.empty(rows, (dout + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+    if y.shape[0] != rows or (add is not None and add.shape[0] != rows):
+        raise RgcnLibraryError("rgcn_rows_transform: x, add and y must have the same number of rows")
+    if rows == 0:       # (nothing to write; an empty tensor has no address to pass)
+        return y
+    with torch.cuda.device(x.device):
+        check(load().rgcn_rows_transform(x.data_ptr(), x.stride(0), din, w.data_ptr(), int(transpose), _ptr(add),
+                                         0 if add is None else add.stride(0), _ptr(bias), y.data_ptr(), y.stride(0), dout, rows,
+                                         _stream(x)), "rgcn_rows_transform")
+    return y
+
+
+def rows_dw(x: torch.Tensor, din: int, g: torch.Tensor, dout: int) -> torch.Tensor:
+    """d_w [din, dout] = x^T g (rgcn_rows_dw): rows of x and g pair up one to one; no rows: zeros."""
+    lib = load()
+    if x.shape[0] != g.shape[0]:
+        raise RgcnLibraryError("rgcn_rows_dw: x and g must have the same number of rows")
+    d_w = torch.empty(din, dout, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = torch.empty(lib.rgcn_rows_dw_workspace_bytes(din, dout), dtype=torch.uint8, device=x.device)
+        check(lib.rgcn_rows_dw(x.data_ptr(), x.stride(0), din, g.data_ptr(), g.stride(0), dout, int(x.shape[0]), ws.data_ptr(),
+                               ws.numel(), d_w.data_ptr(), _stream(x)), "rgcn_rows_dw")
+    return d_w
 
 
 # ---- edge-parallel path (eplan.EdgePlan) ----------------------------------------------------------------------------

@@ -21,7 +21,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
-from .plan import GraphPlans, TilePlan, cached_graph_plans, choose_layout, padded_width
+from .plan import GraphPlans, TilePlan, build_graph_plans, cached_graph_plans, choose_layout, padded_width
 
 
 def _round4(n: int) -> int:
@@ -662,6 +662,102 @@ class _FeaturelessFn(torch.autograd.Function):
         return dw, dcomp, droot, dbias, None, None, None, None
 
 
+class _BipartiteFn(torch.autograd.Function):
+    """out [N_dst, out] = sum_r aggregate_r(x_src) @ W_r + x_dst @ root + bias (PyG's ``x = (x_src, x_dst)``).  The relations run on
+    the plans of a square graph of N = max(N_src, N_dst) nodes that own the rows [0, N_dst) forward and [0, N_src) transposed,
+    with the root relation packed as zeros (its pseudo edges add exactly 0); the root term, d_x_dst and d_root -- a matrix of
+    another width over rows that pair up one to one -- by csrc/rgcn_rows.hip.  ``plans`` is None without a destination row."""
+
+    @staticmethod
+    def forward(ctx, x_src: Tensor, x_dst: Tensor, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor],
+                bias: Optional[Tensor], plans: Optional[GraphPlans], flags: int, num_rel: int, dout: int):
+        (n_src, din), (n_dst, din_r) = x_src.shape, x_dst.shape
+        n = max(n_src, n_dst)
+        wf, cp, rt, bs = _operands(weight, comp, root, bias)
+        ctx.plans, ctx.flags, ctx.dims = plans, flags, (n_src, n_dst, din, din_r, dout, num_rel)
+        if plans is None:
+            ctx.save_for_backward(wf, cp)
+            return torch.empty(0, dout, dtype=torch.float32, device=x_src.device)
+        if n_src == n:
+            xp = _rows16(x_src, din)
+        else:       # gathered operands have plan.n_nodes rows: the rows past N_src are the zeros no edge reads
+            xp = torch.zeros(n, _round4(din), dtype=torch.float32, device=x_src.device)
+            xp[:n_src, :din] = x_src.detach()
+        xd = _rows16(x_dst, din_r)
+        packed = _lib.pack_weights_decomposed(wf, cp, None, num_rel, din, dout, transpose=False)
+        out = _padded_rows(n_dst, dout, x_src.device)
+        ctx.ep_heavy = _launch_fwd(plans.fwd or plans.ep_fwd, xp, din, packed, bs, out, dout, _lib.ACT_NONE, flags)
+        if rt is not None:
+            _lib.rows_transform(xd, din_r, rt, dout, add=out, y=out)
+        ctx.save_for_backward(xp, xd, wf, cp, rt)
+        return _trim(out, dout)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        n_src, n_dst, din, din_r, dout, num_rel = ctx.dims
+        need_xs, need_xd, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:6]   # (False for a None input)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        if ctx.plans is None:       # no destination row: every gradient is a zero
+            wf, cp = ctx.saved_tensors
+            return (torch.zeros(n_src, din, **f32) if need_xs else None, torch.zeros(0, din_r, **f32) if need_xd else None,
+                    torch.zeros_like(wf) if need_wparam else None, torch.zeros_like(cp) if need_comp else None,
+                    torch.zeros(din_r, dout, **f32) if need_root else None, torch.zeros(dout, **f32) if need_bias else None,
+                    None, None, None, None)
+        xp, xd, wf, cp, rt = ctx.saved_tensors
+        plans, flags = ctx.plans, ctx.flags
+        n = max(n_src, n_dst)
+        if n_dst == n:
+            gp = _rows16(g, dout)
+        else:       # the transposed plan gathers rows of g up to N: the upstream gradient straight into N rows, the tail zeroed
+            gp = _padded_rows(n, dout, g.device)
+            gp[n_dst:].zero_()
+            if gp.shape[1] != dout:
+                gp[:n_dst, dout:].zero_()
+            gp[:n_dst, :dout] = g
+        gd = gp[:n_dst]
+        dxs = dxd = dw = droot = dbias = None
+        if need_xs:
+            packed_t = _lib.pack_weights_decomposed(wf, cp, None, num_rel, din, dout, transpose=True)
+            bp = plans.bwd or plans.ep_bwd
+            dxp = _padded_rows(bp.node_end - bp.node_begin, din, g.device)
+            _launch_dx(bp, gp, dout, packed_t, dxp, din, None, flags)
+            dxs = _trim(dxp, din)[:n_src]
+        if need_xd and rt is not None:
+            dxd = _trim(_lib.rows_transform(gd, dout, rt, din_r, transpose=True), din_r)
+        need_w = need_wparam or need_comp
+        if need_w or need_bias:
+            new, views = _flat_grads(need_w, False, need_bias, num_rel, din, dout, g.device)
+            acc = new()
+            _dw_walk(plans, xp, din, gp, dout, views(acc), flags, ctx.ep_heavy)
+            dw, _, dbias = views(acc)
+        if need_root:
+            droot = _lib.rows_dw(xd, din_r, gd, dout)
+        dw, dcomp = _own_param_grads(dw, wf, cp, need_wparam, need_comp)
+        return dxs, dxd, dw, dcomp, droot, dbias, None, None, None, None
+
+
+def target_block(edge_index: Tensor, edge_type: Tensor, rows: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor]:
+    """The edges of a graph of ``num_nodes`` nodes whose destination is one of ``rows`` (int64, unique, in [0, num_nodes)), with
+    the destination relabelled to its position in ``rows``: ``conv((x, x[rows]), *target_block(edge_index, edge_type, rows, N))``
+    equals ``conv(x, edge_index, edge_type)[rows]`` and walks only those edges.  ALL edges into a kept row are kept (duplicates
+    too), so a mean's normaliser is the full graph's.  Pure torch on the device of the edges.  The returned tensors are new and
+    the plan cache keys on their identity: build them ONCE per (graph, rows) and keep them, or every call builds plans."""
+    if rows.dim() != 1 or rows.dtype != torch.int64:
+        raise ValueError(f"rows must be a 1-d int64 tensor, got {tuple(rows.shape)} {rows.dtype}")
+    dev = edge_index.device
+    rows = rows.to(dev)
+    k = int(rows.shape[0])
+    if k and (int(rows.min()) < 0 or int(rows.max()) >= num_nodes):
+        raise ValueError(f"rows must lie in [0, {num_nodes})")
+    pos = torch.full((max(int(num_nodes), 1),), -1, dtype=torch.int64, device=dev)
+    pos[rows] = torch.arange(k, dtype=torch.int64, device=dev)
+    if k and not bool((pos[rows] == torch.arange(k, dtype=torch.int64, device=dev)).all()):
+        raise ValueError("rows must be unique")
+    dst = pos[edge_index[1].long()]
+    keep = dst >= 0
+    return torch.stack([edge_index[0].long()[keep], dst[keep]]).contiguous(), edge_type[keep].contiguous()
+
+
 # inverted indices of integer x (featureless layers), keyed on the index tensor's identity like the plan cache: the node ids
 # sorted by x value and where each value starts -- built (and range-checked, one host synchronisation) once per x
 _INDEX_CACHE: dict = {}
@@ -766,6 +862,15 @@ class RGCNConv(nn.Module):
     It runs on its own kernels (``csrc/rgcn_segmax.hip`` with the edge-parallel transform and sums; plan: ``eplan.MaxPlan``) and
     has one path: ``path`` and ``RGCN_PATH`` are ignored.  One GPU only (no ``dist`` context; ``edge_index`` / ``edge_type`` on
     the device of ``x``), up to 128 features per side, not with ``featureless``.
+
+    Bipartite layers (PyG's ``in_channels=(in_src, in_dst)`` / ``x = (x_src, x_dst)``): ``weight`` takes ``in_src`` rows, ``root`` is
+    ``[in_dst, out]``; ``forward((x_src [N_src, in_src], x_dst [N_dst, in_dst]), edge_index, edge_type) -> [N_dst, out]`` with
+    ``edge_index[0] < N_src``, ``edge_index[1] < N_dst``: ``out[i] = sum_r aggr_r(x_src) W_r + x_dst[i] root + bias``, mean or sum,
+    full, basis or block weights, gradients to both members and every parameter.  A tuple is accepted on a layer built with an int
+    too (both widths equal); ``in_channels`` stays the source width, ``in_channels_l`` / ``in_channels_r`` name both.  The relations
+    run on the plans and kernels of a homogeneous layer over rectangular node ranges, the root term on ``csrc/rgcn_rows.hip``
+    (DESIGN.md 12).  One GPU, up to 128 features per side, no fused activation; not with ``featureless`` nor ``aggr="max"``.
+    ``target_block`` cuts the edges into a set of target rows for ``conv((x, x[rows]), *block)``.
     """
 
     def __init__(self, in_channels: int, out_channels: int, num_relations: int,
@@ -788,18 +893,30 @@ class RGCNConv(nn.Module):
                 raise ValueError(f"featureless RGCNConv: in_channels is the number of table rows, got {in_channels!r}")
             if not 1 <= out_channels <= 128:
                 raise ValueError(f"RGCNConv out_channels must be in 1..128, got {out_channels}")
+        in_channels_r = in_channels
         if isinstance(in_channels, (tuple, list)):
-            if in_channels[0] != in_channels[1]:
-                raise NotImplementedError("bipartite RGCNConv is not used by the reference and not built")
-            in_channels = in_channels[0]
+            # PyG's bipartite form: (source width, destination width); `weight` takes the first, `root` the second
+            if len(in_channels) != 2:
+                raise ValueError(f"in_channels must be an int or a (source, destination) pair, got {in_channels!r}")
+            in_channels, in_channels_r = int(in_channels[0]), int(in_channels[1])
         if aggr not in ("mean", "sum", "add", "max"):
             raise ValueError(f"unsupported aggr {aggr!r} (mean / sum / max)")
+        if in_channels_r != in_channels:
+            if aggr == "max":
+                raise NotImplementedError("bipartite RGCNConv aggregates by mean / sum only: aggr='max' is not built")
+            if self.wide and max(in_channels, in_channels_r, out_channels) > NARROW_MAX_WIDTH:
+                raise NotImplementedError(f"bipartite RGCNConv takes 1..{NARROW_MAX_WIDTH} features per side, got "
+                                          f"({in_channels}, {in_channels_r})->{out_channels} (wide layers are homogeneous)")
+            if not 1 <= in_channels_r <= NARROW_MAX_WIDTH:
+                raise ValueError(f"RGCNConv widths must be in 1..{NARROW_MAX_WIDTH}, got ({in_channels}, {in_channels_r})->{out_channels}")
         if aggr == "max" and self.featureless:
             raise ValueError("featureless RGCNConv has no max aggregation: aggr='max' takes float features x")
         if aggr == "max" and self.wide and max(in_channels, out_channels) > NARROW_MAX_WIDTH:
             raise NotImplementedError(f"RGCNConv(aggr='max') takes 1..{NARROW_MAX_WIDTH} features per side, got "
                                       f"{in_channels}->{out_channels} (wide layers aggregate by mean / sum only)")
-        self.in_channels = in_channels
+        self.in_channels = in_channels         # the SOURCE width (what the plans gather), an int as every use means
+        self.in_channels_l = in_channels       # PyG's name for it
+        self.in_channels_r = in_channels_r     # the destination width: rows of `root` (differs in a bipartite layer only)
         self.out_channels = out_channels
         self.num_relations = num_relations
         self.num_bases = num_bases
@@ -835,7 +952,7 @@ class RGCNConv(nn.Module):
             self.weight = nn.Parameter(torch.empty(num_relations, in_channels, out_channels))
             self.register_parameter("comp", None)
         if root_weight:
-            self.root = nn.Parameter(torch.empty(in_channels, out_channels))
+            self.root = nn.Parameter(torch.empty(in_channels_r, out_channels))
         else:
             self.register_parameter("root", None)
         if bias:
@@ -902,17 +1019,18 @@ class RGCNConv(nn.Module):
         """whether this layer runs on the kernels of csrc/rgcn_xwide.hip: ``wide`` and a side above 128"""
         return self.wide and max(self.in_channels, self.out_channels) > NARROW_MAX_WIDTH
 
-    def _route(self, n_nodes: int, n_edges: int, on_gpu: bool) -> "_Route":
+    def _route(self, n_nodes: int, n_edges: int, on_gpu: bool, plain: bool = False) -> "_Route":
         """Every kernel choice of this layer on a graph of that size (``on_gpu``: its tensors are on the device).  The tile is
         ``layout_for``'s, capped at the producer-split kernel's tile where that kernel will run (dist.attach aligns the ranks' node
-        ranges to it), or at the tile that leaves the exact-fp32 kernel room for shadow row tiles where it walks layout-3 plans."""
+        ranges to it), or at the tile that leaves the exact-fp32 kernel room for shadow row tiles where it walks layout-3 plans.
+        ``plain`` (bipartite layers): as with ``merge_runs`` and ``dw_tiles`` off -- layout 0, relation-major d_weight kernels."""
         if self.xwide:
             raise NotImplementedError("RGCNConv wider than 128 runs on one GPU only: no dist layout")
         if self.aggr == "max":
             raise NotImplementedError("RGCNConv(aggr='max') runs on one GPU only: a dist context is not supported")
         tile, chunk = layout_for(self.in_channels, self.out_channels, n_nodes, n_edges, self.num_relations)
         # the tile-major weight-gradient kernel: 64 x 64 layers with few relations on graphs large enough to fill it
-        dw_rule = self.dw_tiles and self._w64 and self.num_relations <= 32 and n_edges >= DW_TILES_MIN_EDGES
+        dw_rule = self.dw_tiles and not plain and self._w64 and self.num_relations <= 32 and n_edges >= DW_TILES_MIN_EDGES
         exact_merge = False
         if self._use_split_producers(128):
             # the bf16 x 3 kernel's own layout (128-slot chunks, tiles up to 224, its own cycles per chunk and row tile) against the
@@ -950,14 +1068,20 @@ class RGCNConv(nn.Module):
     def forward(self, x: Tensor, edge_index: Tensor, edge_type: Optional[Tensor] = None, *,
                 _activation: Optional[str] = None, _input_relu: bool = False,
                 _grad_premasked: bool = False) -> Tensor:
-        """PyG's ``forward(x, edge_index, edge_type)``.  The keyword-only arguments are the private hook the model
+        """PyG's ``forward(x, edge_index, edge_type)``; ``x`` a ``(x_src, x_dst)`` pair: the bipartite layer (class docstring).
+        The keyword-only arguments are the private hook the model
         wrappers use to fuse the activations either side of the layer (layers._RGCNStack._tail):
         ``_activation`` ('relu' | 'sigmoid') is applied in the forward kernel's store; ``_input_relu`` says x is the
         ReLU output of the previous layer, so the dX kernel stores dL/dz_prev = dX * (x > 0); ``_grad_premasked`` says
         every consumer of THIS layer's ReLU output does that, so no ReLU backward runs here."""
         assert edge_type is not None, "edge_type is required (PyG RGCNConv asserts the same)"
+        if isinstance(x, (tuple, list)):
+            return self._forward_bipartite(x, edge_index, edge_type, _activation, _input_relu, _grad_premasked)
         if self.featureless:
             return self._forward_featureless(x, edge_index, edge_type)
+        if self.in_channels_r != self.in_channels:
+            raise ValueError(f"this RGCNConv was built with in_channels=({self.in_channels}, {self.in_channels_r}): "
+                             f"x must be a (x_src, x_dst) pair")
         if x is None or not torch.is_floating_point(x):
             raise NotImplementedError("featureless (integer / None x) RGCNConv is never used by the reference "
                                       "(x is always float: model/layers.py:21,62,108) and is not built")
@@ -1008,6 +1132,67 @@ class RGCNConv(nn.Module):
         flags = self.kernel_flags | (_lib.FLAG_SPLIT_PRODUCERS if self.split_producers and self._w64 else 0)
         return _MaxLayerFn.apply(x, self.weight, self.comp, self.root, self.bias, mp, act, bool(input_relu), premasked, int(flags), r,
                                  self.out_channels)
+
+    def _forward_bipartite(self, x, edge_index: Tensor, edge_type: Tensor, activation: Optional[str], input_relu: bool,
+                           grad_premasked: bool) -> Tensor:
+        """``x = (x_src [N_src, in_src], x_dst [N_dst, in_dst])``, ``edge_index[0] < N_src``, ``edge_index[1] < N_dst`` ->
+        ``[N_dst, out]`` (_BipartiteFn).  Every refusal comes before a plan is built."""
+        if self.featureless:
+            raise NotImplementedError("featureless RGCNConv takes x = None or node indices: a (x_src, x_dst) pair is not built")
+        if self.aggr == "max":
+            raise NotImplementedError("bipartite RGCNConv aggregates by mean / sum only: aggr='max' is not built")
+        if self.xwide:
+            raise NotImplementedError(f"bipartite RGCNConv takes 1..{NARROW_MAX_WIDTH} features per side (wide layers are homogeneous)")
+        if self.dist is not None:
+            raise NotImplementedError("bipartite RGCNConv runs on one GPU: a dist context is not supported")
+        if activation is not None or input_relu or grad_premasked:
+            raise ValueError("bipartite RGCNConv fuses no activation: _activation / _input_relu / _grad_premasked must be unset")
+        if len(x) != 2:
+            raise ValueError(f"x must be a (x_src, x_dst) pair, got {len(x)} members")
+        x_src, x_dst = x
+        for t in (x_src, x_dst):
+            if not isinstance(t, Tensor) or not torch.is_floating_point(t):
+                raise NotImplementedError("bipartite RGCNConv takes float features on both sides (no None / integer member)")
+        if x_src.dim() != 2 or x_src.shape[1] != self.in_channels:
+            raise ValueError(f"x_src must be [N_src, {self.in_channels}], got {tuple(x_src.shape)}")
+        if x_dst.dim() != 2 or x_dst.shape[1] != self.in_channels_r:
+            raise ValueError(f"x_dst must be [N_dst, {self.in_channels_r}], got {tuple(x_dst.shape)}")
+        if x_src.dtype != torch.float32 or x_dst.dtype != torch.float32:
+            raise ValueError(f"x_src and x_dst must be float32, got {x_src.dtype} and {x_dst.dtype}")
+        if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_type.dim() != 1 or edge_index.shape[1] != edge_type.shape[0]:
+            raise ValueError(f"edge_index must be [2, E] and edge_type [E], got {tuple(edge_index.shape)} and {tuple(edge_type.shape)}")
+        _require_gpu(x_src, x_dst)
+        dev = x_src.device
+        if x_dst.device != dev or edge_index.device != dev or edge_type.device != dev:
+            # (the plan is built where the edges live: a CPU plan's index arrays must never reach a kernel)
+            raise RuntimeError(f"bipartite RGCNConv: x_dst ({x_dst.device}), edge_index ({edge_index.device}) and edge_type "
+                               f"({edge_type.device}) must be on the device of x_src ({dev})")
+        _lib.load()
+        n_src, n_dst, e, r = int(x_src.shape[0]), int(x_dst.shape[0]), int(edge_type.shape[0]), self.num_relations
+        n = max(n_src, n_dst)
+        if e and min(n_src, n_dst) == 0:
+            raise ValueError(f"edge_index out of range: {e} edges between {n_src} source and {n_dst} destination nodes")
+        plans, flags = None, self.kernel_flags
+        if n_dst > 0:
+            # the plans of a homogeneous in_src -> out layer on N = max(N_src, N_dst) nodes that owns the rows [0, N_dst) forward
+            # and [0, N_src) transposed -- what a rank of a partitioned layer builds (DESIGN.md 12)
+            route = self._route(n, e, True, plain=True)
+
+            def build(paths):
+                # the builder checks every id against N only: the side ranges here, one reduction, on a cache miss only
+                if e:
+                    top = edge_index.amax(dim=1).tolist()
+                    if top[0] >= n_src or top[1] >= n_dst:
+                        raise ValueError(f"edge_index out of range: sources must lie in [0, {n_src}), destinations in [0, {n_dst}) "
+                                         f"(largest: {top[0]}, {top[1]})")
+                return build_graph_plans(edge_index, edge_type, n, r, route.tile, self.aggr, fwd_range=(0, n_dst),
+                                         bwd_range=(0, n_src or n), chunk=route.chunk, paths=paths)
+
+            plans = cached_graph_plans(edge_index, edge_type, n, r, route.tile, self.aggr, builder=build,
+                                       extra_key=("bipartite", n_src, n_dst), chunk=route.chunk, paths=route.paths,
+                                       widths=(self.in_channels, self.out_channels))
+            flags |= _lib.FLAG_SPLIT_PRODUCERS if route.split_producers else 0
+        return _BipartiteFn.apply(x_src, x_dst, self.weight, self.comp, self.root, self.bias, plans, int(flags), r, self.out_channels)
 
     def _forward_featureless(self, x: Optional[Tensor], edge_index: Tensor, edge_type: Tensor) -> Tensor:
         if self.dist is not None:
