@@ -100,6 +100,10 @@ typedef struct rgcn_plan {
                             * 5 (chunk = 64; the plan rgcn_bwd_dw_tiles walks): layout 0 with PAIRS of rows of one (destination, relation,
                             * weight) on one slot in the (tile, relation) groups of at most two chunks, see slot_src2; n_units / rel_order
                             * hold the units that are left (its rgcn_plan_build_finish synchronises the stream to count them);
+                            * the heads of one relation inside one of rgcn_dw_tiles_geometry's tile ranges are then packed densely
+                            * across tile boundaries: a unit may hold rows of chunk_tile (its earliest row's tile) AND of the tile
+                            * after it, chunk_flags bit 28 / 29: half 0 / half 1 (slots 0..31 / 32..63) holds rows of both, bit 30:
+                            * half 1 holds rows of the later tile only and half 0 of the earlier only (all three 0: one tile);
                             * rgcn_bwd_dw, rgcn_fwd and rgcn_bwd_dx answer RGCN_ERR_PLAN.
                             * Any other value, and layouts 1 / 3 with 64-slot chunks, is refused by every entry point (RGCN_ERR_PLAN) */
     int32_t chunk_rows;    /* rows a chunk may hold: = chunk, or 112 (chunk = 128: seven row tiles of rows, the eighth free for shadow
@@ -113,7 +117,7 @@ typedef struct rgcn_plan {
                                 * padding slots sit at the end of every row tile */
     const int32_t* chunk_tile; /* [n_chunks] */
     const int32_t* chunk_flags; /* [n_chunks] bit t: row tile t holds a repeated destination (needs the run-sum); layout 1: bit 8;
-                                 * layout 3: bits 16-19, see `layout` */
+                                 * layout 3: bits 16-19, layout 5: bits 28-30, see `layout` */
     const int32_t* rel_order;  /* [n_units] the weight-gradient walk: non-empty 64-slot units (unit u = slots
                                 * [64 u, 64 u + 64), chunk u / (chunk / 64)) sorted by (relation, tile) */
     const int32_t* slot_src;   /* [n_chunks * chunk] row to gather; padding = n_nodes (one past the last row) */

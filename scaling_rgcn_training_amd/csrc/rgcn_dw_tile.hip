@@ -20,6 +20,9 @@ namespace rgcn {
 // 64-slot units of (tile, its relation) -- a contiguous stretch of rel_order -- loading x rows straight from global
 // memory into registers half a unit ahead (rgcn_dw_direct_kernel's pipeline) and reading the gradient rows from LDS.
 // Traffic: x gathers E * 4 * in + four sweeps of g (4 N * 4 * out) + indices = 37 GB instead of 55; one barrier per tile.
+// On a PACKED plan (layout 5, rgcn_plan.hip dw_pack_kernel) a unit holds rows of chunk_tile and of the tile after it: the walk is
+// driven by the units, and a wave steps to the next tile -- wait for its DMAs, barrier, DMAs of the tile after -- where the unit's
+// chunk_flags say, in front of a half or in the middle of one (step_tile, gather_g / merge_g below).
 // The root relation and the bias gradient stay with rgcn_dw_direct_kernel (RGCN_FLAG_DW_ROOT_ONLY): their x rows are
 // the tile's own.
 // The split form raises its wave priority around the MFMA block of the output-column groups.  Two waves share a SIMD and
@@ -50,6 +53,7 @@ struct DwTileArgs {
     const int* rel_order;   // of a plan with tile = kDwTileT, 64-slot chunks (unit == chunk), layout 0
     const int* chunk_cnt;
     const int* chunk_tile;
+    const int* chunk_flags; // bits 28-30: which halves of a packed unit hold rows of chunk_tile + 1 (rgcn_plan.hip dw_pack_kernel)
     const int* slot_src;
     const float* slot_w;
     const int* slot_row;
@@ -134,22 +138,35 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
         for (int s = 0; s < HS; ++s)
             a4[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(__umul24((unsigned)ih[s], rbx) + colb), 0, 0));
     };
-    // half a unit: 8 k-steps of 4 rows; gradient rows from the LDS tile (row ids local to the tile, padding clamped: its
-    // weight is 0 and every LDS word is a finite number)
-    // nks (the unit's 4-row k-steps) is not used; dropping the argument reschedules the exact-fp32 kernels slightly, so it goes
-    // in a change that is measured on its own
-    auto compute_half = [&](f32x4 (&a4)[HS], const f32x4& pair, const Idx& ix, int h, int ngrp, int nks, const float* gbuf, int tile_row0) {
-        if constexpr (PAIRS) a4[0] += pair;
+    // the gradient rows and weights of half h's slots, in the lane geometry of the products (register s of lane (kq, ml): slot
+    // 32 h + 4 s + kq, columns 4 ml ..), from the LDS tile that starts at row tile_row0 (row ids local to the tile, padding clamped:
+    // its weight is 0 and every LDS word is a finite number)
+    auto gather_g = [&](f32x4 (&g4)[HS], float (&wv)[HS], const Idx& ix, int h, const float* gbuf, int tile_row0) {
         const unsigned loc = (unsigned)(ix.g - tile_row0);
         const int goff = (int)((loc < (unsigned)T ? loc : (unsigned)(T - 1)) * (unsigned)(NP * 4));    // byte offset of this lane's slot row
-        float wv[HS];
-        f32x4 g4[HS];
 #pragma unroll
         for (int s = 0; s < HS; ++s) {
             wv[s] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), __builtin_bit_cast(int, ix.w)));
             const int o = __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), goff);
             g4[s] = *(const f32x4*)((const char*)gbuf + o + colb);
         }
+    };
+    // a half that STRADDLES two tiles (a packed plan, rgcn_plan.hip dw_pack_kernel): gather_g on the earlier tile before the tile
+    // barrier (the later tile's slots read its last row: finite, replaced here), this on the later tile after it
+    auto merge_g = [&](f32x4 (&g4)[HS], const Idx& ix, int h, const float* gbuf, int tile_row0) {
+        const unsigned loc = (unsigned)(ix.g - tile_row0);
+        const int goff = loc < (unsigned)T ? (int)(loc * (unsigned)(NP * 4)) : -1;
+#pragma unroll
+        for (int s = 0; s < HS; ++s) {
+            const int o = __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), goff);
+            if (o >= 0) g4[s] = *(const f32x4*)((const char*)gbuf + o + colb);
+        }
+    };
+    // half a unit: 8 k-steps of 4 rows
+    // nks (the unit's 4-row k-steps) is not used; dropping the argument reschedules the exact-fp32 kernels slightly, so it goes
+    // in a change that is measured on its own
+    auto compute_half = [&](f32x4 (&a4)[HS], const f32x4& pair, const f32x4 (&g4)[HS], const float (&wv)[HS], int h, int ngrp, int nks) {
+        if constexpr (PAIRS) a4[0] += pair;
 #pragma unroll
         for (int gi = 0; gi < 2; ++gi) {
             if (2 * h + gi < ngrp) {
@@ -170,20 +187,9 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
         }
     };
 
-    // half a unit as ONE 32-row k-step (a half with no valid slot is skipped; padding slots inside one have weight 0)
-    auto compute_half3 = [&](f32x4 (&a4)[HS], const f32x4& pair, const Idx& ix, int h, int ngrp, const float* gbuf, int tile_row0) {
-        if (2 * h >= ngrp) return;      // (ix.w carries the period's sign, see fold_into_slab)
-        if constexpr (PAIRS) a4[0] += pair;
-        const unsigned loc = (unsigned)(ix.g - tile_row0);
-        const int goff = (int)((loc < (unsigned)T ? loc : (unsigned)(T - 1)) * (unsigned)(NP * 4));
-        float wv[HS];
-        f32x4 g4[HS];
-#pragma unroll
-        for (int s = 0; s < HS; ++s) {
-            wv[s] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), __builtin_bit_cast(int, ix.w)));
-            const int o = __builtin_amdgcn_ds_bpermute(perm + 16 * (HS * h + s), goff);
-            g4[s] = *(const f32x4*)((const char*)gbuf + o + colb);
-        }
+    // half a unit as ONE 32-row k-step (a half with no valid slot is skipped by the walk; padding slots inside one have weight 0)
+    auto compute_half3 = [&](f32x4 (&a4)[HS], const f32x4& pair, const f32x4 (&g4)[HS], const float (&wv)[HS]) {
+        if constexpr (PAIRS) a4[0] += pair;      // (the weights carry the period's sign, see fold_into_slab)
         u32x4 ap[3][4];      // [piece][ia]: 8 bf16 = k index 8 kq + 0..7 of input channel 4 ml + ia
         // the four pairs of an input channel cut side by side, stage by stage (split3_pair's arithmetic, same pieces): left
         // alone the scheduler emits one dependent chain after the other with a wait state behind every conversion
@@ -309,60 +315,97 @@ __global__ void __launch_bounds__(512, 2) rgcn_dw_tile_kernel(const DwTileArgs a
     dma_tile(t0, 0);
     int k = 0;
     int uid_cur = unit_of(0), uid_nxt = unit_of(1), uid_nn = unit_of(2);
-    int cnt_cur = ldc(a.chunk_cnt, uid_cur), tile_cur = nun > 0 ? ldc(a.chunk_tile, uid_cur) : t1;
-    int cnt_nxt = ldc(a.chunk_cnt, uid_nxt), tile_nxt = nun > 1 ? ldc(a.chunk_tile, uid_nxt) : t1;
+    int cnt_cur = ldc(a.chunk_cnt, uid_cur), tile_cur = nun > 0 ? ldc(a.chunk_tile, uid_cur) : t1, flg_cur = ldc(a.chunk_flags, uid_cur);
+    int cnt_nxt = ldc(a.chunk_cnt, uid_nxt), tile_nxt = nun > 1 ? ldc(a.chunk_tile, uid_nxt) : t1, flg_nxt = ldc(a.chunk_flags, uid_nxt);
     Idx ix_cur = load_idx(uid_cur), ix_nxt = load_idx(uid_nxt);
     f32x4 s0[HS], s1[HS];
     f32x4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = {0.f, 0.f, 0.f, 0.f};
     if (nun > 0) issue_half(s0, p0, ix_cur, 0);
-    constexpr int kInFlight = 11 + (PAIRS ? 2 : 0);      // 8 (+ 1) row loads + 3 (+ 1) index loads
-    bool walked = nun > 0;      // at least kInFlight vector-memory operations were issued after the pending tile's DMAs
-    for (int t = t0; t < t1; ++t) {
-        // The DMAs of tile t were issued a tile ago (or in the prologue).  If the wave has walked a unit since (or issued the
-        // prologue's loads), more than kInFlight younger operations exist and at most kInFlight are in flight at a unit boundary (8 row
-        // loads + 3 index loads of the unit after next): a counted wait retires the DMAs and leaves the prefetches alone.  A wave
-        // without units in between (an empty relation) has nothing younger to count: it waits for everything.
-        if (walked) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
+    constexpr int kHalfOps = 8 + (PAIRS ? 1 : 0), kIdxOps = 3 + (PAIRS ? 1 : 0);      // vector-memory operations of issue_half / load_idx
+    constexpr int kInFlight = kHalfOps + kIdxOps;      // 8 (+ 1) row loads + 3 (+ 1) index loads
+    // vector-memory operations this wave has issued since its DMAs of the tile that comes next (at least: a fold's are not counted)
+    int since = nun > 0 ? kHalfOps + 2 * kIdxOps : 0;
+    int t = t0 - 1;
+    const float* gbuf = lds;
+    // On to the next tile.  Its DMAs were issued a tile ago (or in the prologue).  Vector-memory operations retire in order, so a
+    // wait for all but the n youngest retires the DMAs whenever the wave has issued n operations since -- and leaves those n, its
+    // row and index prefetches, alone: kInFlight of them are in flight at a unit boundary (8 row loads + 3 index loads of the
+    // unit after next), a half's row loads more in the middle of a unit, where a packed plan steps.  A wave without units in
+    // between (an empty relation) has nothing younger to count: it waits for everything.
+    auto step_tile = [&] {
+        if (t + 1 >= t1) return;      // (only a plan that breaks its contract asks: no barrier that the other waves do not reach)
+        ++t;
+        if (since >= kInFlight + kHalfOps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight + kHalfOps) : "memory");
+        else if (since >= kInFlight) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kInFlight) : "memory");
+        else if (since >= kHalfOps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kHalfOps) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        wg_barrier();          // tile t landed for every wave; every wave is done with the buffer tile t + 1 goes to
+        wg_barrier();          // tile t landed for every wave; every wave is done with the buffer tile t + 1 goes to (its LDS reads retired)
         const int b = (t - t0) & 1;
         if (t + 1 < t1) dma_tile(t + 1, b ^ 1);
-        walked = false;
-        const float* gbuf = lds + b * T * NP;
-        while (k < nun && tile_cur == t) {
-            const int ngrp = (cnt_cur + 15) >> 4, nks = (cnt_cur + 3) >> 2;
-            walked = true;
-            issue_half(s1, p1, ix_cur, 1);
-            pin_loads();
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (SPLIT) ix_cur.w *= sgn;
-            if constexpr (SPLIT) compute_half3(s0, p0, ix_cur, 0, ngrp, gbuf, t * T);
-            else compute_half(s0, p0, ix_cur, 0, ngrp, nks, gbuf, t * T);
-            __builtin_amdgcn_sched_barrier(0);
-            const Idx ix_nn = load_idx(uid_nn);
-            issue_half(s0, p0, ix_nxt, 0);
-            pin_loads();
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (SPLIT) compute_half3(s1, p1, ix_cur, 1, ngrp, gbuf, t * T);
-            else compute_half(s1, p1, ix_cur, 1, ngrp, nks, gbuf, t * T);
-            __builtin_amdgcn_sched_barrier(0);
-            ++k;
-            if (--fold_left == 0) {      // wave-uniform
-                fold_left = fold_period;
-                fold_into_slab(sgn);
-                if (SPLIT) sgn = -sgn;
+        since = 0;
+        gbuf = lds + b * T * NP;
+    };
+    // Units of a packed plan hold rows of chunk_tile and of the tile after it (chunk_flags).  A half that straddles reads its rows
+    // of the earlier tile into registers, steps, and reads the others from the buffer that landed; a half that lies in the later
+    // tile steps first.  Every wave of the workgroup steps t1 - t0 times in all, wherever in its walk.
+    constexpr int kH0Straddles = 1 << 28, kH1Straddles = 1 << 29, kH1Next = 1 << 30;
+    while (k < nun) {
+        while (t < tile_cur && t + 1 < t1) step_tile();
+        const int ngrp = (cnt_cur + 15) >> 4, nks = (cnt_cur + 3) >> 2;
+        issue_half(s1, p1, ix_cur, 1);
+        since += kHalfOps;
+        pin_loads();
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SPLIT) ix_cur.w *= sgn;
+        if (!SPLIT || 0 < ngrp) {
+            float wv[HS];
+            f32x4 g4[HS];
+            gather_g(g4, wv, ix_cur, 0, gbuf, t * T);
+            if (flg_cur & kH0Straddles) {
+                step_tile();
+                merge_g(g4, ix_cur, 0, gbuf, t * T);
             }
-            ix_cur = ix_nxt;
-            ix_nxt = ix_nn;
-            uid_cur = uid_nxt;
-            uid_nxt = uid_nn;
-            uid_nn = unit_of(k + 2);
-            cnt_cur = cnt_nxt;
-            tile_cur = k < nun ? tile_nxt : t1;
-            cnt_nxt = ldc(a.chunk_cnt, uid_nxt);
-            tile_nxt = k + 1 < nun ? ldc(a.chunk_tile, uid_nxt) : t1;
+            if constexpr (SPLIT) compute_half3(s0, p0, g4, wv);
+            else compute_half(s0, p0, g4, wv, 0, ngrp, nks);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        const Idx ix_nn = load_idx(uid_nn);
+        issue_half(s0, p0, ix_nxt, 0);
+        since += kHalfOps + kIdxOps;
+        pin_loads();
+        __builtin_amdgcn_sched_barrier(0);
+        if (!SPLIT || 2 < ngrp) {
+            float wv[HS];
+            f32x4 g4[HS];
+            if (flg_cur & kH1Next) step_tile();
+            gather_g(g4, wv, ix_cur, 1, gbuf, t * T);
+            if (flg_cur & kH1Straddles) {
+                step_tile();
+                merge_g(g4, ix_cur, 1, gbuf, t * T);
+            }
+            if constexpr (SPLIT) compute_half3(s1, p1, g4, wv);
+            else compute_half(s1, p1, g4, wv, 1, ngrp, nks);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        ++k;
+        if (--fold_left == 0) {      // wave-uniform
+            fold_left = fold_period;
+            fold_into_slab(sgn);
+            if (SPLIT) sgn = -sgn;
+        }
+        ix_cur = ix_nxt;
+        ix_nxt = ix_nn;
+        uid_cur = uid_nxt;
+        uid_nxt = uid_nn;
+        uid_nn = unit_of(k + 2);
+        cnt_cur = cnt_nxt;
+        flg_cur = flg_nxt;
+        tile_cur = k < nun ? tile_nxt : t1;
+        cnt_nxt = ldc(a.chunk_cnt, uid_nxt);
+        flg_nxt = ldc(a.chunk_flags, uid_nxt);
+        tile_nxt = k + 1 < nun ? ldc(a.chunk_tile, uid_nxt) : t1;
     }
+    while (t + 1 < t1) step_tile();      // the tiles behind the wave's last unit: the other waves' barriers
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the accumulators are read by plain stores the compiler schedules: keep them clear of the last asm MFMA
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -446,6 +489,7 @@ extern "C" int rgcn_bwd_dw_tiles(const rgcn_plan_t* plan, const int32_t* walk_pt
     a.rel_order = plan->rel_order;
     a.chunk_cnt = plan->chunk_cnt;
     a.chunk_tile = plan->chunk_tile;
+    a.chunk_flags = plan->chunk_flags;
     a.slot_src = plan->slot_src;
     a.slot_w = plan->slot_w;
     a.slot_row = plan->slot_row;

@@ -738,6 +738,177 @@ __global__ void __launch_bounds__(kPairThreads) dw_pairs_kernel(u32 n_chunks, u3
     for (u32 i = 0; i < m; ++i) chunk_cnt[c + i] = i < U ? (int32_t)(((unit_heads(i) + 15u) / 16u) * 16u) : 0;
 }
 
+// Layout 5, second pass (plan.dw_pack is its twin; runs on the unit list built after dw_pairs_kernel, which is then built again):
+// dw_pairs_kernel leaves every (tile, relation) group with a last half that is 2/3 empty on average, and the tile-major kernel's
+// time goes with the halves it walks.  A STREAM = the units of one relation in the tiles of one walker range, the stretch of
+// rel_order ONE wave of rgcn_dw_tile_kernel walks.  Its heads are packed densely in tile order, 32 per half, 64 per unit, into the
+// storage of the stream's first units; a unit holds rows of at most two consecutive tiles, chunk_tile (its earliest row's) and the
+// next -- a head that would break that closes the unit with padding.  A half takes a consecutive stretch of the stream (so once a
+// half holds a row of the later tile, everything behind it in the unit does), its pair heads -- at most four, on its first slots --
+// first; a pair that meets four pairs in its half becomes two single rows.  chunk_flags of a packed unit = which halves straddle,
+// what the kernel needs to know before it reads the rows.  Units the stream no longer needs get chunk_cnt 0.  Streams of one tile
+// (every plan with fewer tiles than walkers) or one unit are left as they are, bit for bit.
+// One wave per stream: the lanes copy input unit i to LDS, lane 0 deals its heads.  In place: output unit j is written after input
+// unit i >= j was copied -- a pair only splits where a half that was not full left as many free slots (its pair run moved up into
+// a half that already has four), so the write position never passes the read position; s_bad guards the arrays regardless.
+// The walker ranges are found by binary search over chunk_tile while other waves rewrite it: a unit's tile stays inside its
+// walker range, and the searches only ask on which side of a range boundary a unit lies.
+constexpr u32 kDwWalkers = 64;                      // = rgcn_dw_tiles_geometry's walkers (rgcn_dw_tile.hip)
+constexpr int32_t kDwFlagH0Straddles = 1 << 28;     // half 0 holds rows of chunk_tile and of chunk_tile + 1
+constexpr int32_t kDwFlagH1Straddles = 1 << 29;     // half 1 does
+constexpr int32_t kDwFlagH1Next = 1 << 30;          // half 1 holds rows of chunk_tile + 1 only, half 0 rows of chunk_tile only
+__global__ void __launch_bounds__(64) dw_pack_kernel(const u32* __restrict__ n_units_ptr, u32 n_tiles, u32 walkers, u32 n_nodes, u32 n_own,
+                                                     const int32_t* __restrict__ rel_order, const int32_t* __restrict__ chunk_rel,
+                                                     int32_t* chunk_tile, int32_t* __restrict__ chunk_cnt, int32_t* __restrict__ chunk_flags,
+                                                     int32_t* __restrict__ slot_src, float* __restrict__ slot_w, int32_t* __restrict__ slot_row,
+                                                     int32_t* __restrict__ slot_src2) {
+    const u32 r = blockIdx.x / walkers, p = blockIdx.x % walkers;
+    const u32 t0 = (u32)((u64)p * n_tiles / walkers), t1 = (u32)((u64)(p + 1) * n_tiles / walkers);
+    if (t1 - t0 < 2u) return;
+    const u32 n_units = *n_units_ptr;
+    auto lower = [&](u32 tile) {
+        const u64 target = (u64)r * n_tiles + tile;
+        u32 lo = 0, hi = n_units;
+        while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            const int32_t c = rel_order[mid];
+            if ((u64)(u32)chunk_rel[c] * n_tiles + (u32)((volatile int32_t*)chunk_tile)[c] < target) lo = mid + 1; else hi = mid;
+        }
+        return lo;
+    };
+    const u32 i0 = lower(t0), n = lower(t1) - i0;
+    if (n < 2u) return;
+    __shared__ int32_t i_src[64], i_row[64], i_s2[8], q_src[32], q_row[32], p_src[4], p_row[4], p_s2[4];
+    __shared__ u32 i_w[64], q_w[32], p_w[4], s_j, s_bad;
+    const u32 lane = threadIdx.x;
+    // lane 0: the open output unit j (stored where the stream's j-th unit was), its half hh with np pairs and ns single rows so far
+    u32 j = 0, hh = 0, np = 0, ns = 0, cur_i = 0, n_half[2] = {0u, 0u}, tmask = 0;   // tmask bit 2 hh + d: half hh holds a row of tile ut + d
+    bool open = false, bad = false;
+    int32_t ut = 0;
+    auto pad_half = [&](u32 u, u32 h, u32 from) {
+        for (u32 q = from; q < 32u; ++q) {
+            const size_t g = (size_t)u * 64u + 32u * h + q;
+            slot_src[g] = (int32_t)n_nodes;
+            slot_w[g] = 0.f;
+            slot_row[g] = (int32_t)n_own;
+        }
+    };
+    auto close_unit = [&]() {      // (the open half is closed already)
+        const u32 u = (u32)rel_order[i0 + j];
+        if (hh == 1u) {
+            pad_half(u, 1u, 0u);
+            for (u32 q = 0; q < 4u; ++q) slot_src2[(size_t)u * 8u + 4u + q] = (int32_t)n_nodes;
+        }
+        const u32 used = n_half[1] ? 32u + n_half[1] : n_half[0];
+        chunk_cnt[u] = (int32_t)(((used + 15u) / 16u) * 16u);
+        chunk_tile[u] = ut;
+        const bool a0 = tmask & 1u, b0 = tmask & 2u, a1 = tmask & 4u, b1 = tmask & 8u;
+        chunk_flags[u] = (a0 && b0 ? kDwFlagH0Straddles : 0) | (a1 && b1 ? kDwFlagH1Straddles : 0) | (b1 && !a1 && !b0 ? kDwFlagH1Next : 0);
+        ++j;
+        open = false;
+    };
+    auto close_half = [&]() {
+        const u32 u = (u32)rel_order[i0 + j];
+        const size_t base = (size_t)u * 64u + 32u * hh;
+        for (u32 q = 0; q < 4u; ++q) {
+            if (q < np) {
+                slot_src[base + q] = p_src[q];
+                slot_w[base + q] = __uint_as_float(p_w[q]);
+                slot_row[base + q] = p_row[q];
+            }
+            slot_src2[(size_t)u * 8u + 4u * hh + q] = q < np ? p_s2[q] : (int32_t)n_nodes;
+        }
+        for (u32 q = 0; q < ns; ++q) {
+            slot_src[base + np + q] = q_src[q];
+            slot_w[base + np + q] = __uint_as_float(q_w[q]);
+            slot_row[base + np + q] = q_row[q];
+        }
+        pad_half(u, hh, np + ns);
+        n_half[hh] = np + ns;
+        np = ns = 0;
+        if (++hh == 2u) close_unit();
+    };
+    auto enter = [&](int32_t th) {      // the unit the next head of tile th goes to
+        if (open && th > ut + 1) {
+            if (np + ns > 0u) close_half();
+            if (open) close_unit();
+        }
+        if (!open) {
+            if (j > cur_i) { bad = true; return; }
+            open = true;
+            ut = th;
+            hh = 0;
+            n_half[0] = n_half[1] = 0;
+            tmask = 0;
+        }
+        tmask |= 1u << (2u * hh + (u32)(th - ut));
+    };
+    auto put_single = [&](int32_t s, int32_t rw, u32 w, int32_t th) {
+        enter(th);
+        if (bad) return;
+        q_src[ns] = s;
+        q_row[ns] = rw;
+        q_w[ns] = w;
+        ++ns;
+        if (np + ns == 32u) close_half();
+    };
+    for (u32 i = 0; i < n; ++i) {
+        const u32 u = (u32)rel_order[i0 + i];
+        const int32_t ti = chunk_tile[u];
+        i_src[lane] = slot_src[(size_t)u * 64u + lane];
+        i_row[lane] = slot_row[(size_t)u * 64u + lane];
+        i_w[lane] = __float_as_uint(slot_w[(size_t)u * 64u + lane]);
+        if (lane < 8u) i_s2[lane] = slot_src2[(size_t)u * 8u + lane];
+        __syncthreads();
+        if (lane == 0u) {
+            cur_i = i;
+            for (u32 s = 0; s < 64u && !bad; ++s) {
+                const int32_t sv = i_src[s];
+                if ((u32)sv == n_nodes) continue;
+                const int32_t rw = i_row[s];
+                const u32 w = i_w[s];
+                const int32_t s2 = s < 4u ? i_s2[s] : (s >= 32u && s < 36u ? i_s2[s - 28u] : (int32_t)n_nodes);
+                if ((u32)s2 == n_nodes) {
+                    put_single(sv, rw, w, ti);
+                    continue;
+                }
+                enter(ti);
+                if (bad) break;
+                if (np == 4u) {      // no pair place left in this half: two single rows
+                    put_single(sv, rw, w, ti);
+                    put_single(s2, rw, w, ti);
+                    continue;
+                }
+                p_src[np] = sv;
+                p_row[np] = rw;
+                p_w[np] = w;
+                p_s2[np] = s2;
+                ++np;
+                if (np + ns == 32u) close_half();
+            }
+            if (i + 1u == n && !bad && open) {
+                if (np + ns > 0u) close_half();
+                if (open) close_unit();
+            }
+            s_j = j;
+            s_bad = bad ? 1u : 0u;
+        }
+        __syncthreads();
+        if (s_bad) return;
+    }
+    for (u32 jj = s_j; jj < n; ++jj) {      // the units the stream no longer needs
+        const u32 u = (u32)rel_order[i0 + jj];
+        slot_src[(size_t)u * 64u + lane] = (int32_t)n_nodes;
+        slot_w[(size_t)u * 64u + lane] = 0.f;
+        slot_row[(size_t)u * 64u + lane] = (int32_t)n_own;
+        if (lane < 8u) slot_src2[(size_t)u * 8u + lane] = (int32_t)n_nodes;
+        if (lane == 0u) {
+            chunk_cnt[u] = 0;
+            chunk_flags[u] = 0;
+        }
+    }
+}
+
 __global__ void fill_i32_kernel(int32_t* __restrict__ p, u64 n, int32_t v) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -1088,7 +1259,16 @@ extern "C" int rgcn_plan_build_finish(const rgcn_plan_sizes_t* sizes, void* work
     exclusive_scan(ucnt, ucnt, bs.n_chunks, ws.sb.sums, s);
     hipLaunchKernelGGL(emit_units_kernel, dim3(grid_for(bs.n_chunks)), dim3(256), 0, s, cb.v[cur], chunk_cnt, ucnt, bs.n_chunks,
                        bs.chunk / 64u, (int32_t*)plan->rel_order);
-    if (bs.layout == 3)      // last: the unit list above is layout 0's (nothing walks it on a layout-3 plan)
+    if (bs.layout == 5 && bs.num_rel > 0) {      // pack every stream of that unit list, then list the units that are left
+        hipLaunchKernelGGL(dw_pack_kernel, dim3(bs.num_rel * kDwWalkers), dim3(64), 0, s, ws.sb.sums + scan_blocks(bs.n_chunks), n_tiles,
+                           kDwWalkers, bs.n_nodes, bs.n_own, (const int32_t*)plan->rel_order, chunk_rel, chunk_tile, chunk_cnt, chunk_flags,
+                           slot_src, slot_w, slot_row, (int32_t*)plan->slot_src2);
+        hipLaunchKernelGGL(unit_counts_kernel, dim3(grid_for(bs.n_chunks)), dim3(256), 0, s, cb.v[cur], chunk_cnt, bs.n_chunks, ucnt);
+        exclusive_scan(ucnt, ucnt, bs.n_chunks, ws.sb.sums, s);
+        hipLaunchKernelGGL(emit_units_kernel, dim3(grid_for(bs.n_chunks)), dim3(256), 0, s, cb.v[cur], chunk_cnt, ucnt, bs.n_chunks,
+                           bs.chunk / 64u, (int32_t*)plan->rel_order);
+    }
+    if (bs.layout == 3)     // last: the unit list above is layout 0's (nothing walks it on a layout-3 plan)
         hipLaunchKernelGGL(compact_runs_kernel, dim3(grid_for(bs.n_chunks, kCompactThreads)), dim3(kCompactThreads), 0, s, bs.n_chunks, bs.n_nodes, bs.tile, bs.n_own,
                            chunk_rel, chunk_tile, chunk_cnt, chunk_flags, slot_src, slot_w, slot_row, slot_acc);
     plan->n_nodes = (int32_t)bs.n_nodes;

@@ -65,6 +65,7 @@ class TilePlan:
     chunk_cnt: Tensor     # int32 [n_chunks]
     chunk_tile: Tensor    # int32 [n_chunks]
     chunk_flags: Tensor   # int32 [n_chunks]  bit t: MFMA row tile t of the chunk holds a repeated destination
+                          # (layout 5: bits 28-30 = which halves of a packed unit hold rows of chunk_tile + 1, see dw_pack)
     rel_order: Tensor     # int32 [n_units]  non-empty 64-row units (unit u = rows [64 u, 64 u + 64) of the slot
                           #   arrays, chunk u // (chunk // 64)), relation-major then tile: the dW kernels' walk
     slot_src: Tensor      # int32 [n_chunks * chunk]
@@ -136,7 +137,7 @@ def build_plan(gather: Tensor, scatter: Tensor, rel: Tensor, w: Tensor, n_nodes:
     if int(split) == 5:
         if chunk != 64:
             raise ValueError("layout 5 (pairs on one slot: the tile-major weight-gradient plan) needs 64-slot chunks")
-        return dw_pairs(build_plan(gather, scatter, rel, w, n_nodes, num_relations, tile, node_begin, node_end, chunk, False))
+        return dw_pack(dw_pairs(build_plan(gather, scatter, rel, w, n_nodes, num_relations, tile, node_begin, node_end, chunk, False)))
     if split and chunk != 128:
         raise ValueError("the team placement and the run compaction need 128-slot chunks")
     if int(split) == 3:
@@ -487,6 +488,137 @@ def dw_pairs(plan: TilePlan) -> TilePlan:
     used = plan.chunk_cnt.to(torch.int64)[chunk_order] > 0
     plan.rel_order = chunk_order[used].to(torch.int32)
     plan.layout = 5
+    return plan
+
+
+DW_WALKERS = 64             # tile ranges of the tile-major weight-gradient kernel (rgcn_dw_tiles_geometry reports the same number)
+DW_FLAG_H0_STRADDLES = 1 << 28      # chunk_flags of a packed unit: half 0 holds rows of chunk_tile AND of chunk_tile + 1
+DW_FLAG_H1_STRADDLES = 1 << 29      # ... half 1 does
+DW_FLAG_H1_NEXT = 1 << 30           # half 1 holds rows of chunk_tile + 1 only, half 0 rows of chunk_tile only
+
+
+def dw_pack(plan: TilePlan, walkers: int = DW_WALKERS) -> TilePlan:
+    """Twin of ``dw_pack_kernel`` (csrc/rgcn_plan.hip), the pass after ``dw_pairs``: the heads of a STREAM -- the units of one relation
+    in the tiles of one walker range ``[p * n_tiles // walkers, (p + 1) * n_tiles // walkers)``, the stretch of ``rel_order`` one wave
+    of the kernel walks -- are packed densely in tile order, 32 per half, 64 per unit, into the storage of the stream's first
+    units.  A unit holds rows of at most two consecutive tiles, ``chunk_tile`` (its earliest row's) and the next; a head that would
+    break that closes the unit with padding.  A half takes a consecutive stretch of the stream, its pair heads (at most four, on the
+    half's first slots) first; a pair that meets four pairs in its half becomes two single rows.  ``chunk_flags`` of a packed unit =
+    which of its halves straddle (DW_FLAG_*).  Units the stream no longer needs get ``chunk_cnt`` 0 and leave ``rel_order``.
+    Streams of one tile (every plan of fewer tiles than walkers) or of one unit stay as ``dw_pairs`` left them.
+    In place: output unit j is written when input unit i >= j has been read -- a pair only splits where a short half left room."""
+    if plan.chunk != 64 or plan.layout != 5:
+        raise ValueError("dw_pack wants a layout-5 plan")
+    dev = plan.slot_src.device
+    n_nodes, n_own, n_tiles = plan.n_nodes, plan.n_owned, plan.n_tiles
+    src = plan.slot_src.cpu().numpy().copy()
+    wbits = plan.slot_w.cpu().numpy().copy().view("uint32")
+    row = plan.slot_row.cpu().numpy().copy()
+    src2 = plan.slot_src2.cpu().numpy().copy()
+    cnt = plan.chunk_cnt.cpu().numpy().copy()
+    ctile = plan.chunk_tile.cpu().numpy().copy()
+    flags = plan.chunk_flags.cpu().numpy().copy()
+    crel = plan.chunk_rel.cpu().numpy()
+    order = plan.rel_order.cpu().numpy().astype(np.int64)
+    key = crel.astype(np.int64)[order] * max(n_tiles, 1) + ctile.astype(np.int64)[order]
+
+    def pack_stream(units):
+        # state of the output: unit j, half hh with its pairs / singles so far, the tiles its halves hold
+        st = {"j": 0, "open": False, "ut": 0, "hh": 0, "n": [0, 0], "t1": [[False, False], [False, False]]}
+        pairs, singles = [], []
+        o_src, o_row, o_w, o_s2 = [None], [None], [None], [None]
+
+        def open_unit(th):
+            st.update(open=True, ut=th, hh=0, n=[0, 0], t1=[[False, False], [False, False]])
+            o_src[0] = np.full(64, n_nodes, np.int32)
+            o_row[0] = np.full(64, n_own, np.int32)
+            o_w[0] = np.zeros(64, np.uint32)
+            o_s2[0] = np.full(8, n_nodes, np.int32)
+
+        def close_half():
+            hh, b = st["hh"], 32 * st["hh"]
+            for q, (s_, r_, w_, s2_) in enumerate(pairs):
+                o_src[0][b + q], o_row[0][b + q], o_w[0][b + q], o_s2[0][4 * hh + q] = s_, r_, w_, s2_
+            for q, (s_, r_, w_) in enumerate(singles):
+                o_src[0][b + len(pairs) + q], o_row[0][b + len(pairs) + q], o_w[0][b + len(pairs) + q] = s_, r_, w_
+            st["n"][hh] = len(pairs) + len(singles)
+            pairs.clear()
+            singles.clear()
+            st["hh"] = hh + 1
+            if hh == 1:
+                close_unit()
+
+        def close_unit():
+            if pairs or singles:
+                close_half()
+                if not st["open"]:
+                    return
+            u = units[st["j"]]
+            assert st["j"] <= st["i"], "dw_pack: output overtook input"
+            n0, n1 = st["n"]
+            src[64 * u:64 * u + 64], row[64 * u:64 * u + 64], wbits[64 * u:64 * u + 64] = o_src[0], o_row[0], o_w[0]
+            src2[8 * u:8 * u + 8] = o_s2[0]
+            cnt[u] = ((32 + n1 if n1 else n0) + 15) // 16 * 16
+            ctile[u] = st["ut"]
+            (a0, b0), (a1, b1) = st["t1"]
+            flags[u] = ((DW_FLAG_H0_STRADDLES if a0 and b0 else 0) | (DW_FLAG_H1_STRADDLES if a1 and b1 else 0)
+                        | (DW_FLAG_H1_NEXT if b1 and not a1 and not b0 else 0))
+            st["j"] += 1
+            st["open"] = False
+
+        def put(s_, r_, w_, s2_, th):
+            if st["open"] and th > st["ut"] + 1:
+                close_unit()
+            if not st["open"]:
+                open_unit(th)
+            if s2_ is not None and len(pairs) == 4:      # no pair place left in this half: two single rows
+                put(s_, r_, w_, None, th)
+                put(s2_, r_, w_, None, th)
+                return
+            st["t1"][st["hh"]][th - st["ut"]] = True
+            if s2_ is not None:
+                pairs.append((s_, r_, w_, s2_))
+            else:
+                singles.append((s_, r_, w_))
+            if len(pairs) + len(singles) == 32:
+                close_half()
+
+        for i, u in enumerate(units):
+            st["i"] = i
+            i_src, i_row, i_w = src[64 * u:64 * u + 64].copy(), row[64 * u:64 * u + 64].copy(), wbits[64 * u:64 * u + 64].copy()
+            i_s2, ti = src2[8 * u:8 * u + 8].copy(), int(ctile[u])
+            for s in range(64):
+                if i_src[s] == n_nodes:
+                    continue
+                k = s if s < 4 else (s - 28 if 32 <= s < 36 else -1)
+                put(i_src[s], i_row[s], i_w[s], int(i_s2[k]) if k >= 0 and i_s2[k] != n_nodes else None, ti)
+        st["i"] = len(units)
+        if st["open"]:
+            close_unit()
+        for jj in range(st["j"], len(units)):
+            u = units[jj]
+            src[64 * u:64 * u + 64], row[64 * u:64 * u + 64], wbits[64 * u:64 * u + 64] = n_nodes, n_own, 0
+            src2[8 * u:8 * u + 8] = n_nodes
+            cnt[u], flags[u] = 0, 0
+
+    for r in range(plan.num_relations):
+        for p in range(walkers):
+            t0, t1 = p * n_tiles // walkers, (p + 1) * n_tiles // walkers
+            if t1 - t0 < 2:
+                continue
+            i0, i1 = np.searchsorted(key, [r * n_tiles + t0, r * n_tiles + t1])
+            if i1 - i0 >= 2:
+                pack_stream(order[i0:i1])
+    plan.slot_src = torch.from_numpy(src).to(dev)
+    plan.slot_w = torch.from_numpy(wbits.view("float32")).to(dev)
+    plan.slot_row = torch.from_numpy(row).to(dev)
+    plan.slot_src2 = torch.from_numpy(src2).to(dev)
+    plan.chunk_cnt = torch.from_numpy(cnt).to(dev)
+    plan.chunk_tile = torch.from_numpy(ctile).to(dev)
+    plan.chunk_flags = torch.from_numpy(flags).to(dev)
+    chunk_order = torch.sort(plan.chunk_rel.to(torch.int64), stable=True)[1]      # stable: a relation's units in tile order
+    used = plan.chunk_cnt.to(torch.int64)[chunk_order] > 0
+    plan.rel_order = chunk_order[used].to(torch.int32)
     return plan
 
 
