@@ -1174,25 +1174,33 @@ class RGCNConv(nn.Module):
             raise ValueError(f"edge_index out of range: {e} edges between {n_src} source and {n_dst} destination nodes")
         plans, flags = None, self.kernel_flags
         if n_dst > 0:
-            # the plans of a homogeneous in_src -> out layer on N = max(N_src, N_dst) nodes that owns the rows [0, N_dst) forward
-            # and [0, N_src) transposed -- what a rank of a partitioned layer builds
             route = self._route(n, e, True, plain=True)
-
-            def build(paths):
-                # the builder checks every id against N only: the side ranges here, one reduction, on a cache miss only
-                if e:
-                    top = edge_index.amax(dim=1).tolist()
-                    if top[0] >= n_src or top[1] >= n_dst:
-                        raise ValueError(f"edge_index out of range: sources must lie in [0, {n_src}), destinations in [0, {n_dst}) "
-                                         f"(largest: {top[0]}, {top[1]})")
-                return build_graph_plans(edge_index, edge_type, n, r, route.tile, self.aggr, fwd_range=(0, n_dst),
-                                         bwd_range=(0, n_src or n), chunk=route.chunk, paths=paths)
-
-            plans = cached_graph_plans(edge_index, edge_type, n, r, route.tile, self.aggr, builder=build,
-                                       extra_key=("bipartite", n_src, n_dst), chunk=route.chunk, paths=route.paths,
-                                       widths=(self.in_channels, self.out_channels))
+            plans = self._bipartite_plans(edge_index, edge_type, n_src, n_dst, route)
             flags |= _lib.FLAG_SPLIT_PRODUCERS if route.split_producers else 0
         return _BipartiteFn.apply(x_src, x_dst, self.weight, self.comp, self.root, self.bias, plans, int(flags), r, self.out_channels)
+
+    def _bipartite_plans(self, edge_index: Tensor, edge_type: Tensor, n_src: int, n_dst: int,
+                         route: Optional["_Route"] = None) -> GraphPlans:
+        """the (cached) plans of a bipartite call with N_dst > 0: those of a homogeneous in_src -> out layer on N = max(N_src,
+        N_dst) nodes that owns the rows [0, N_dst) forward and [0, N_src) transposed -- what a rank of a partitioned layer builds
+        """
+        e, r = int(edge_type.shape[0]), self.num_relations
+        n = max(n_src, n_dst)
+        route = self._route(n, e, True, plain=True) if route is None else route
+
+        def build(paths):
+            # the builder checks every id against N only: the side ranges here, one reduction, on a cache miss only
+            if e:
+                top = edge_index.amax(dim=1).tolist()
+                if top[0] >= n_src or top[1] >= n_dst:
+                    raise ValueError(f"edge_index out of range: sources must lie in [0, {n_src}), destinations in [0, {n_dst}) "
+                                     f"(largest: {top[0]}, {top[1]})")
+            return build_graph_plans(edge_index, edge_type, n, r, route.tile, self.aggr, fwd_range=(0, n_dst),
+                                     bwd_range=(0, n_src or n), chunk=route.chunk, paths=paths)
+
+        return cached_graph_plans(edge_index, edge_type, n, r, route.tile, self.aggr, builder=build,
+                                  extra_key=("bipartite", n_src, n_dst), chunk=route.chunk, paths=route.paths,
+                                  widths=(self.in_channels, self.out_channels))
 
     def _forward_featureless(self, x: Optional[Tensor], edge_index: Tensor, edge_type: Tensor) -> Tensor:
         if self.dist is not None:

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import rgcn_oracle as O
-from tests.bipartite_reference import bipartite_graph, pyg_bipartite_loop, reference
+from tests.bipartite_reference import bipartite_graph, device_reference, pyg_bipartite_loop, reference
 
 
 # ---- the reference helper ------------------------------------------------------------------------------------------------------
@@ -46,6 +46,35 @@ def test_reference_without_root_and_bias():
     assert sorted(ref) == ["out", "weight", "x_src"]
     y = pyg_bipartite_loop(xs, xd, ei, et, w, None, None)
     assert float(np.abs(ref["out"] - y.numpy()).max()) < 1e-12
+
+
+@pytest.mark.parametrize("sizes", [(300, 180), (180, 300)])
+@pytest.mark.parametrize("aggr", ["mean", "sum"])
+@pytest.mark.parametrize("root_bias", [(True, True), (False, False)])
+def test_device_reference_equals_reference(sizes, aggr, root_bias, monkeypatch):
+    """the torch form used past 2^24 rows (tests/test_gpu_bipartite_past_4gib.py) against the numpy composition, on the CPU:
+    values, condition sums, and its fp32 evaluation within fp32 rounding of the float64 one; row blocks smaller than the sides"""
+    from tests import bipartite_reference
+    monkeypatch.setattr(bipartite_reference, "BATCH_ROWS", 32)      # (its batched float64 products, with a remainder, at these sizes)
+    n_src, n_dst = sizes
+    r, in_src, in_dst, out = 5, 7, 5, 6
+    ei, et = bipartite_graph(n_src, n_dst, r, seed=n_src + 3 * n_dst)
+    gen = torch.Generator().manual_seed(4)
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    xs, xd, w, g = rnd(n_src, in_src), rnd(n_dst, in_dst), rnd(r, in_src, out), rnd(n_dst, out)
+    root, bias = (rnd(in_dst, out) if root_bias[0] else None), (rnd(out) if root_bias[1] else None)
+    ref, cond, _ = reference(xs, xd, ei, et, w, root, bias, g, aggr)
+    got = device_reference(xs, xd, ei, et, w, root, bias, g, aggr, torch.float64, False, block=64)
+    gcond = device_reference(xs, xd, ei, et, w, root, bias, g, aggr, torch.float64, True, block=64)
+    g32 = device_reference(xs, xd, ei, et, w, root, bias, g, aggr, torch.float32, False, block=64)
+    assert sorted(got) == sorted(ref) == sorted(gcond) == sorted(g32)
+    for k in ref:
+        assert tuple(got[k].shape) == ref[k].shape and got[k].dtype == torch.float64 and g32[k].dtype == torch.float32, k
+        scale = max(1.0, float(np.abs(cond[k]).max()))
+        assert float(np.abs(got[k].numpy() - ref[k]).max()) < 1e-12 * scale, k
+        assert float(np.abs(gcond[k].numpy() - cond[k]).max()) < 1e-12 * scale, k
+        assert float(np.abs(g32[k].double().numpy() - ref[k]).max()) < 1e-5 * scale, k
+    assert not bool(got["weight"][r - 1].any())
 
 
 # ---- constructor ---------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,12 @@
 and d_bias against the fp64 reference of tests/bipartite_reference.py under oracle/tolerance.py (bound (1) with the condition sums,
 bound (2) at 2 x the fp32 CPU loop), on both paths, on graphs with a hub, repeated triples, an empty relation and isolated
 destinations; target rows (``target_block``) against the full layer's rows; the two kernels of csrc/rgcn_rows.hip through the
-binding against torch fp64; the refusals that need the device."""
+binding against torch fp64; the refusals that need the device.
+
+``ROWS`` stops at 20,000: up to there every wave of both kernels of csrc/rgcn_rows.hip makes exactly ONE trip through its loop
+(a second one starts above 65,536 rows in rgcn_rows_transform_kernel, above 131,072 / 65,536 / 32,768 rows in rgcn_rows_dw_kernel
+at 1 / 2 / 4 quadrants).  tests/test_gpu_rows_kernels.py continues from there; tests/test_gpu_bipartite_options.py runs the layer's
+options on every route, tests/test_gpu_bipartite_past_4gib.py both past 2^24 rows and 4 GiB."""
 
 import numpy as np
 import pytest
@@ -10,7 +15,7 @@ import torch
 
 from oracle import rgcn_oracle as O
 from oracle.tolerance import U32, abs_condition, assert_close, cpu32_reference
-from tests.bipartite_reference import bipartite_graph, reference
+from tests.bipartite_reference import bipartite_graph, check as _check, reference
 
 pytestmark = pytest.mark.gpu
 R = 5
@@ -48,40 +53,6 @@ def _run(conv, xs, xd, ei, et, g, grad_src=True, grad_dst=True):
     res = {"out": out.detach().cpu(), "x_src": None if xs.grad is None else xs.grad.cpu(), "x_dst": None if xd.grad is None else xd.grad.cpu()}
     res.update({k: p.grad.detach().cpu().clone() for k, p in conv.named_parameters() if p.grad is not None})
     return res
-
-
-def _check(conv, xs, xd, ei, et, g, got, aggr, tag):
-    """every tensor of ``got`` against the fp64 reference of the equivalent dense layer; a decomposition's gradients pushed from the
-    dense d_W through ``effective_weight`` by fp64 autograd (their condition: the same on absolute values)"""
-    din, dout = conv.in_channels, conv.out_channels
-    w = conv.weight.detach().cpu().double()
-    comp = None if conv.comp is None else conv.comp.detach().cpu().double()
-    cpu = lambda p: None if p is None else p.detach().cpu()
-    wf = O.effective_weight(w, comp, R, conv.num_blocks, din, dout)
-    ref, cond, cpu32 = reference(xs.cpu(), xd.cpu(), ei.cpu(), et.cpu(), wf, cpu(conv.root), cpu(conv.bias), g.cpu(), aggr)
-    for k in ("out", "x_src", "x_dst", "root", "bias"):
-        if got.get(k) is not None:
-            assert tuple(got[k].shape) == ref[k].shape, (k, tag)
-            assert_close(got[k].numpy(), ref[k], cond[k], f"bipartite {k} {tag}", cpu32=cpu32[k])
-    if "weight" not in got and "comp" not in got:
-        return ref
-    if conv.comp is None and conv.num_blocks is None:
-        assert_close(got["weight"].numpy(), ref["weight"], cond["weight"], f"bipartite d_weight {tag}", cpu32=cpu32["weight"])
-        return ref
-
-    def push(wv, cv, dw):
-        wv = wv.clone().requires_grad_(True)
-        cv = None if cv is None else cv.clone().requires_grad_(True)
-        full = O.effective_weight(wv, cv, R, conv.num_blocks, din, dout)
-        return torch.autograd.grad(full, [t for t in (wv, cv) if t is not None], torch.from_numpy(dw))
-
-    want = push(w, comp, ref["weight"])
-    cnd = push(w.abs(), None if comp is None else comp.abs(), np.abs(cond["weight"]))
-    if "weight" in got:
-        assert_close(got["weight"].numpy(), want[0].numpy(), cnd[0].numpy(), f"bipartite d_weight {tag}")
-    if "comp" in got:
-        assert_close(got["comp"].numpy(), want[1].numpy(), cnd[1].numpy(), f"bipartite d_comp {tag}")
-    return ref
 
 
 def _inputs(n_src, n_dst, in_src, in_dst, dout, dev, seed=9):
