@@ -265,7 +265,10 @@ int rgcn_bwd_dw_tiles(const rgcn_plan_t* plan, const int32_t* walk_ptr, const fl
  * autograd's backward of RGCNConv (reference model/modelTrainer.py:66), which needs no plan: the rows the root relation
  * "gathers" are the nodes' own.  Widths up to 64 per side (RGCN_ERR_WIDTH beyond: use rgcn_bwd_dw with
  * RGCN_FLAG_DW_ROOT_ONLY).  A streaming kernel without LDS whose workgroups fit a CU next to rgcn_bwd_dx's: enqueue it on a
- * second stream beside the dX launch.  d_root or d_bias may be NULL (not both).  Bit-reproducible. */
+ * second stream beside the dX launch.  d_root or d_bias may be NULL (not both).  Bit-reproducible.  The kernel is the one
+ * behind rgcn_rows_dw (csrc/rgcn_dw_root.hip), here on one 64 x 64 output with the bias sums: where both entry points cut the
+ * rows into the same ranges their products agree bit for bit.  A row count whose share per wave cannot be addressed with
+ * 32-bit offsets is RGCN_ERR_STRIDE. */
 size_t rgcn_bwd_dw_root_workspace_bytes(void);
 int rgcn_bwd_dw_root(const float* x, int ldx, int din, const float* g, int ldg, int dout, long rows, void* workspace,
                      size_t workspace_bytes, float* d_root, float* d_bias, void* stream);
@@ -384,7 +387,7 @@ size_t rgcn_xwide_bwd_dw_workspace_bytes(const rgcn_plan_t* plan, int din, int d
 int rgcn_xwide_bwd_dw(const rgcn_plan_t* plan, const float* x, int ldx, int din, const float* g, int ldg, int dout, void* workspace,
                       size_t workspace_bytes, float* d_weight, float* d_root, float* d_bias, void* stream);
 
-/* ---- bipartite layers: the root term (csrc/rgcn_rows.hip) ------------------------------------------------------
+/* ---- bipartite layers: the root term (csrc/rgcn_rows.hip, rgcn_rows_dw: csrc/rgcn_dw_root.hip) ------------------
  * RGCNConv with x = (x_src, x_dst) (PyG 2.3.1): `root` is [in_dst, out] and multiplies x_dst, whose rows pair up one to one
  * with the output rows -- a different matrix of a different width than the rows the plans gather, so the plans' root relation
  * is packed as zeros and the term and its two gradients are dense, plan-free products over rows.  Widths 1..128 per side
@@ -400,6 +403,7 @@ int rgcn_xwide_bwd_dw(const rgcn_plan_t* plan, const float* x, int ldx, int din,
  *   bias: NULL or [dout].
  *   Columns dout..roundup4(dout) of y are written as +0.0.  rows == 0 touches nothing.
  * rgcn_rows_dw: d_w [din, dout] (dense, no padding) = x^T g over rows [0, rows).  rows == 0 writes zeros (x and g may then be NULL).
+ *   The streaming kernel of rgcn_bwd_dw_root with the output cut into quadrants of 64 x 64, one per wave, and no bias sums.
  *   Per-wave partial slabs in `workspace` (the query answers 0 on bad widths), summed in a fixed order.  A row count whose
  *   share per wave cannot be addressed with 32-bit offsets (beyond 2^31 rows at 128 columns) is RGCN_ERR_STRIDE. */
 int rgcn_rows_transform(const float* x, int ldx, int din, const float* w, int transpose, const float* add, int lda,

@@ -5,7 +5,7 @@
 //   rgcn_tile3p.hip      forward / dX of 64 x 64 layers on bf16 x 3 MFMAs (the default there)
 //   rgcn_dw_relmajor.hip weight gradients, relation-major walks (every width class) + rgcn_bwd_dw
 //   rgcn_dw_tile.hip     weight gradients, tile-major walk (64 x 64, <= 32 relations) + rgcn_bwd_dw_tiles
-//   rgcn_dw_root.hip     d_root / d_bias by a plan-free streaming product
+//   rgcn_dw_root.hip     d_root / d_bias by a plan-free streaming product: rgcn_bwd_dw_root, rgcn_rows_dw
 //   rgcn_abi.hip         version / status strings, weight packing, activation backward
 //   rgcn_plan.hip        device-side graph plan builder
 #pragma once

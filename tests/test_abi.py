@@ -50,7 +50,7 @@ def test_argument_errors_are_status_codes_not_crashes():
 
 def test_rows_dw_refuses_a_row_range_past_its_32_bit_offsets():
     """rgcn_rows_dw addresses a wave's row range -- and the batches it loads past its end -- through 32-bit buffer offsets: one row
-    is one range of 1 k-step, rows_per_wave = 4 * (1 + 1 + 3 * kRowsDwBatch) = 104, and the first stride with
+    is one range of 1 k-step, rows_per_wave = 4 * (1 + 1 + 3 * kDwRootBatch) = 104, and the first stride with
     104 * ld * 4 >= 0xFFFFFF00 answers RGCN_ERR_STRIDE.  check_stride accepts that stride (a multiple of 4 at least the padded
     width), so the refusal is the range check's own; it sits before check_device and nothing is read: host dummy pointers, no
     memory behind the stride, no launch on any machine."""
@@ -58,7 +58,7 @@ def test_rows_dw_refuses_a_row_range_past_its_32_bit_offsets():
     buf = (ctypes.c_float * 64)()
     p = ctypes.addressof(buf)
     need = lib.rgcn_rows_dw_workspace_bytes(16, 16)
-    rows_per_wave = 4 * (1 + 1 + 3 * 8)                   # csrc/rgcn_rows.hip: kRowsDwBatch = 8
+    rows_per_wave = 4 * (1 + 1 + 3 * 8)                   # csrc/rgcn_dw_root.hip: kDwRootBatch = 8
     ld = -(-0xFFFFFF00 // (rows_per_wave * 4))
     ld += -ld % 4
     assert ld == 10_324_440 and rows_per_wave * (ld - 4) * 4 < 0xFFFFFF00 <= rows_per_wave * ld * 4 and ld < 2 ** 31

@@ -1,11 +1,12 @@
 """Bipartite RGCNConv (``x = (x_src, x_dst)``) on the GPU: output, dX_src, d_x_dst, d_weight (dense, basis, blocks), d_comp, d_root
 and d_bias against the fp64 reference of tests/bipartite_reference.py under oracle/tolerance.py (bound (1) with the condition sums,
 bound (2) at 2 x the fp32 CPU loop), on both paths, on graphs with a hub, repeated triples, an empty relation and isolated
-destinations; target rows (``target_block``) against the full layer's rows; the two kernels of csrc/rgcn_rows.hip through the
-binding against torch fp64; the refusals that need the device.
+destinations; target rows (``target_block``) against the full layer's rows; the two rows kernels (rgcn_rows_transform_kernel of
+csrc/rgcn_rows.hip, rgcn_dw_root_kernel<false> of csrc/rgcn_dw_root.hip behind rgcn_rows_dw) through the binding against torch
+fp64; the refusals that need the device.
 
-``ROWS`` stops at 20,000: up to there every wave of both kernels of csrc/rgcn_rows.hip makes exactly ONE trip through its loop
-(a second one starts above 65,536 rows in rgcn_rows_transform_kernel, above 131,072 / 65,536 / 32,768 rows in rgcn_rows_dw_kernel
+``ROWS`` stops at 20,000: up to there every wave of both kernels makes exactly ONE trip through its loop
+(a second one starts above 65,536 rows in rgcn_rows_transform_kernel, above 131,072 / 65,536 / 32,768 rows in rgcn_rows_dw's kernel
 at 1 / 2 / 4 quadrants).  tests/test_gpu_rows_kernels.py continues from there; tests/test_gpu_bipartite_options.py runs the layer's
 options on every route, tests/test_gpu_bipartite_past_4gib.py both past 2^24 rows and 4 GiB."""
 

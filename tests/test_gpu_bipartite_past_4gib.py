@@ -1,7 +1,7 @@
 """The bipartite layer past 2^24 rows and 4 GiB, in the manner of tests/test_gpu_past_4gib.py (whose conventions, ``check`` and
 memory fixture are used as they are): its natural use is a huge x_src with few target rows.
 
-  the kernels of csrc/rgcn_rows.hip through the binding, rows = 2^24 + 4099 ("Row offsets are 64-bit: rows x ld may pass 2^31"):
+  the kernels behind rgcn_rows_transform and rgcn_rows_dw through the binding, rows = 2^24 + 4099 ("Row offsets are 64-bit: rows x ld may pass 2^31"):
     3 -> 5      rows past 2^24 alone (0.27 / 0.54 GB per matrix)
     64 -> 4     x passes 2^32 bytes, y / add / g do not
     4 -> 64     y / add / g pass 2^32 bytes, x does not

@@ -1,17 +1,20 @@
-"""The two kernels of csrc/rgcn_rows.hip past their first trip: tests/test_gpu_bipartite.py stops at 20,000 rows, where every wave
+"""The two rows kernels (csrc/rgcn_rows.hip, csrc/rgcn_dw_root.hip) past their first trip: tests/test_gpu_bipartite.py stops at 20,000 rows, where every wave
 of both kernels makes exactly one trip through its loop.  Here the row counts are the smallest at which
 
   rgcn_rows_transform_kernel   (at most kRowsTfMaxBlocks = 512 workgroups of kRowsTfWaves = 8 waves, 16 rows per wave and trip: a
                                second trip above 65,536 rows) consumes its look-ahead registers (KT <= 4) or reloads (KT = 8),
                                reaches a partial last tile on a later trip and reads ``add`` aliased to ``y`` across trips;
-  rgcn_rows_dw_kernel          (ranges of ceil(ksteps / 16) k-steps until 2048 / nq ranges are reached: a second trip of the double
+  rgcn_dw_root_kernel<false>   (rgcn_rows_dw: ranges of ceil(ksteps / 16) k-steps until 2048 / nq ranges are reached: a second trip of the double
                                batch above 131,072 / 65,536 / 32,768 rows at nq = 1 / 2 / 4) runs its second load_batch(0) /
                                compute_batch(1) round on the running 32-bit offsets, over ranges that are no multiple of 16
                                k-steps, and the reduce kernel folds 512, 1024 and 2048 slabs per quadrant.
 
 Every case computes the trip counts it claims from the host code's formulas and asserts them BEFORE launching: a change of a
 constant that lets a case drift back to one trip fails here.  Reference: plain torch float64 on the device (x @ W, x^T g, the
-condition the same products on absolute values), judged by bound (1) of oracle/tolerance.py; never another kernel."""
+condition the same products on absolute values), judged by bound (1) of oracle/tolerance.py; never another kernel.
+
+rgcn_rows_dw and rgcn_bwd_dw_root are two instantiations of ONE kernel template with one reduce kernel behind them: the last test
+holds them to the same bits wherever both apply and cut the rows into the same ranges."""
 import pytest
 import torch
 
@@ -19,8 +22,8 @@ from tests.test_gpu_bipartite import _bound1, _padded
 
 pytestmark = pytest.mark.gpu
 
-# csrc/rgcn_rows.hip: kRowsTfMaxBlocks, kRowsTfWaves (= kRowsTfThreads / 64), kRowsDwBatch.  kRowsDwMaxWaves is read from the
-# library (the workspace holds one 64 x 64 slab of floats per wave).
+# csrc/rgcn_rows.hip: kRowsTfMaxBlocks, kRowsTfWaves (= kRowsTfThreads / 64); csrc/rgcn_dw_root.hip: kDwRootBatch.  kRowsDwMaxWaves is
+# read from the library (the workspace holds one 64 x 64 slab of floats per wave).
 TF_MAX_BLOCKS, TF_WAVES, DW_BATCH = 512, 8, 8
 
 # rows -> (transform trips per wave (min, max), {nq: d_w trips per range (min, max)})
@@ -162,3 +165,24 @@ def test_rows_dw_past_the_first_trip(dev, rows, din, dout):
     _bound1(runs[0], ref, cond, f"rows_dw {rows}x{din}x{dout}")
     assert torch.equal(runs[0], runs[1]), "bit-reproducible"
     assert torch.equal(_lib.rows_dw(x, din, g, dout), runs[0]), "the binding's own call"
+
+
+@pytest.mark.parametrize("din,dout", [(64, 64), (61, 3), (4, 64), (33, 20)])
+@pytest.mark.parametrize("rows", [259, 4099, 65_536])
+def test_rows_dw_is_the_root_kernel(dev, rows, din, dout):
+    """rgcn_rows_dw and rgcn_bwd_dw_root run one kernel template and one reduce kernel: up to 64 columns per side (one quadrant) and
+    where both cut the rows into the same ranges -- min(want, 2048) against clamp(want, 4, 1024), want = ceil(ksteps / 16) -- the two
+    products are the same bits.  259 rows: five ranges, the last k-step three rows past the end; 65,536: exactly the root entry's
+    cap of 1024 ranges.  The widths leave partial 16-byte pieces and lanes beyond the width on either operand."""
+    from scaling_rgcn_training_amd import _lib
+    want = ((rows + 3) // 4 + 2 * DW_BATCH - 1) // (2 * DW_BATCH)
+    assert 4 <= want <= 1024 and want == {259: 5, 4099: 65, 65_536: 1024}[rows]
+    gen = torch.Generator().manual_seed(rows + din * 139 + dout)
+    x = _padded(rows, din, 8, dev, gen)
+    g = _padded(rows, dout, 4, dev, gen)
+    x[:, (din + 3) // 4 * 4:] = 7.0                                # beyond the 16-byte pieces of the width nothing is read
+    g[:, (dout + 3) // 4 * 4:] = 7.0
+    d_root = torch.full((din, dout), NAN, device=dev)
+    d_bias = torch.full((dout,), NAN, device=dev)
+    _lib.bwd_dw_root(x, din, g, dout, d_root, d_bias)
+    assert torch.equal(_lib.rows_dw(x, din, g, dout), d_root), f"rows_dw vs bwd_dw_root {rows}x{din}x{dout}"

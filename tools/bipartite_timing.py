@@ -4,7 +4,7 @@ homogeneous layer's step on the FULL graph in the same process (what a caller wh
   * target rows (``target_block``) on 1M nodes / 10M edges / 32 relations at 64 -> 64, rows = 1 % and 10 % of the nodes;
   * the AM-like shape (1.5M / 6M / 267, 30 bases, 32 -> 32) with 1,000 rows;
   * a hop block ``(x, x[:N_dst])`` with N_dst = N_src / 4 on the 1M graph;
-and the two kernels of csrc/rgcn_rows.hip alone at 1M rows (64 x 64 and 128 x 128) with their fraction of 6.3 TB/s by the byte models
+and rgcn_rows_transform / rgcn_rows_dw alone at 1M rows (64 x 64 and 128 x 128) with their fraction of 6.3 TB/s by the byte models
 rows x (din + 2 dout) x 4 (transform: x and add read, y written) and rows x (din + dout) x 4 (d_w).
     python tools/bipartite_timing.py [--cases ...] [--steps 10]
 Prints one JSON line per case.  The bipartite step includes the caller's ``x[rows]`` and its backward.  Kernel-only times of a step:
