@@ -412,6 +412,43 @@ size_t rgcn_rows_dw_workspace_bytes(int din, int dout);
 int rgcn_rows_dw(const float* x, int ldx, int din, const float* g, int ldg, int dout, long rows, void* workspace,
                  size_t workspace_bytes, float* d_w, void* stream);
 
+/* ---- graph summaries: k-bisimulation node partitions and quotient graphs (csrc/rgcn_summary.hip) --------------
+ * The step that makes the summary graphs the method trains on first, on the same strided int64 COO (struct rgcn_graph) the
+ * plan builder takes.  A partition is an int32 block id per node.  One refinement round maps a partition b to b':
+ * b'[i] == b'[j] iff b[i] == b[j] and S(i) == S(j), where S is a SET (duplicates and order ignored) over the node's edges:
+ *   RGCN_DIR_OUT:    S(i) = {(type_e, b[dst_e]) : src_e = i}
+ *   RGCN_DIR_IN:     S(i) = {(type_e, b[src_e]) : dst_e = i}
+ *   RGCN_DIR_IN_OUT: S(i) = {(0, type_e, b[dst_e]) : src_e = i} u {(1, type_e, b[src_e]) : dst_e = i}
+ * b' is numbered canonically: ids 0 .. B' - 1 in the order of the smallest node of every block.  From the all-zero partition
+ * round 1 is the reference's attribute summary over relation ids (graphs/createAttributeSum.py), rounds 2 .. k the
+ * k-bisimulation; a round that returns B' == B (B the number of DISTINCT ids in b) changed nothing: the fixpoint.
+ * Sets are compared through 128-bit signatures (sums of two 64-bit mixes per distinct element, the node's own block folded
+ * in); block ids do not depend on the hash.  Limits: num_relations <= 65536, num_edges (twice that for RGCN_DIR_IN_OUT)
+ * <= 0xFFFF0000 (RGCN_ERR_PLAN beyond).  Both entry points SYNCHRONISE the stream once, to read one data-dependent count back
+ * into the HOST pointer they take last but one; they allocate nothing.  An edge_index / edge_type value out of range, or a
+ * block id outside [0, num_blocks), is RGCN_ERR_GRAPH (found on the device: outputs are then unspecified, nothing is written
+ * outside them).  route: 0 = the library chooses; 1 = one stable sort over a single packed 64-bit key (RGCN_ERR_PLAN when the
+ * fields do not fit 64 bits); 2 = two stable sorts (always possible; what route 0 falls back to). */
+enum rgcn_summary_direction { RGCN_DIR_OUT = 0, RGCN_DIR_IN = 1, RGCN_DIR_IN_OUT = 2 };
+
+/* Bytes of scratch for rgcn_summary_round on num_edges edges and num_nodes nodes in `direction` (0 on bad arguments);
+ * rgcn_summary_quotient needs the RGCN_DIR_OUT size.  A larger workspace serves a smaller call. */
+size_t rgcn_summary_workspace_bytes(int64_t num_edges, int32_t num_nodes, int direction);
+
+/* One refinement round.  block_in [num_nodes] with ids in [0, num_blocks_in), num_blocks_in >= 1 (the ids need not be
+ * canonical nor all in use: num_blocks_in only sizes the key field); block_out [num_nodes] (may alias block_in);
+ * *num_blocks_out (host) = B'.  A graph without edges is allowed (src / dst / type may then be NULL): the call then numbers
+ * block_in canonically. */
+int rgcn_summary_round(const rgcn_graph_t* graph, int direction, const int32_t* block_in, int32_t num_blocks_in, int route,
+                       int32_t* block_out, void* workspace, size_t workspace_bytes, int32_t* num_blocks_out, void* stream);
+
+/* The quotient graph of a partition: the distinct (block[src], type, block[dst]) triples sorted by (type, block[dst],
+ * block[src]), with the number of edges behind each.  src_out / dst_out / type_out / mult_out: int64 [num_edges] each (the
+ * worst case; may be NULL when num_edges == 0), of which the first *num_edges_out (host) are written. */
+int rgcn_summary_quotient(const rgcn_graph_t* graph, const int32_t* block, int32_t num_blocks, int route, int64_t* src_out,
+                          int64_t* dst_out, int64_t* type_out, int64_t* mult_out, void* workspace, size_t workspace_bytes,
+                          int64_t* num_edges_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

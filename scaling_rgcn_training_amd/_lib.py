@@ -103,6 +103,9 @@ def _prototypes() -> dict:
         "rgcn_rows_transform": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, lng, vp]),
         "rgcn_rows_dw_workspace_bytes": (sz, [i32, i32]),
         "rgcn_rows_dw": (i32, [vp, i32, i32, vp, i32, i32, lng, vp, sz, vp, vp]),
+        "rgcn_summary_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_summary_round": (i32, [graph, i32, vp, i32, i32, vp, vp, sz, C.POINTER(C.c_int32), vp]),
+        "rgcn_summary_quotient": (i32, [graph, vp, i32, i32, vp, vp, vp, vp, vp, sz, C.POINTER(C.c_int64), vp]),
     }
 
 
@@ -376,6 +379,43 @@ def bwd_dw_root(x: torch.Tensor, din: int, g: torch.Tensor, dout: int, d_root: O
         ws = torch.empty(lib.rgcn_bwd_dw_root_workspace_bytes(), dtype=torch.uint8, device=x.device)
         check(lib.rgcn_bwd_dw_root(x.data_ptr(), x.stride(0), din, g.data_ptr(), g.stride(0), dout, x.shape[0],
                                    ws.data_ptr(), ws.numel(), _ptr(d_root), _ptr(d_bias), _stream(x)), "rgcn_bwd_dw_root")
+
+
+# ---- graph summaries (rgcn_summary.hip; summaries.py validates and drives them) -------------------------------------------
+SUMMARY_DIRECTIONS = {"out": 0, "in": 1, "in_out": 2}      # enum rgcn_summary_direction
+SUMMARY_MAX_KEYS = 0xFFFF0000                              # edges (twice that for "in_out") one call sorts
+SUMMARY_MAX_RELATIONS = 65536
+
+
+def summary_workspace(num_edges: int, num_nodes: int, direction: int, device) -> torch.Tensor:
+    n = load().rgcn_summary_workspace_bytes(int(num_edges), int(num_nodes), int(direction))
+    if n == 0:
+        raise RgcnLibraryError("rgcn_summary_workspace_bytes: bad arguments")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def summary_round(graph: RgcnGraphStruct, direction: int, block_in: torch.Tensor, num_blocks_in: int, block_out: torch.Tensor,
+                  ws: torch.Tensor, route: int = 0) -> int:
+    """one refinement round (rgcn_summary_round): int32 ``block_in`` -> ``block_out``, returns the number of blocks"""
+    nb = C.c_int32(-1)
+    with torch.cuda.device(ws.device):
+        check(load().rgcn_summary_round(C.byref(graph), int(direction), block_in.data_ptr(), int(num_blocks_in), int(route),
+                                        block_out.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(nb), _stream(ws)),
+              "rgcn_summary_round")
+    return int(nb.value)
+
+
+def summary_quotient(graph: RgcnGraphStruct, block: torch.Tensor, num_blocks: int, ws: torch.Tensor, route: int = 0):
+    """(edge_index_s int64 [2, E_s], edge_type_s [E_s], multiplicity [E_s]) of rgcn_summary_quotient"""
+    e = int(graph.num_edges)
+    out = torch.empty(4, max(e, 1), dtype=torch.int64, device=ws.device)      # rows: src, dst, type, multiplicity
+    ne = C.c_int64(-1)
+    with torch.cuda.device(ws.device):
+        check(load().rgcn_summary_quotient(C.byref(graph), block.data_ptr(), int(num_blocks), int(route), out[0].data_ptr(),
+                                           out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), ws.data_ptr(), ws.numel(),
+                                           C.byref(ne), _stream(ws)), "rgcn_summary_quotient")
+    out = out[:, :int(ne.value)]
+    return out[:2].clone(), out[2].clone(), out[3].clone()
 
 
 # ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------

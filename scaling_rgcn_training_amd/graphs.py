@@ -105,11 +105,43 @@ def node_mappings(map_triples) -> Tuple[Dict[str, str], Dict[str, List[str]]]:
     return dict(sorted(org2sum.items())), dict(sorted(sum2org.items()))
 
 
+def summary_graph(org: Graph, partition, name: str, dedup: bool = False) -> Graph:
+    """The summary ``Graph`` of a node partition of ``org`` (``summaries.node_partition``), ready for ``Dataset.sumGraphs``:
+    block ``i`` is node ``<b{i}>`` with enumeration ``i``, ``relations`` is ``org``'s own (a summary made from the original's COO
+    has the original's relation ids by construction), ``training_data`` is the quotient graph -- one summary edge per original
+    edge as in the reference's summary files, or with ``dedup`` the distinct triples (``summaries.quotient_graph``, which needs
+    the partition on the GPU) -- and the two node maps follow ``partition.block``."""
+    from . import summaries
+    block, nb = partition.block, int(partition.num_blocks)
+    if block.shape[0] != org.num_nodes:
+        raise ValueError(f"the partition has {block.shape[0]} nodes, graph {org.name!r} has {org.num_nodes}")
+    td = org.training_data
+    if dedup:
+        ei, et, _ = summaries.quotient_graph(td.edge_index.to(block.device), td.edge_type.to(block.device), block, nb)
+    else:
+        ei, et = block.cpu()[td.edge_index], td.edge_type.clone()
+    sg = Graph(name, deepcopy(org.org2type_dict))
+    sg.nodes = [f"<b{i}>" for i in range(nb)]
+    sg.node_to_enum = {n: i for i, n in enumerate(sg.nodes)}
+    sg.num_nodes = nb
+    sg.num_edges = int(et.shape[0])
+    sg.relations = dict(org.relations)
+    sg.training_data = Data(edge_index=ei.cpu().contiguous())
+    sg.training_data.edge_type = et.cpu().contiguous()
+    ids = block.cpu().tolist()
+    sg.orgNode2sumNode_dict = {node: sg.nodes[b] for node, b in zip(org.nodes, ids)}
+    sg.sumNode2orgNode_dict = {n: [] for n in sg.nodes}
+    for node, b in zip(org.nodes, ids):
+        sg.sumNode2orgNode_dict[sg.nodes[b]].append(node)
+    return sg
+
+
 class Dataset:
     """``Dataset(org_path, sum_path, map_path).init_dataset()`` -> ``orgGraph``, ``sumGraphs``, ``num_classes``
-    with ``training_data.{x,y}_{train,val,test}`` filled (reference graphs/dataset.py)."""
+    with ``training_data.{x,y}_{train,val,test}`` filled (reference graphs/dataset.py).  Without ``sum_path`` / ``map_path``
+    the original graph is loaded alone and ``add_summary`` makes the summaries from it on the GPU."""
 
-    def __init__(self, org_path: str, sum_path: str, map_path: str) -> None:
+    def __init__(self, org_path: str, sum_path: Optional[str] = None, map_path: Optional[str] = None) -> None:
         self.org_path, self.sum_path, self.map_path = org_path, sum_path, map_path
         self.sumGraphs: List[Graph] = []
         self.orgGraph: Graph = None
@@ -170,7 +202,7 @@ class Dataset:
         org2type = nodes2type_mapping(org_triples, classes)
         self.orgGraph = Graph(os.path.basename(self.org_path), deepcopy(org2type))
         self.orgGraph.init_graph(org_lines)
-        sums, maps = self.get_file_names()
+        sums, maps = self.get_file_names() if self.sum_path is not None else ([], [])
         for sf, mf in zip(sums, maps):
             sg = Graph(sf, deepcopy(org2type))
             sg.init_graph(parse_graph_nt(os.path.join(self.sum_path, sf)))
@@ -178,6 +210,26 @@ class Dataset:
                 split_triples(parse_graph_nt(os.path.join(self.map_path, mf))))
             self.sumGraphs.append(sg)
         self.make_training_data()
+
+    def add_summary(self, k: Optional[int] = 1, direction: str = "out", device=None, *, partition=None, name: Optional[str] = None,
+                    dedup: bool = False) -> Graph:
+        """Append the k-bisimulation summary of the original graph (``k=1``: the attribute summary over relation ids; ``k=None``:
+        the full bisimulation) made on ``device`` (default ``cuda``) by ``summaries.node_partition`` over the message-passing
+        edges, inverse edges included -- or the summary of a ``partition`` the caller made -- and refresh the training data."""
+        from . import summaries
+        org = self.orgGraph
+        if org is None:
+            raise RuntimeError("add_summary needs the original graph: call init_dataset() first")
+        if partition is None:
+            dev = torch.device("cuda" if device is None else device)
+            td = org.training_data
+            partition = summaries.node_partition(td.edge_index.to(dev), td.edge_type.to(dev), org.num_nodes,
+                                                 max(2 * len(org.relations), 1), k=k, direction=direction)
+        label = "fix" if k is None else str(k)
+        sg = summary_graph(org, partition, name or f"{org.name}_bisim_k{label}_{direction}", dedup=dedup)
+        self.sumGraphs.append(sg)
+        self.make_training_data()
+        return sg
 
 
 # ---- model/embeddingTricks.py equivalents (SURVEY.md 8f-3) ---------------------------------------------
