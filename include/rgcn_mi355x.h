@@ -67,8 +67,10 @@ enum rgcn_status {
     RGCN_ERR_DEVICE = -7,    /* current device is not gfx950 / no device */
     RGCN_ERR_ACT = -8,       /* unknown activation code */
     RGCN_ERR_GRAPH = -9,     /* rgcn_plan_build: an edge_index / edge_type value is out of range */
-    RGCN_ERR_ADDRESS = -10   /* rgcn_bwd_dw_tiles: a gathered matrix cannot be addressed through a buffer descriptor (2^24 rows or
+    RGCN_ERR_ADDRESS = -10,  /* rgcn_bwd_dw_tiles: a gathered matrix cannot be addressed through a buffer descriptor (2^24 rows or
                               * 4 GiB and more): use rgcn_bwd_dw, whose kernels fall back to 64-bit pointers */
+    RGCN_ERR_ARG = -11       /* rgcn_sample_*: a scalar argument outside its domain (fan-out, seed, hop, number of destinations),
+                              * or a destination listed twice */
 };
 
 /* Graph plan in HBM, built once per graph (scaling_rgcn_training_amd/plan.py documents the layout;
@@ -448,6 +450,51 @@ int rgcn_summary_round(const rgcn_graph_t* graph, int direction, const int32_t* 
 int rgcn_summary_quotient(const rgcn_graph_t* graph, const int32_t* block, int32_t num_blocks, int route, int64_t* src_out,
                           int64_t* dst_out, int64_t* type_out, int64_t* mult_out, void* workspace, size_t workspace_bytes,
                           int64_t* num_edges_out, void* stream);
+
+/* ---- neighbour sampling: the in-edge index and one fan-out hop (csrc/rgcn_sample.hip) ----------------------------
+ * What makes the (x_src, x_dst) blocks a mini-batch step walks, on the same strided int64 COO (struct rgcn_graph).
+ * Index: the edges sorted stably by destination; ptr[v] .. ptr[v + 1] are the in-edges of v in input order (duplicate triples stay
+ * distinct in-edges), src / type the sorted edges' sources and relations.  Limits: num_edges <= 0xFFFF0000, num_relations <= 65536
+ * (RGCN_ERR_PLAN beyond).
+ * Hop: for destination v = dst_nodes[i] (unique, in [0, num_nodes)) with in-degree d: fanout == -1 or d <= fanout takes all d
+ * in-edges, otherwise a uniform fanout-subset of the positions 0 .. d-1 by Floyd's algorithm (S = {}; for j = d-k .. d-1:
+ * t = draw(j); add j if t is in S, else t) on a counter-based generator, arithmetic mod 2^64:
+ *   mix(z):  z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31
+ *   key      = mix(seed + 0x9E3779B97F4A7C15 * (hop + 1))
+ *   r        = mix(mix(key + v) + j)
+ *   draw(j)  = ((r >> 32) * (j + 1)) >> 32
+ * so the choice depends on (seed, hop, v) alone.  The block: src_nodes = dst_nodes followed by the ascending distinct sampled
+ * sources that are no destination; edges ordered by destination position, then by ascending in-edge position, relabelled to
+ * positions in src_nodes (edge_src) and in dst_nodes (edge_dst).  A pure function of its arguments.
+ * cap, the most edges a block can hold: num_edges for fanout == -1, else min(num_edges, num_dst * fanout).
+ * Both calls allocate nothing and SYNCHRONISE the stream once: the index build to read its error word, the hop to read the error
+ * word, E_b and n_src back.  An edge_index / edge_type value or a destination out of range is RGCN_ERR_GRAPH, a destination listed
+ * twice RGCN_ERR_ARG (both found on the device: outputs are then unspecified, nothing is written outside them, node_map is reset);
+ * a fan-out outside {-1} u [1, 256], seed < 0, hop < 0, num_dst < 0 or > num_nodes: RGCN_ERR_ARG, answered before any launch. */
+typedef struct rgcn_sample_index {
+    const uint32_t* ptr;   /* [num_nodes + 1] */
+    const int32_t* src;    /* [num_edges] (may be NULL when num_edges == 0) */
+    const int32_t* type;   /* [num_edges] */
+    int64_t num_edges;
+    int32_t num_nodes;
+    int32_t num_relations;
+} rgcn_sample_index_t;
+
+/* Bytes of scratch for rgcn_sample_index_build / rgcn_sample_hop (0 on bad arguments).  A larger workspace serves a smaller call. */
+size_t rgcn_sample_index_workspace_bytes(int64_t num_edges, int32_t num_nodes);
+size_t rgcn_sample_hop_workspace_bytes(int64_t num_dst, int fanout, int64_t num_edges, int32_t num_nodes);
+
+/* ptr_out [num_nodes + 1], src_out / type_out [num_edges] (may be NULL when num_edges == 0). */
+int rgcn_sample_index_build(const rgcn_graph_t* graph, uint32_t* ptr_out, int32_t* src_out, int32_t* type_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* One hop.  node_map [num_nodes]: the caller's persistent scratch, every entry 0xFFFFFFFF on entry; the call writes the entries of
+ * the block's nodes and resets exactly those before it returns.  edge_src_out / edge_dst_out / edge_type_out: int64 [cap] each,
+ * src_nodes_out: int64 [num_dst + min(cap, num_nodes)]; the first *num_edges_out / *num_src_out (host) entries are written.
+ * num_dst == 0 is an empty block and launches nothing. */
+int rgcn_sample_hop(const rgcn_sample_index_t* index, const int64_t* dst_nodes, int64_t num_dst, int fanout, int64_t seed, int hop,
+                    uint32_t* node_map, int64_t* edge_src_out, int64_t* edge_dst_out, int64_t* edge_type_out, int64_t* src_nodes_out,
+                    void* workspace, size_t workspace_bytes, int64_t* num_edges_out, int64_t* num_src_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,8 @@ Sub-modules:
 * ``dist``    -- one-process-per-GPU edge partition + per-layer collective over RCCL
 * ``summaries`` -- attribute-summary generation (murmur3 x64-128 of predicate sets; graphs/createAttributeSum.py), and on
   the GPU ``node_partition`` (k-bisimulation partition refinement) / ``quotient_graph`` over the layer's int64 COO
+* ``sampling`` -- ``NeighborSampler``: fan-out neighbour sampling on the GPU into the layered bipartite ``Block`` lists that
+  ``forward_blocks`` / ``Trainer.train_minibatch`` walk
 
 There is no CPU compute path: the layer raises if the HIP library or a GPU is missing.
 """
@@ -38,4 +40,7 @@ def __getattr__(name):
     if name in ("create_sum_map", "hash128", "node_partition", "quotient_graph", "Partition"):
         from . import summaries
         return getattr(summaries, name)
+    if name in ("NeighborSampler", "Block"):
+        from . import sampling
+        return getattr(sampling, name)
     raise AttributeError(name)

@@ -22,6 +22,7 @@ XWIDE_MAX_WIDTH = 512  # RGCN_XWIDE_MAX_WIDTH
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 ERR_PLAN = -4          # inconsistent plan, or a plan layout the called kernel does not walk
 ERR_ADDRESS = -10      # rgcn_bwd_dw_tiles: operands not addressable through a buffer descriptor
+ERR_GRAPH, ERR_ARG = -9, -11      # rgcn_sample_*: an id out of range / a scalar outside its domain, a destination listed twice
 FLAG_POINTER_GATHER, FLAG_DW_RING, FLAG_DW_DIRECT, FLAG_EXACT_FP32, FLAG_DW_ROOT_ONLY, FLAG_SPLIT_PRODUCERS = 1, 2, 4, 8, 16, 32
 
 
@@ -47,6 +48,12 @@ class RgcnGraphStruct(C.Structure):
     """struct rgcn_graph: the int64 COO exactly as the caller holds it (strided views allowed)"""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("type", C.c_void_p),
                 ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("type_stride", C.c_int64),
+                ("num_edges", C.c_int64), ("num_nodes", C.c_int32), ("num_relations", C.c_int32)]
+
+
+class RgcnSampleIndex(C.Structure):
+    """struct rgcn_sample_index: the in-edge index of a graph (rgcn_sample_index_build)"""
+    _fields_ = [("ptr", C.c_void_p), ("src", C.c_void_p), ("type", C.c_void_p),
                 ("num_edges", C.c_int64), ("num_nodes", C.c_int32), ("num_relations", C.c_int32)]
 
 
@@ -106,6 +113,11 @@ def _prototypes() -> dict:
         "rgcn_summary_workspace_bytes": (sz, [i64, i32, i32]),
         "rgcn_summary_round": (i32, [graph, i32, vp, i32, i32, vp, vp, sz, C.POINTER(C.c_int32), vp]),
         "rgcn_summary_quotient": (i32, [graph, vp, i32, i32, vp, vp, vp, vp, vp, sz, C.POINTER(C.c_int64), vp]),
+        "rgcn_sample_index_workspace_bytes": (sz, [i64, i32]),
+        "rgcn_sample_hop_workspace_bytes": (sz, [i64, i32, i64, i32]),
+        "rgcn_sample_index_build": (i32, [graph, vp, vp, vp, vp, sz, vp]),
+        "rgcn_sample_hop": (i32, [C.POINTER(RgcnSampleIndex), vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, sz,
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
     }
 
 
@@ -416,6 +428,58 @@ def summary_quotient(graph: RgcnGraphStruct, block: torch.Tensor, num_blocks: in
                                            C.byref(ne), _stream(ws)), "rgcn_summary_quotient")
     out = out[:, :int(ne.value)]
     return out[:2].clone(), out[2].clone(), out[3].clone()
+
+
+# ---- neighbour sampling (rgcn_sample.hip; sampling.py validates and drives them) -------------------------------------------
+SAMPLE_MAX_EDGES = 0xFFFF0000
+SAMPLE_MAX_RELATIONS = 65536
+SAMPLE_MAX_FANOUT = 256
+
+
+def sample_index_build(graph: RgcnGraphStruct, device):
+    """(struct rgcn_sample_index, (ptr uint32-as-int32 [N + 1], src int32 [E], type int32 [E])) of rgcn_sample_index_build"""
+    lib = load()
+    e, n = int(graph.num_edges), int(graph.num_nodes)
+    nbytes = lib.rgcn_sample_index_workspace_bytes(e, n)
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_sample_index_workspace_bytes: bad arguments")
+    with torch.cuda.device(device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        ptr = torch.empty(n + 1, dtype=torch.int32, device=device)      # (uint32 on the device: edge counts pass 2^31)
+        src = torch.empty(max(e, 1), dtype=torch.int32, device=device)
+        typ = torch.empty(max(e, 1), dtype=torch.int32, device=device)
+        check(lib.rgcn_sample_index_build(C.byref(graph), ptr.data_ptr(), src.data_ptr(), typ.data_ptr(), ws.data_ptr(), nbytes,
+                                          _stream(ws)), "rgcn_sample_index_build")
+    ix = RgcnSampleIndex(ptr.data_ptr(), src.data_ptr(), typ.data_ptr(), e, n, int(graph.num_relations))
+    return ix, (ptr, src, typ)
+
+
+def sample_hop_cap(num_dst: int, fanout: int, num_edges: int) -> int:
+    """the most edges a block of ``num_dst`` destinations can hold (`cap` of include/rgcn_mi355x.h)"""
+    return num_edges if fanout < 0 else min(num_edges, num_dst * fanout)
+
+
+def sample_hop(ix: RgcnSampleIndex, dst_nodes: torch.Tensor, fanout: int, seed: int, hop: int, node_map: torch.Tensor):
+    """one hop (rgcn_sample_hop) -> (edge_index [2, E_b], edge_type [E_b], src_nodes [n_src]), int64 on the device of
+    ``dst_nodes`` (contiguous int64); ``node_map``: the sampler's persistent int32 [N] map, all -1 between calls"""
+    lib, dev = load(), dst_nodes.device
+    nd, e, n = int(dst_nodes.shape[0]), int(ix.num_edges), int(ix.num_nodes)
+    cap = sample_hop_cap(nd, int(fanout), e)
+    nbytes = lib.rgcn_sample_hop_workspace_bytes(nd, int(fanout), e, n)
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_sample_hop_workspace_bytes: bad arguments")
+    ne, ns = C.c_int64(-1), C.c_int64(-1)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        edges = torch.empty(3, max(cap, 1), dtype=torch.int64, device=dev)      # rows: src, dst, type
+        nodes = torch.empty(max(nd + min(cap, n), 1), dtype=torch.int64, device=dev)
+        check(lib.rgcn_sample_hop(C.byref(ix), dst_nodes.data_ptr() if nd else None, nd, int(fanout), int(seed), int(hop),
+                                  node_map.data_ptr(), edges[0].data_ptr(), edges[1].data_ptr(), edges[2].data_ptr(),
+                                  nodes.data_ptr(), ws.data_ptr(), nbytes, C.byref(ne), C.byref(ns), _stream(ws)), "rgcn_sample_hop")
+    eb, nsrc = int(ne.value), int(ns.value)
+    if eb == cap:      # (no copy where the worst case was met)
+        return edges[:2, :eb], edges[2, :eb], nodes[:nsrc].clone()
+    return edges[:2, :eb].clone(), edges[2, :eb].clone(), nodes[:nsrc].clone()
 
 
 # ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------

@@ -1,0 +1,444 @@
+// rgcn_sample.hip -- neighbour sampling ON THE DEVICE behind the C ABI (include/rgcn_mi355x.h: rgcn_sample_index_build,
+// rgcn_sample_hop): the in-edge index of a graph and one fan-out hop that turns a set of destination nodes into a relabelled
+// bipartite block for RGCNConv((x_src, x_dst), ...).  gfx950 only.  DESIGN.md section 14 has the semantics.
+//
+// Index (once per graph):
+//   keys      (dst, edge id) per edge, in-degree counts by integer atomics; ids out of range set an error bit
+//   sort      one stable sort by dst: the in-edges of a node keep the input order
+//   ptr       exclusive scan of the in-degrees (num_nodes + 1 entries)
+//   gather    src / type of the sorted edges as int32
+//
+// Hop (once per layer and step), every launch sized on the host -- by the destinations, by the worst-case edge count `cap`
+// (grid-stride, bounded by the count on the device) or by the 32-node words of the graph:
+//   mark      map[dst_nodes[i]] = i in the caller's persistent num_nodes-entry map; range check
+//   count     min(d, k) per destination; a node listed twice lost one map entry: error, and it counts nothing
+//   scan      offsets of every destination's edges; the total is E_b
+//   floyd     one wave per SAMPLED destination (d > k): Floyd's k-subset, a dependency chain of k draws; the chosen positions sit
+//             in registers (ceil(k / 64) per lane), the membership test is one compare per register and a ballot; the wave then
+//             ranks its positions (k broadcasts) and stores them in ascending order
+//   expand    one thread per block edge (take-all destinations need no wave): destination by binary search in the offsets, the
+//             in-edge's source and type from the index; a source the map does not hold sets its bit in a num_nodes-bit set
+//   frontier  popcount per word, scan: the rank of a set bit IS the ascending order of the new sources -- no sort, no second
+//             count to read back; every bit writes src_nodes and its map entry
+//   relabel   edge sources through the map
+//   reset     the map entries written (destinations, new sources) go back to "none"
+//   read      error bits, E_b and the number of new sources: the one copy and the one synchronisation of a hop
+//
+// All integer work: no float, no waiting between workgroups, every loop bounded by k, d or the grid.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/rgcn_mi355x.h"
+#include "rgcn_sort_scan.h"
+
+namespace rgcn_sample {
+
+using namespace rgcn_sort_scan;
+
+constexpr u32 kErrRange = 1u, kErrDuplicate = 2u;
+constexpr u32 kNone = 0xFFFFFFFFu;           // map entry of a node outside the block
+constexpr u64 kMaxKeys = 0xFFFF0000ull;      // the sort counts keys in u32, rounded up to whole 2,048-key segments
+constexpr int32_t kMaxRelations = 65536;
+constexpr int kMaxFanout = 256;
+constexpr u32 kEdgeGridMax = 16384;          // workgroups of an edge-parallel launch: beyond that the threads stride
+
+struct Results {        // device-resident scalars of one call: what the host reads back in one copy
+    u32 error;          // kErr* bits
+    u32 num_edges;      // E_b
+    u32 num_new;        // sources that are no destination
+    u32 reserved;
+};
+
+__host__ __device__ inline u64 mix(u64 z) {      // splitmix64's finaliser
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+
+// ------------------------------------------------------------------------------------------------
+// index
+// ------------------------------------------------------------------------------------------------
+// An id out of range sets the error bit and the key of node 0: everything later stays inside its arrays whatever the input holds.
+__global__ void index_keys_kernel(const int64_t* __restrict__ src, int64_t src_stride, const int64_t* __restrict__ dst,
+                                  int64_t dst_stride, const int64_t* __restrict__ typ, int64_t typ_stride, u32 num_edges,
+                                  u32 n_nodes, u32 num_rel, u64* __restrict__ keys, u32* __restrict__ vals, u32* __restrict__ deg,
+                                  Results* __restrict__ res) {
+    const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= num_edges) return;
+    const int64_t sv = src[(u64)e * src_stride], dv = dst[(u64)e * dst_stride], t = typ[(u64)e * typ_stride];
+    const bool bad = t < 0 || t >= (int64_t)num_rel || sv < 0 || sv >= (int64_t)n_nodes || dv < 0 || dv >= (int64_t)n_nodes;
+    if (bad) atomicOr(&res->error, kErrRange);
+    const u32 v = bad ? 0u : (u32)dv;
+    keys[e] = v;
+    vals[e] = e;
+    atomicAdd(&deg[v], 1u);
+}
+
+__global__ void index_gather_kernel(const u32* __restrict__ edge, u32 num_edges, const int64_t* __restrict__ src, int64_t src_stride,
+                                    const int64_t* __restrict__ typ, int64_t typ_stride, u32 n_nodes, u32 num_rel,
+                                    int32_t* __restrict__ src_sorted, int32_t* __restrict__ type_sorted) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_edges) return;
+    const u32 e = edge[i];
+    const int64_t sv = src[(u64)e * src_stride], t = typ[(u64)e * typ_stride];
+    src_sorted[i] = (sv < 0 || sv >= (int64_t)n_nodes) ? 0 : (int32_t)sv;      // (else: the error bit is set already)
+    type_sorted[i] = (t < 0 || t >= (int64_t)num_rel) ? 0 : (int32_t)t;
+}
+
+struct IndexWorkspace {
+    SortBufs sb;
+    Results* res;
+    size_t bytes;
+};
+
+static IndexWorkspace carve_index(void* base, u64 num_edges, u64 n_nodes) {
+    IndexWorkspace w;
+    size_t off = 0;
+    auto take = [&](size_t nbytes) {
+        void* p = base ? (char*)base + off : nullptr;
+        off += align_up(nbytes);
+        return p;
+    };
+    const u32 nseg = sort_segments((u32)num_edges);
+    w.res = (Results*)take(sizeof(Results));
+    w.sb.k[0] = (u64*)take(num_edges * 8);
+    w.sb.k[1] = (u64*)take(num_edges * 8);
+    w.sb.v[0] = (u32*)take(num_edges * 4);
+    w.sb.v[1] = (u32*)take(num_edges * 4);
+    w.sb.hist = (u32*)take(((size_t)256 * nseg + 1) * 4);
+    const u64 scan_len = n_nodes + 1 > (u64)256 * nseg ? n_nodes + 1 : (u64)256 * nseg;
+    w.sb.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
+    w.bytes = off;
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------
+// hop
+// ------------------------------------------------------------------------------------------------
+// A destination out of range marks nothing.  src_nodes starts with the destinations.
+__global__ void hop_mark_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, u32 n_nodes, u32* __restrict__ map,
+                                int64_t* __restrict__ src_nodes, Results* __restrict__ res) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_dst) return;
+    const int64_t v = dst_nodes[i];
+    src_nodes[i] = v;
+    if (v < 0 || v >= (int64_t)n_nodes) {
+        atomicOr(&res->error, kErrRange);
+        return;
+    }
+    map[v] = i;
+}
+
+// cnt has n_dst + 1 entries (the last one 0: its scan is E_b).  Of a node listed twice one position lost the map entry: it counts
+// nothing, so the counts add up to at most the edges of the graph -- and of `cap` -- whatever the list holds.
+__global__ void hop_count_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, u32 n_nodes, const u32* __restrict__ ptr,
+                                 int fanout, const u32* __restrict__ map, u32* __restrict__ cnt, Results* __restrict__ res) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_dst) return;
+    u32 c = 0u;
+    if (i < n_dst) {
+        const int64_t v = dst_nodes[i];
+        if (v >= 0 && v < (int64_t)n_nodes) {
+            if (map[v] != i) {
+                atomicOr(&res->error, kErrDuplicate);
+            } else {
+                const u32 d = ptr[v + 1] - ptr[v];
+                c = (fanout < 0 || d <= (u32)fanout) ? d : (u32)fanout;
+            }
+        }
+    }
+    cnt[i] = c;
+}
+
+// One wave per destination; a wave whose destination is taken whole (or counts nothing) leaves at once: off[i + 1] - off[i] is k
+// exactly where d > k.  Slot t (0 .. k-1) of the chosen set lives in
+// register t / 64 of lane t % 64.  Floyd: for j = d-k .. d-1: t = draw(j) in [0, j]; add j if t is chosen already, else t.
+template <int REGS>
+__global__ void hop_floyd_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, const u32* __restrict__ ptr, u32 k,
+                                 u64 key, const u32* __restrict__ off, u32* __restrict__ sel) {
+    const u32 i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const u32 lane = threadIdx.x & 63u;
+    if (i >= n_dst) return;
+    const u32 base = off[i];
+    if (off[i + 1] - base != k) return;
+    const int64_t v = dst_nodes[i];      // (in range and listed once: it has edges)
+    const u32 d = ptr[v + 1] - ptr[v];
+    if (d <= k) return;
+    const u64 kv = mix(key + (u64)v);
+    u32 c[REGS];
+#pragma unroll
+    for (int r = 0; r < REGS; ++r) c[r] = kNone;      // (positions stay below 0xFFFF0000: no position equals an empty slot)
+    for (u32 t = 0; t < k; ++t) {
+        const u32 j = d - k + t;
+        const u64 rnd = mix(kv + (u64)j);
+        const u32 draw = (u32)(((rnd >> 32) * ((u64)j + 1ull)) >> 32);
+        bool hit = false;
+#pragma unroll
+        for (int r = 0; r < REGS; ++r) hit = hit || c[r] == draw;
+        const u32 val = __ballot(hit) != 0ull ? j : draw;
+#pragma unroll
+        for (int r = 0; r < REGS; ++r)
+            if ((u32)r == (t >> 6) && lane == (t & 63u)) c[r] = val;
+    }
+    // rank of a chosen position = chosen positions below it: the block's edges of a destination ascend by in-edge position
+    u32 rank[REGS];
+#pragma unroll
+    for (int r = 0; r < REGS; ++r) rank[r] = 0u;
+#pragma unroll
+    for (int q = 0; q < REGS; ++q) {
+        if ((u32)q * 64u >= k) break;
+        const u32 in_reg = k - (u32)q * 64u < 64u ? k - (u32)q * 64u : 64u;      // slots of register q in use
+        for (u32 l = 0; l < in_reg; ++l) {
+            const u32 b = (u32)__shfl((int)c[q], (int)l);
+#pragma unroll
+            for (int r = 0; r < REGS; ++r) rank[r] += b < c[r] ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < REGS; ++r)
+        if ((u32)r * 64u + lane < k) sel[base + rank[r]] = c[r];
+}
+
+// destination position of block edge e: the last i with off[i] <= e (off has n_dst + 1 entries, off[n_dst] = E_b > e)
+__device__ inline u32 owner_of(const u32* __restrict__ off, u32 n_dst, u32 e) {
+    u32 lo = 0, hi = n_dst;      // answer in [lo, hi)
+    while (hi - lo > 1u) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= e) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// sel[e]: in: the in-edge position of a sampled destination's edge (hop_floyd_kernel); out: the edge's GLOBAL source
+__global__ void hop_expand_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, const u32* __restrict__ ptr,
+                                  const int32_t* __restrict__ src_sorted, const int32_t* __restrict__ type_sorted,
+                                  const u32* __restrict__ off, const u32* __restrict__ map, u32* __restrict__ sel,
+                                  u32* __restrict__ bits, int64_t* __restrict__ edge_dst, int64_t* __restrict__ edge_type,
+                                  Results* __restrict__ res) {
+    const u32 total = off[n_dst];
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) res->num_edges = total;
+    for (u64 e64 = (u64)blockIdx.x * blockDim.x + threadIdx.x; e64 < total; e64 += stride) {
+        const u32 e = (u32)e64;
+        const u32 i = owner_of(off, n_dst, e);
+        const u32 first = off[i], count = off[i + 1] - first;
+        const int64_t v = dst_nodes[i];      // (in range: it has edges)
+        const u32 begin = ptr[v], d = ptr[v + 1] - begin;
+        const u32 p = count == d ? e - first : sel[e];
+        const u32 s = (u32)src_sorted[(u64)begin + p];
+        edge_dst[e] = (int64_t)i;
+        edge_type[e] = (int64_t)type_sorted[(u64)begin + p];
+        sel[e] = s;
+        if (map[s] == kNone) atomicOr(&bits[s >> 5], 1u << (s & 31u));
+    }
+}
+
+__global__ void hop_popcount_kernel(const u32* __restrict__ bits, u32 n_words, u32* __restrict__ wcnt) {
+    const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w > n_words) return;
+    wcnt[w] = w < n_words ? (u32)__popc(bits[w]) : 0u;      // (n_words + 1 entries: the scan of the last one is the total)
+}
+
+// woff = exclusive scan of the popcounts: bit b of word w is new source number woff[w] + (set bits of w below b)
+__global__ void hop_frontier_kernel(const u32* __restrict__ bits, u32 n_words, const u32* __restrict__ woff, u32 n_dst,
+                                    u32* __restrict__ map, int64_t* __restrict__ src_nodes, Results* __restrict__ res) {
+    const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w == 0) res->num_new = woff[n_words];
+    if (w >= n_words) return;
+    u32 m = bits[w], r = n_dst + woff[w];
+    while (m != 0u) {      // at most 32 trips
+        const u32 b = (u32)__ffs((int)m) - 1u;
+        m &= m - 1u;
+        const u32 s = w * 32u + b;
+        src_nodes[r] = (int64_t)s;
+        map[s] = r;
+        ++r;
+    }
+}
+
+__global__ void hop_relabel_kernel(const u32* __restrict__ off, u32 n_dst, const u32* __restrict__ sel, const u32* __restrict__ map,
+                                   int64_t* __restrict__ edge_src) {
+    const u32 total = off[n_dst];
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) edge_src[e] = (int64_t)map[sel[e]];
+}
+
+__global__ void hop_reset_dst_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, u32 n_nodes, u32* __restrict__ map) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_dst) return;
+    const int64_t v = dst_nodes[i];
+    if (v >= 0 && v < (int64_t)n_nodes) map[v] = kNone;
+}
+
+__global__ void hop_reset_new_kernel(const u32* __restrict__ bits, u32 n_words, u32* __restrict__ map) {
+    const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n_words) return;
+    u32 m = bits[w];
+    while (m != 0u) {
+        const u32 b = (u32)__ffs((int)m) - 1u;
+        m &= m - 1u;
+        map[w * 32u + b] = kNone;
+    }
+}
+
+struct HopWorkspace {
+    Results* res;
+    u32* cnt;       // n_dst + 1: counts, scanned in place into offsets
+    u32* sel;       // cap
+    u32* bits;      // n_words
+    u32* wcnt;      // n_words + 1: popcounts, scanned in place
+    u32* sums;
+    size_t bytes;
+};
+
+static u64 hop_cap(int64_t num_dst, int fanout, int64_t num_edges) {      // the most edges a block can hold
+    if (fanout < 0) return (u64)num_edges;
+    const u64 c = (u64)num_dst * (u64)fanout;
+    return c < (u64)num_edges ? c : (u64)num_edges;
+}
+
+static HopWorkspace carve_hop(void* base, u64 n_dst, u64 cap, u64 n_nodes) {
+    HopWorkspace w;
+    size_t off = 0;
+    auto take = [&](size_t nbytes) {
+        void* p = base ? (char*)base + off : nullptr;
+        off += align_up(nbytes);
+        return p;
+    };
+    const u64 n_words = (n_nodes + 31) / 32;
+    w.res = (Results*)take(sizeof(Results));
+    w.cnt = (u32*)take((n_dst + 1) * 4);
+    w.sel = (u32*)take(cap * 4);
+    w.bits = (u32*)take(n_words * 4);
+    w.wcnt = (u32*)take((n_words + 1) * 4);
+    const u64 scan_len = n_dst + 1 > n_words + 1 ? n_dst + 1 : n_words + 1;
+    w.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
+    w.bytes = off;
+    return w;
+}
+
+static int read_results(const Results* dev, Results* host, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(host, dev, sizeof(Results), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return (int)e;
+}
+
+static int check_hop_scalars(const rgcn_sample_index_t* ix, int64_t num_dst, int fanout, int64_t seed, int hop) {
+    if (ix->num_nodes <= 0 || ix->num_edges < 0 || (u64)ix->num_edges > kMaxKeys) return RGCN_ERR_PLAN;
+    if (fanout != -1 && (fanout < 1 || fanout > kMaxFanout)) return RGCN_ERR_ARG;
+    if (seed < 0 || hop < 0 || num_dst < 0 || num_dst > (int64_t)ix->num_nodes) return RGCN_ERR_ARG;
+    return RGCN_OK;
+}
+
+}  // namespace rgcn_sample
+
+using namespace rgcn_sample;
+
+extern "C" size_t rgcn_sample_index_workspace_bytes(int64_t num_edges, int32_t num_nodes) {
+    if (num_edges < 0 || num_nodes <= 0 || (u64)num_edges > kMaxKeys) return 0;
+    return carve_index(nullptr, (u64)num_edges, (u64)num_nodes).bytes;
+}
+
+extern "C" int rgcn_sample_index_build(const rgcn_graph_t* g, uint32_t* ptr_out, int32_t* src_out, int32_t* type_out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    if (g == nullptr) return RGCN_ERR_NULL;
+    if (g->num_edges < 0 || g->num_nodes <= 0 || g->num_relations <= 0 || g->num_relations > kMaxRelations) return RGCN_ERR_PLAN;
+    if ((u64)g->num_edges > kMaxKeys) return RGCN_ERR_PLAN;
+    if (g->num_edges > 0 && (!g->src || !g->dst || !g->type || !src_out || !type_out)) return RGCN_ERR_NULL;
+    if (!ptr_out || !workspace) return RGCN_ERR_NULL;
+    const u32 E = (u32)g->num_edges, N = (u32)g->num_nodes;
+    IndexWorkspace ws = carve_index(workspace, E, N);
+    if (workspace_bytes < ws.bytes) return RGCN_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.res, 0, sizeof(Results), s);
+    if (e == hipSuccess) e = hipMemsetAsync(ptr_out, 0, ((size_t)N + 1) * 4, s);
+    if (e != hipSuccess) return (int)e;
+    if (E > 0) {
+        hipLaunchKernelGGL(index_keys_kernel, dim3(grid_for(E)), dim3(256), 0, s, g->src, g->src_stride, g->dst, g->dst_stride,
+                           g->type, g->type_stride, E, N, (u32)g->num_relations, ws.sb.k[0], ws.sb.v[0], ptr_out, ws.res);
+        const int c = radix_sort_pairs(ws.sb, E, bits_for((u64)N - 1), s);
+        hipLaunchKernelGGL(index_gather_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.sb.v[c], E, g->src, g->src_stride, g->type,
+                           g->type_stride, N, (u32)g->num_relations, src_out, type_out);
+    }
+    exclusive_scan(ptr_out, ptr_out, N + 1u, ws.sb.sums, s);      // in-degrees -> ptr, ptr[N] = E
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    Results r;
+    int st = read_results(ws.res, &r, s);
+    if (st != 0) return st;
+    return r.error ? RGCN_ERR_GRAPH : RGCN_OK;
+}
+
+extern "C" size_t rgcn_sample_hop_workspace_bytes(int64_t num_dst, int fanout, int64_t num_edges, int32_t num_nodes) {
+    if (num_edges < 0 || num_nodes <= 0 || (u64)num_edges > kMaxKeys || num_dst < 0 || num_dst > (int64_t)num_nodes) return 0;
+    if (fanout != -1 && (fanout < 1 || fanout > kMaxFanout)) return 0;
+    return carve_hop(nullptr, (u64)num_dst, hop_cap(num_dst, fanout, num_edges), (u64)num_nodes).bytes;
+}
+
+extern "C" int rgcn_sample_hop(const rgcn_sample_index_t* ix, const int64_t* dst_nodes, int64_t num_dst, int fanout, int64_t seed,
+                               int hop, uint32_t* node_map, int64_t* edge_src_out, int64_t* edge_dst_out, int64_t* edge_type_out,
+                               int64_t* src_nodes_out, void* workspace, size_t workspace_bytes, int64_t* num_edges_out,
+                               int64_t* num_src_out, void* stream) {
+    if (ix == nullptr) return RGCN_ERR_NULL;
+    int st = check_hop_scalars(ix, num_dst, fanout, seed, hop);
+    if (st != RGCN_OK) return st;
+    if (!ix->ptr || !node_map || !workspace || !num_edges_out || !num_src_out) return RGCN_ERR_NULL;
+    if (ix->num_edges > 0 && (!ix->src || !ix->type)) return RGCN_ERR_NULL;
+    const u64 cap = hop_cap(num_dst, fanout, ix->num_edges);
+    if (num_dst > 0 && !dst_nodes) return RGCN_ERR_NULL;
+    if (num_dst > 0 && !src_nodes_out) return RGCN_ERR_NULL;
+    if (cap > 0 && (!edge_src_out || !edge_dst_out || !edge_type_out)) return RGCN_ERR_NULL;
+    const u32 N = (u32)ix->num_nodes, nd = (u32)num_dst, n_words = (N + 31u) / 32u;
+    HopWorkspace ws = carve_hop(workspace, nd, cap, N);
+    if (workspace_bytes < ws.bytes) return RGCN_ERR_WORKSPACE;
+    if (nd == 0) {
+        *num_edges_out = 0;
+        *num_src_out = 0;
+        return RGCN_OK;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.res, 0, sizeof(Results), s);
+    if (e == hipSuccess) e = hipMemsetAsync(ws.bits, 0, (size_t)n_words * 4, s);
+    if (e != hipSuccess) return (int)e;
+    const u64 key = mix((u64)seed + 0x9E3779B97F4A7C15ull * ((u64)hop + 1ull));
+
+    hipLaunchKernelGGL(hop_mark_kernel, dim3(grid_for(nd)), dim3(256), 0, s, dst_nodes, nd, N, node_map, src_nodes_out, ws.res);
+    hipLaunchKernelGGL(hop_count_kernel, dim3(grid_for((u64)nd + 1)), dim3(256), 0, s, dst_nodes, nd, N, ix->ptr, fanout, node_map,
+                       ws.cnt, ws.res);
+    exclusive_scan(ws.cnt, ws.cnt, nd + 1u, ws.sums, s);
+    if (cap > 0) {
+        if (fanout > 0) {
+            const dim3 grid(grid_for((u64)nd, 4)), block(256);      // four waves, four destinations per workgroup
+            const u32 k = (u32)fanout;
+            if (k <= 64)
+                hipLaunchKernelGGL(hop_floyd_kernel<1>, grid, block, 0, s, dst_nodes, nd, ix->ptr, k, key, ws.cnt, ws.sel);
+            else if (k <= 128)
+                hipLaunchKernelGGL(hop_floyd_kernel<2>, grid, block, 0, s, dst_nodes, nd, ix->ptr, k, key, ws.cnt, ws.sel);
+            else if (k <= 192)
+                hipLaunchKernelGGL(hop_floyd_kernel<3>, grid, block, 0, s, dst_nodes, nd, ix->ptr, k, key, ws.cnt, ws.sel);
+            else
+                hipLaunchKernelGGL(hop_floyd_kernel<4>, grid, block, 0, s, dst_nodes, nd, ix->ptr, k, key, ws.cnt, ws.sel);
+        }
+        u32 eg = grid_for(cap);
+        if (eg > kEdgeGridMax) eg = kEdgeGridMax;
+        hipLaunchKernelGGL(hop_expand_kernel, dim3(eg), dim3(256), 0, s, dst_nodes, nd, ix->ptr, ix->src, ix->type, ws.cnt, node_map,
+                           ws.sel, ws.bits, edge_dst_out, edge_type_out, ws.res);
+        hipLaunchKernelGGL(hop_popcount_kernel, dim3(grid_for((u64)n_words + 1)), dim3(256), 0, s, ws.bits, n_words, ws.wcnt);
+        exclusive_scan(ws.wcnt, ws.wcnt, n_words + 1u, ws.sums, s);
+        hipLaunchKernelGGL(hop_frontier_kernel, dim3(grid_for(n_words)), dim3(256), 0, s, ws.bits, n_words, ws.wcnt, nd, node_map,
+                           src_nodes_out, ws.res);
+        hipLaunchKernelGGL(hop_relabel_kernel, dim3(eg), dim3(256), 0, s, ws.cnt, nd, ws.sel, node_map, edge_src_out);
+        hipLaunchKernelGGL(hop_reset_new_kernel, dim3(grid_for(n_words)), dim3(256), 0, s, ws.bits, n_words, node_map);
+    }
+    hipLaunchKernelGGL(hop_reset_dst_kernel, dim3(grid_for(nd)), dim3(256), 0, s, dst_nodes, nd, N, node_map);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    Results r;
+    if ((st = read_results(ws.res, &r, s)) != 0) return st;
+    if (r.error & kErrRange) return RGCN_ERR_GRAPH;
+    if (r.error & kErrDuplicate) return RGCN_ERR_ARG;
+    *num_edges_out = (int64_t)r.num_edges;
+    *num_src_out = (int64_t)nd + (int64_t)r.num_new;
+    return RGCN_OK;
+}

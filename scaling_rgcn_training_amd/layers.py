@@ -47,6 +47,28 @@ class _RGCNStack(nn.Module):
             return self.rgcn2(h, ei, et, _activation="sigmoid", _input_relu=True)
         return activation(self.rgcn2(h, ei, et, _input_relu=True))
 
+    def _tail_blocks(self, x: Tensor, blocks, activation: Callable) -> Tensor:
+        """The same two layers over sampled blocks (sampling.NeighborSampler.sample): ``x`` holds the rows ``blocks[0].src_nodes``
+        of the layer input, a block's destinations are its first ``n_dst`` source rows.  The bipartite layer fuses no
+        activation: both run as torch ops.  Returns the rows of ``blocks[1]``'s destinations, the seeds."""
+        b0, b1 = blocks
+        if x.shape[0] != b0.n_src or b0.n_dst != b1.n_src:
+            raise ValueError(f"blocks do not chain: x has {x.shape[0]} rows, blocks[0] is {b0.n_src} -> {b0.n_dst}, "
+                             f"blocks[1] is {b1.n_src} -> {b1.n_dst}")
+        h = F.relu(self.rgcn1((x, x[:b0.n_dst]), b0.edge_index, b0.edge_type))
+        return activation(self.rgcn2((h, h[:b1.n_dst]), b1.edge_index, b1.edge_type))
+
+    def forward_blocks(self, blocks, activation: Callable) -> Tensor:
+        """``forward`` on the two sampled blocks of a mini-batch: every model gathers the rows ``blocks[0].src_nodes`` of its
+        embedding BEFORE its own pre-transform (``_block_input``), so that nothing runs over the whole graph.  Returns the seeds'
+        rows ``[blocks[1].n_dst, num_labels]``.  Eager torch activations; ``forward`` is untouched."""
+        if len(blocks) != 2:
+            raise ValueError(f"the models have two RGCN layers: forward_blocks takes 2 blocks, got {len(blocks)}")
+        return self._tail_blocks(self._block_input(blocks[0].src_nodes), blocks, activation)
+
+    def _block_input(self, nodes: Tensor) -> Tensor:
+        raise NotImplementedError
+
     def override_params(self, weight_1: Tensor, bias_1: Tensor, root_1: Tensor, weight_2: Tensor,
                         bias_2: Tensor, root_2: Tensor, grad: bool = True) -> None:
         """Re-bind both convs' parameters to fresh ``nn.Parameter`` objects (weight transfer from the
@@ -69,6 +91,9 @@ class Emb_Layers(_RGCNStack):
     def forward(self, training_data: Data, activation: Callable) -> Tensor:
         return self._tail(self.embedding.weight, training_data, activation)
 
+    def _block_input(self, nodes: Tensor) -> Tensor:
+        return self.embedding(nodes)
+
     def reset_embedding(self, num_nodes: int, emb_dim: int) -> None:
         self.embedding = nn.Embedding(num_nodes, emb_dim)
 
@@ -90,6 +115,11 @@ class Emb_ATT_Layers(_RGCNStack):
     def forward(self, training_data: Data, activation: Callable) -> Tensor:
         attn_output, _ = self.att(self.embedding, self.embedding, self.embedding, average_attn_weights=True)
         return self._tail(attn_output[0], training_data, activation)
+
+    def _block_input(self, nodes: Tensor) -> Tensor:
+        emb = self.embedding[:, nodes]      # the node axis: attention runs over the S axis of the gathered nodes only
+        attn_output, _ = self.att(emb, emb, emb, average_attn_weights=True)
+        return attn_output[0]
 
     def load_embedding(self, embedding: Tensor, freeze: bool = True) -> None:
         self.embedding = nn.Parameter(embedding, requires_grad=not freeze)
@@ -114,6 +144,9 @@ class Emb_MLP_Layers(_RGCNStack):
     def forward(self, training_data: Data, activation: Callable, save=False) -> Tensor:
         x = self.lin2(torch.tanh(self.lin1(self.embedding.weight)))
         return self._tail(x, training_data, activation)
+
+    def _block_input(self, nodes: Tensor) -> Tensor:
+        return self.lin2(torch.tanh(self.lin1(self.embedding(nodes))))
 
     def load_embedding(self, embedding: Tensor, freeze: bool = True) -> None:
         self.embedding = nn.Embedding.from_pretrained(embedding, freeze=freeze)

@@ -1,0 +1,91 @@
+"""Neighbour sampling on the GPU (csrc/rgcn_sample.hip): fan-out sampling of in-edges into the layered bipartite
+blocks a mini-batch step walks -- what PyG's ``NeighborLoader`` / DGL's ``sample_neighbors`` do on the host.
+
+``NeighborSampler`` builds the in-edge index of a graph once (edges sorted stably by destination); ``sample(seeds, fanouts,
+seed)`` returns one ``Block`` per model layer, sampled from the last layer back: ``blocks[-1]`` has the seeds as destinations,
+``blocks[i]`` the source nodes of ``blocks[i + 1]``.  A block's ``src_nodes`` start with its destinations, so a layer runs as
+``conv((x, x[:block.n_dst]), block.edge_index, block.edge_type)`` with ``x`` the rows ``src_nodes`` of its input.
+
+The choice of a destination's in-edges is a pure function of ``(seed, layer, global node id)`` (a counter-based generator and
+Floyd's k-subset algorithm): it depends neither on the other nodes of the batch nor on launch geometry, and two calls return equal
+tensors.  There is no CPU path: every argument is checked on the host, then the HIP library does the work.
+"""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Sequence
+
+import torch
+from torch import Tensor
+
+from .summaries import _check_coo, _need_gpu
+
+MAX_FANOUT = 256
+
+
+class Block(NamedTuple):
+    edge_index: Tensor      # int64 [2, E_b]: positions in src_nodes (row 0) and among the destinations (row 1)
+    edge_type: Tensor       # int64 [E_b]
+    n_src: int
+    n_dst: int
+    src_nodes: Tensor       # int64 [n_src] global node ids; src_nodes[:n_dst] are the destinations
+
+
+def check_fanouts(fanouts) -> List[int]:
+    """a non-empty sequence of ints in {-1} u [1, 256]"""
+    if isinstance(fanouts, (str, bytes)) or not isinstance(fanouts, Sequence) or len(fanouts) == 0:
+        raise ValueError(f"fanouts must be a non-empty sequence of ints, one per layer (got {fanouts!r})")
+    for k in fanouts:
+        if isinstance(k, bool) or not isinstance(k, int) or not (k == -1 or 1 <= k <= MAX_FANOUT):
+            raise ValueError(f"a fan-out must be -1 (all in-edges) or an int in 1 .. {MAX_FANOUT} (got {k!r})")
+    return list(fanouts)
+
+
+def check_seeds(seeds, num_nodes: int) -> None:
+    """int64 [n], unique, in [0, num_nodes): one reduction where the seeds live"""
+    if not torch.is_tensor(seeds) or seeds.dim() != 1 or seeds.dtype != torch.int64:
+        raise ValueError("seeds must be a 1-d int64 tensor")
+    if seeds.numel():
+        s = torch.sort(seeds).values
+        lo, hi, repeats = torch.stack([s[0], s[-1], (s[1:] == s[:-1]).sum()]).tolist()
+        if lo < 0 or hi >= num_nodes:
+            raise ValueError(f"seeds must lie in [0, {num_nodes}) (got [{lo}, {hi}])")
+        if repeats:
+            raise ValueError("seeds must be unique")
+
+
+def check_sample_seed(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 63:
+        raise ValueError(f"seed must be an int in [0, 2^63) (got {seed!r})")
+    return seed
+
+
+class NeighborSampler:
+    """``NeighborSampler(edge_index [2, E], edge_type [E], num_nodes, num_relations)`` on GPU tensors (``edge_index`` may be the
+    strided rows of a transposed [E, 3] tensor).  Builds the index once and owns its arrays (12 bytes per edge, 8 per node)."""
+
+    def __init__(self, edge_index: Tensor, edge_type: Tensor, num_nodes: int, num_relations: int):
+        from . import _lib
+        _check_coo(edge_index, edge_type, num_nodes, num_relations)
+        _need_gpu(edge_index, "NeighborSampler")
+        self.num_nodes, self.num_relations = num_nodes, num_relations
+        self.num_edges = int(edge_type.shape[0])
+        self.device = edge_index.device
+        graph, keep = _lib.graph_struct(edge_index, edge_type, num_nodes, num_relations)
+        self._index, self._arrays = _lib.sample_index_build(graph, self.device)
+        del keep
+        # node id -> position in the block being built; all "none" (-1) between hops, which reset only what they wrote
+        self._map = torch.full((num_nodes,), -1, dtype=torch.int32, device=self.device)
+
+    def sample(self, seeds: Tensor, fanouts: Sequence[int], seed: int = 0) -> List[Block]:
+        """``blocks[0 .. L-1]``, ``fanouts[i]`` belonging to model layer ``i``.  One host synchronisation per layer."""
+        from . import _lib
+        fanouts = check_fanouts(fanouts)
+        seed = check_sample_seed(seed)
+        check_seeds(seeds, self.num_nodes)
+        dst = seeds.to(self.device).contiguous()
+        blocks = []
+        for i in reversed(range(len(fanouts))):
+            ei, et, src_nodes = _lib.sample_hop(self._index, dst, fanouts[i], seed, i, self._map)
+            blocks.append(Block(ei, et, int(src_nodes.shape[0]), int(dst.shape[0]), src_nodes))
+            dst = src_nodes
+        return blocks[::-1]

@@ -1,4 +1,4 @@
-"""Full-batch training loop with the reference's ``Trainer`` API
+"""Full-batch training loop (and ``Trainer.train_minibatch``, its neighbour-sampled form) with the reference's ``Trainer`` API
 (/root/reference/model/modelTrainer.py:15-116) and the loss / activation / metric helpers of
 /root/reference/model/evaluation.py, re-provided so the HIP layer can be dropped into the same
 experiment flow.  SURVEY.md 8f-2: the step either side of the hot path.
@@ -116,6 +116,7 @@ class Trainer:
         # capturable as it is.  ``last_train_mode`` records what the last ``train`` call did ("hipgraph" / "eager").
         self.hipgraph = hipgraph
         self.last_train_mode = None
+        self.last_batches = []      # train_minibatch: the batches (node ids) of the last epoch
 
     def transfer_weights(self, orgModel: nn.Module, grad: bool) -> None:
         s = self.sumModel
@@ -197,6 +198,84 @@ class Trainer:
             optimizer.step()
             loss_value = output.item()
             losses.append(loss_value)
+            if self.verbose and epoch % 10 == 0:
+                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}")
+        return accuracies, losses, f1_ws, f1_ms
+
+    def _sampler(self, graph, training_data, model: nn.Module):
+        """the graph's ``NeighborSampler`` on the device edges, cached on the graph beside ``_device_edges`` (same key: the
+        in-edge index is built once per graph and device)"""
+        from .sampling import NeighborSampler
+        key = getattr(graph, "_device_edges", (None,))[0]
+        cached = getattr(graph, "_sampler", None)
+        if cached is None or key is None or cached[0] != key:
+            num_nodes = getattr(graph, "num_nodes", None)
+            if num_nodes is None:      # the rows of the model's embedding ([S, N, emb] in the attention model)
+                emb = model.embedding
+                num_nodes = emb.num_embeddings if isinstance(emb, nn.Embedding) else emb.shape[-2]
+            cached = (key, NeighborSampler(training_data.edge_index, training_data.edge_type, int(num_nodes),
+                                           int(model.rgcn1.num_relations)))
+            try:
+                graph._sampler = cached
+            except AttributeError:
+                pass
+        return cached[1]
+
+    def train_minibatch(self, model: nn.Module, graph, loss_f: Callable, activation: Callable, batch_size: int,
+                        fanouts, sum_graph: bool = True, seed: int = 0) -> Tuple[List[float], List[float], List[float], List[float]]:
+        """``train`` with neighbour sampling: per epoch the full-batch validation forward exactly as ``train`` does it (when
+        ``not sum_graph``), then a seeded permutation of ``x_train`` cut into batches of ``batch_size`` (the last may be short)
+        and ONE optimizer step per batch on the blocks ``NeighborSampler.sample(batch, fanouts, step seed)`` returns, through
+        ``model.forward_blocks``.  The step seed is a fixed odd-multiplier combination of ``seed``, the epoch and the batch index
+        (mod 2^63; the sampler mixes it): runs repeat, steps differ.  The epoch's
+        loss is the mean over its batches.  Eager only -- block shapes change every step, nothing is captured.  Returns the four
+        lists of ``train``; ``self.last_batches`` holds the last epoch's batches (tensors of node ids)."""
+        from .sampling import check_fanouts, check_sample_seed
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"batch_size must be an int >= 1 (got {batch_size!r})")
+        fanouts = check_fanouts(fanouts)
+        if len(fanouts) != 2:
+            raise ValueError(f"the models have two RGCN layers: fanouts takes 2 entries, got {len(fanouts)}")
+        seed = check_sample_seed(seed)
+        model = model.to(self.device)
+        training_data = self._device_data(graph)
+        sampler = self._sampler(graph, training_data, model)
+        targets = training_data.y_train.to(torch.float32)
+        x_train = training_data.x_train.to(self.device)
+        n_train = int(x_train.shape[0])
+        self.last_train_mode = "eager"
+        self.last_batches = []
+        optimizer = torch.optim.Adam(model.parameters(), lr=self.lr, weight_decay=self.weight_d)
+        perm_gen = torch.Generator().manual_seed(seed)
+        accuracies, losses, f1_ws, f1_ms = [], [], [], []
+        for epoch in range(self.epochs):
+            if not sum_graph:
+                model.eval()
+                acc, f1_w, f1_m = evaluate(model, activation, training_data, training_data.x_val,
+                                           training_data.y_val, no_grad=self.eval_no_grad)
+                if self.verbose:
+                    print(f"Accuracy on validation set = {acc}")
+                accuracies.append(acc)
+                f1_ws.append(f1_w)
+                f1_ms.append(f1_m)
+            model.train()
+            perm = torch.randperm(n_train, generator=perm_gen).to(self.device)
+            batch_losses, batches = [], []
+            for b, start in enumerate(range(0, n_train, batch_size)):
+                rows = perm[start:start + batch_size]
+                batch = x_train[rows]
+                step_seed = (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
+                blocks = sampler.sample(batch, fanouts, step_seed)
+                optimizer.zero_grad()
+                out = model.forward_blocks(blocks, activation)
+                output = loss_f(out, targets[rows])
+                output.backward()
+                optimizer.step()
+                batch_losses.append(output.detach())
+                batches.append(batch)
+            loss_value = float(torch.stack(batch_losses).mean().item()) if batch_losses else float("nan")
+            losses.append(loss_value)
+            self.last_batches = batches
             if self.verbose and epoch % 10 == 0:
                 print(f"Epoch: {epoch}, Loss: {loss_value:.4f}")
         return accuracies, losses, f1_ws, f1_ms
