@@ -66,7 +66,7 @@ enum rgcn_status {
     RGCN_ERR_WORKSPACE = -6, /* workspace smaller than the *_workspace_bytes query */
     RGCN_ERR_DEVICE = -7,    /* current device is not gfx950 / no device */
     RGCN_ERR_ACT = -8,       /* unknown activation code */
-    RGCN_ERR_GRAPH = -9,     /* rgcn_plan_build: an edge_index / edge_type value is out of range */
+    RGCN_ERR_GRAPH = -9,     /* rgcn_plan_build, rgcn_sample_*, rgcn_mb_index_build: an edge_index / edge_type value is out of range */
     RGCN_ERR_ADDRESS = -10,  /* rgcn_bwd_dw_tiles: a gathered matrix cannot be addressed through a buffer descriptor (2^24 rows or
                               * 4 GiB and more): use rgcn_bwd_dw, whose kernels fall back to 64-bit pointers */
     RGCN_ERR_ARG = -11       /* rgcn_sample_*: a scalar argument outside its domain (fan-out, seed, hop, number of destinations),
@@ -495,6 +495,76 @@ int rgcn_sample_index_build(const rgcn_graph_t* graph, uint32_t* ptr_out, int32_
 int rgcn_sample_hop(const rgcn_sample_index_t* index, const int64_t* dst_nodes, int64_t num_dst, int fanout, int64_t seed, int hop,
                     uint32_t* node_map, int64_t* edge_src_out, int64_t* edge_dst_out, int64_t* edge_type_out, int64_t* src_nodes_out,
                     void* workspace, size_t workspace_bytes, int64_t* num_edges_out, int64_t* num_src_out, void* stream);
+
+/* ---- mini-batch layers: a bipartite R-GCN layer straight from a sampled block (csrc/rgcn_minibatch.hip) ----------
+ * ("block" in this header already means block-diagonal weights: hence rgcn_mb_.)  For a block of E_b edges (strided int64 src /
+ * dst / type, src in [0, n_src), dst in [0, n_dst), type in [0, R)) whose destinations are its first n_dst source rows
+ * (n_dst <= n_src) and x [n_src, in]:  out[i] = bias + x[i] root + sum_r aggregate over the edges of relation r into i of x[src] W_r,
+ * mean (divided by the number of edges of the (destination, relation) pair, duplicates counted) or sum.  No graph plan: ONE index
+ * per block serves forward, dX and d_weight.  No order is required of the edges.
+ * Index.  The root is relation R with one pseudo edge i -> i per destination: M = E_b + n_dst edges, sorted stably by (relation,
+ * destination); everything below refers to POSITIONS in that order.  A run of equal (relation, destination) is cut into rows of at
+ * most 256 consecutive positions, each with scale = 1 / run length (mean) or 1 (sum).  Rows lie relation-major in tiles of 16 row
+ * slots that never straddle a relation: the tiles of relation r are tile_ptr[r] .. tile_ptr[r + 1], its rows fill their slots from
+ * the first on, the slots left over in its last tile are empty (row_cnt == 0, row_scale == 0).  n_tiles = tile_ptr[R + 1]; row
+ * slot = 16 * tile + (0 .. 15).
+ *   edge_src [M]            source of every position
+ *   row_beg / row_cnt       [16 n_tiles] first position and number of positions (1 .. 256; 0: empty) of a slot's row
+ *   row_dst / row_scale     [16 n_tiles] its destination and scale
+ *   dst_ptr [n_dst + 1], dst_rows [n_rows]   the row slots of every destination, ascending relation within it
+ *   src_ptr [n_src + 1], src_row / src_scale [M]   row slot and scale of every position, grouped by source, ascending position
+ * Limits: n_src, n_dst < 2^31, E_b + n_dst <= 0xFFFF0000, R <= 65536, 16 (M / 16 + R + 1) < 2^32, widths 1..128: RGCN_ERR_PLAN
+ * beyond; negative counts or n_dst > n_src: RGCN_ERR_ARG; an id out of range (found on the device): RGCN_ERR_GRAPH.  A refused
+ * call launches nothing.
+ * The build allocates nothing and SYNCHRONISES the stream once, to read the error word, the row count and the tile count back;
+ * the three layer calls are asynchronous.  No float atomics: the same block and inputs give the same bits. */
+typedef struct rgcn_mb_index {
+    const int32_t* tile_ptr;   /* [num_relations + 2] */
+    const uint32_t* row_beg;   /* [16 n_tiles] */
+    const int32_t* row_cnt;
+    const int32_t* row_dst;
+    const float* row_scale;
+    const int32_t* edge_src;   /* [num_edges + n_dst] */
+    const uint32_t* dst_ptr;   /* [n_dst + 1] */
+    const uint32_t* dst_rows;  /* [n_rows] */
+    const uint32_t* src_ptr;   /* [n_src + 1] */
+    const uint32_t* src_row;   /* [num_edges + n_dst] */
+    const float* src_scale;
+    int64_t num_edges;         /* E_b */
+    int64_t n_rows;            /* non-empty row slots */
+    int32_t n_src, n_dst, num_relations;
+    int32_t mean;              /* 1: mean, 0: sum */
+    int32_t n_tiles;
+    int32_t reserved;
+} rgcn_mb_index_t;
+
+/* Bytes of the index arena / of the build's scratch (0 on arguments the build would refuse).  Larger buffers serve. */
+size_t rgcn_mb_index_bytes(int64_t num_edges, int64_t n_src, int64_t n_dst, int32_t num_relations);
+size_t rgcn_mb_index_workspace_bytes(int64_t num_edges, int64_t n_src, int64_t n_dst, int32_t num_relations);
+
+/* Builds the index into the caller's arena `index_mem` and fills *index_out (host) with pointers into it and the counts.  src / dst /
+ * type may be NULL when num_edges == 0.  n_dst == 0 (then num_edges must be 0) gives an index without tiles and reads nothing back. */
+int rgcn_mb_index_build(const int64_t* src, int64_t src_stride, const int64_t* dst, int64_t dst_stride, const int64_t* type,
+                        int64_t type_stride, int64_t num_edges, int64_t n_src, int64_t n_dst, int32_t num_relations, int mean,
+                        void* index_mem, size_t index_bytes, void* workspace, size_t workspace_bytes, rgcn_mb_index_t* index_out,
+                        void* stream);
+
+/* Forward.  packed_w: rgcn_pack_weights* of the layer (relation R = root, zeros without one).  h [16 n_tiles][ldh] receives the
+ * aggregated rows (keep it for rgcn_mb_bwd_dw), z [16 n_tiles][ldz] their products, out [n_dst][ldo] the layer output; bias
+ * [out] or NULL.  n_dst == 0 launches nothing. */
+int rgcn_mb_fwd(const rgcn_mb_index_t* index, const float* x, int ldx, int din, const float* packed_w, const float* bias, float* h,
+                int ldh, float* z, int ldz, float* out, int ldo, int dout, void* stream);
+
+/* dX [n_src][lddx] from g [n_dst][ldg] = dL/d out: the root's g root^T included in the first n_dst rows, zeros in rows no edge
+ * reads.  packed_wt: the transposed pack.  dh [16 n_tiles][lddh]: scratch. */
+int rgcn_mb_bwd_dx(const rgcn_mb_index_t* index, const float* g, int ldg, int dout, const float* packed_wt, float* dh, int lddh,
+                   float* dx, int lddx, int din, void* stream);
+
+/* d_weight [R][din][dout] (dense) and d_root [din][dout], either may be NULL, from the forward's h.  A relation's tiles are cut
+ * into a number of slabs fixed by (n_tiles, R, din, dout) and the slabs added in order; the query gives the slabs' bytes (0: none). */
+size_t rgcn_mb_bwd_dw_workspace_bytes(const rgcn_mb_index_t* index, int din, int dout);
+int rgcn_mb_bwd_dw(const rgcn_mb_index_t* index, const float* h, int ldh, int din, const float* g, int ldg, int dout, float* d_weight,
+                   float* d_root, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

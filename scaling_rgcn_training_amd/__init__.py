@@ -14,7 +14,8 @@ Sub-modules:
 * ``summaries`` -- attribute-summary generation (murmur3 x64-128 of predicate sets; graphs/createAttributeSum.py), and on
   the GPU ``node_partition`` (k-bisimulation partition refinement) / ``quotient_graph`` over the layer's int64 COO
 * ``sampling`` -- ``NeighborSampler``: fan-out neighbour sampling on the GPU into the layered bipartite ``Block`` lists that
-  ``forward_blocks`` / ``Trainer.train_minibatch`` walk
+  ``forward_blocks`` / ``Trainer.train_minibatch`` walk; ``block_index`` / ``BlockIndex``: the index ``RGCNConv.forward_block``
+  runs a layer from, straight from a block, without graph plans
 
 There is no CPU compute path: the layer raises if the HIP library or a GPU is missing.
 """
@@ -40,7 +41,7 @@ def __getattr__(name):
     if name in ("create_sum_map", "hash128", "node_partition", "quotient_graph", "Partition"):
         from . import summaries
         return getattr(summaries, name)
-    if name in ("NeighborSampler", "Block"):
+    if name in ("NeighborSampler", "Block", "BlockIndex", "block_index"):
         from . import sampling
         return getattr(sampling, name)
     raise AttributeError(name)

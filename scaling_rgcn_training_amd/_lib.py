@@ -57,6 +57,15 @@ class RgcnSampleIndex(C.Structure):
                 ("num_edges", C.c_int64), ("num_nodes", C.c_int32), ("num_relations", C.c_int32)]
 
 
+class RgcnMbIndex(C.Structure):
+    """struct rgcn_mb_index: the index of one sampled block (rgcn_mb_index_build)"""
+    _fields_ = [("tile_ptr", C.c_void_p), ("row_beg", C.c_void_p), ("row_cnt", C.c_void_p), ("row_dst", C.c_void_p),
+                ("row_scale", C.c_void_p), ("edge_src", C.c_void_p), ("dst_ptr", C.c_void_p), ("dst_rows", C.c_void_p),
+                ("src_ptr", C.c_void_p), ("src_row", C.c_void_p), ("src_scale", C.c_void_p),
+                ("num_edges", C.c_int64), ("n_rows", C.c_int64), ("n_src", C.c_int32), ("n_dst", C.c_int32),
+                ("num_relations", C.c_int32), ("mean", C.c_int32), ("n_tiles", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RgcnPlanSizes(C.Structure):
     """struct rgcn_plan_sizes"""
     _fields_ = [("n_tiles", C.c_int32), ("n_chunks", C.c_int32), ("n_units", C.c_int32), ("reserved", C.c_int32),
@@ -118,6 +127,13 @@ def _prototypes() -> dict:
         "rgcn_sample_index_build": (i32, [graph, vp, vp, vp, vp, sz, vp]),
         "rgcn_sample_hop": (i32, [C.POINTER(RgcnSampleIndex), vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, sz,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
+        "rgcn_mb_index_bytes": (sz, [i64, i64, i64, i32]),
+        "rgcn_mb_index_workspace_bytes": (sz, [i64, i64, i64, i32]),
+        "rgcn_mb_index_build": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, i32, vp, sz, vp, sz, C.POINTER(RgcnMbIndex), vp]),
+        "rgcn_mb_fwd": (i32, [C.POINTER(RgcnMbIndex), vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, vp]),
+        "rgcn_mb_bwd_dx": (i32, [C.POINTER(RgcnMbIndex), vp, i32, i32, vp, vp, i32, vp, i32, i32, vp]),
+        "rgcn_mb_bwd_dw_workspace_bytes": (sz, [C.POINTER(RgcnMbIndex), i32, i32]),
+        "rgcn_mb_bwd_dw": (i32, [C.POINTER(RgcnMbIndex), vp, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
     }
 
 
@@ -480,6 +496,89 @@ def sample_hop(ix: RgcnSampleIndex, dst_nodes: torch.Tensor, fanout: int, seed: 
     if eb == cap:      # (no copy where the worst case was met)
         return edges[:2, :eb], edges[2, :eb], nodes[:nsrc].clone()
     return edges[:2, :eb].clone(), edges[2, :eb].clone(), nodes[:nsrc].clone()
+
+
+# ---- mini-batch layers straight from a sampled block (rgcn_minibatch.hip; sampling.block_index / conv._BlockFn drive them) ------
+_MB_ARRAYS = (("tile_ptr", torch.int32), ("row_beg", torch.int32), ("row_cnt", torch.int32), ("row_dst", torch.int32),
+              ("row_scale", torch.float32), ("edge_src", torch.int32), ("dst_ptr", torch.int32), ("dst_rows", torch.int32),
+              ("src_ptr", torch.int32), ("src_row", torch.int32), ("src_scale", torch.float32))
+
+
+class MbIndex:
+    """The index of one block as rgcn_mb_index_build made it.  It owns its arena; ``struct`` is what the layer calls take; the
+    attributes named in ``_MB_ARRAYS`` are views of the arena's valid parts (uint32 arrays read as int32: positions and slots of
+    the blocks a test or a step handles stay far below 2^31)."""
+
+    def __init__(self, struct: RgcnMbIndex, arena: torch.Tensor):
+        self.struct, self.arena = struct, arena
+        self.num_edges, self.n_src, self.n_dst = int(struct.num_edges), int(struct.n_src), int(struct.n_dst)
+        self.num_relations, self.mean = int(struct.num_relations), bool(struct.mean)
+        self.n_rows, self.n_tiles = int(struct.n_rows), int(struct.n_tiles)
+        self.n_slots = 16 * self.n_tiles
+        m = self.num_edges + self.n_dst
+        sizes = {"tile_ptr": self.num_relations + 2, "row_beg": self.n_slots, "row_cnt": self.n_slots, "row_dst": self.n_slots,
+                 "row_scale": self.n_slots, "edge_src": m, "dst_ptr": self.n_dst + 1, "dst_rows": self.n_rows,
+                 "src_ptr": self.n_src + 1, "src_row": m, "src_scale": m}
+        base = arena.data_ptr()
+        for name, dtype in _MB_ARRAYS:
+            off = (getattr(struct, name) or base) - base
+            setattr(self, name, arena[off:off + 4 * sizes[name]].view(dtype))
+
+
+def mb_index_build(edge_index: torch.Tensor, edge_type: torch.Tensor, n_src: int, n_dst: int, num_relations: int,
+                   mean: bool = True) -> MbIndex:
+    """rgcn_mb_index_build on the int64 device tensors of a block (strided rows allowed): one host synchronisation"""
+    lib, dev = load(), edge_index.device
+    src, dst = edge_index[0], edge_index[1]
+    if src.dtype != torch.int64:
+        src, dst = src.long(), dst.long()
+    typ = edge_type if edge_type.dtype == torch.int64 else edge_type.long()
+    e = int(typ.shape[0])
+    args = (e, int(n_src), int(n_dst), int(num_relations))
+    nbytes, wbytes = lib.rgcn_mb_index_bytes(*args), lib.rgcn_mb_index_workspace_bytes(*args)
+    st = RgcnMbIndex()
+    with torch.cuda.device(dev):
+        arena = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(wbytes, 1), dtype=torch.uint8, device=dev)
+        check(lib.rgcn_mb_index_build(src.data_ptr() if e else None, src.stride(0) if e else 1, dst.data_ptr() if e else None,
+                                      dst.stride(0) if e else 1, typ.data_ptr() if e else None, typ.stride(0) if e else 1, *args,
+                                      int(bool(mean)), arena.data_ptr(), nbytes, ws.data_ptr(), wbytes, C.byref(st), _stream(arena)),
+              "rgcn_mb_index_build")
+    return MbIndex(st, arena)
+
+
+def mb_fwd(ix: MbIndex, x: torch.Tensor, din: int, packed: torch.Tensor, bias: Optional[torch.Tensor], dout: int):
+    """(out [n_dst, round4(dout)], H [slots, round4(din)]) of rgcn_mb_fwd; ``x``: padded rows [n_src, ld]"""
+    dev, r4 = x.device, lambda w: (w + 3) // 4 * 4
+    with torch.cuda.device(dev):
+        h = torch.empty(ix.n_slots, r4(din), dtype=torch.float32, device=dev)
+        z = torch.empty(ix.n_slots, r4(dout), dtype=torch.float32, device=dev)
+        out = torch.empty(ix.n_dst, r4(dout), dtype=torch.float32, device=dev)
+        check(load().rgcn_mb_fwd(C.byref(ix.struct), x.data_ptr(), x.stride(0), din, packed.data_ptr(), _ptr(bias), h.data_ptr(),
+                                 h.stride(0), z.data_ptr(), z.stride(0), out.data_ptr(), out.stride(0), dout, _stream(x)), "rgcn_mb_fwd")
+    return out, h
+
+
+def mb_bwd_dx(ix: MbIndex, g: torch.Tensor, dout: int, packed_t: torch.Tensor, din: int) -> torch.Tensor:
+    """dX [n_src, round4(din)] of rgcn_mb_bwd_dx; ``g``: padded rows [n_dst, ld]"""
+    dev, ld = g.device, (din + 3) // 4 * 4
+    with torch.cuda.device(dev):
+        dh = torch.empty(ix.n_slots, ld, dtype=torch.float32, device=dev)
+        dx = torch.empty(ix.n_src, ld, dtype=torch.float32, device=dev)
+        check(load().rgcn_mb_bwd_dx(C.byref(ix.struct), g.data_ptr(), g.stride(0), dout, packed_t.data_ptr(), dh.data_ptr(), ld,
+                                    dx.data_ptr(), ld, din, _stream(g)), "rgcn_mb_bwd_dx")
+    return dx
+
+
+def mb_bwd_dw(ix: MbIndex, h: torch.Tensor, din: int, g: torch.Tensor, dout: int, d_weight: Optional[torch.Tensor],
+              d_root: Optional[torch.Tensor]) -> None:
+    """dense d_W [R, din, dout] and d_root [din, dout] (either None) of rgcn_mb_bwd_dw from the forward's H"""
+    lib, dev = load(), g.device
+    nbytes = lib.rgcn_mb_bwd_dw_workspace_bytes(C.byref(ix.struct), din, dout)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        check(lib.rgcn_mb_bwd_dw(C.byref(ix.struct), h.data_ptr(), h.stride(0), din, g.data_ptr(), g.stride(0), dout, _ptr(d_weight),
+                                 _ptr(d_root), _ptr(ws), nbytes, _stream(g)), "rgcn_mb_bwd_dw")
 
 
 # ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------

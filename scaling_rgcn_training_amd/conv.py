@@ -736,6 +736,54 @@ class _BipartiteFn(torch.autograd.Function):
         return dxs, dxd, dw, dcomp, droot, dbias, None, None, None, None
 
 
+class _BlockFn(torch.autograd.Function):
+    """out [n_dst, out] = sum_r aggregate_r(x) @ W_r + x[:n_dst] @ root + bias on one sampling.BlockIndex (csrc/rgcn_minibatch.hip):
+    the root is relation R of the index, so one transform + one sum per direction and one d_weight launch make the whole layer;
+    the aggregated rows H of the forward are kept for d_weight.  No graph plan, no plan cache."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, comp: Optional[Tensor], root: Optional[Tensor], bias: Optional[Tensor], index,
+                num_rel: int, dout: int):
+        n_src, din = x.shape
+        wf, cp, rt, bs = _operands(weight, comp, root, bias)
+        ctx.index, ctx.dims = index, (n_src, din, dout, num_rel)
+        if index.n_dst == 0:
+            ctx.save_for_backward(wf, cp, rt)
+            return torch.empty(0, dout, dtype=torch.float32, device=x.device)
+        xp = _rows16(x, din)
+        packed = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=False)
+        out, hmat = _lib.mb_fwd(index._ix, xp, din, packed, bs, dout)
+        ctx.save_for_backward(wf, cp, rt, hmat)
+        return _trim(out, dout)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        n_src, din, dout, num_rel = ctx.dims
+        need_x, need_wparam, need_comp, need_root, need_bias = ctx.needs_input_grad[:5]      # (False for an input that is None)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        if ctx.index.n_dst == 0:       # no destination row: every gradient is a zero
+            wf, cp, rt = ctx.saved_tensors
+            return (torch.zeros(n_src, din, **f32) if need_x else None, torch.zeros_like(wf) if need_wparam else None,
+                    torch.zeros_like(cp) if need_comp else None, torch.zeros(din, dout, **f32) if need_root else None,
+                    torch.zeros(dout, **f32) if need_bias else None, None, None, None)
+        wf, cp, rt, hmat = ctx.saved_tensors
+        ix = ctx.index._ix
+        gp = _rows16(g, dout)
+        dx = dw = droot = dbias = None
+        if need_x:
+            packed_t = _lib.pack_weights_decomposed(wf, cp, rt, num_rel, din, dout, transpose=True)
+            dx = _trim(_lib.mb_bwd_dx(ix, gp, dout, packed_t, din), din)
+        need_w = need_wparam or need_comp
+        if need_w or need_root:
+            dw = torch.empty(num_rel, din, dout, **f32) if need_w else None
+            droot = torch.empty(din, dout, **f32) if need_root else None
+            _lib.mb_bwd_dw(ix, hmat, din, gp, dout, dw, droot)
+        if need_bias:
+            dbias = g.sum(0)
+        dw, dcomp = _own_param_grads(dw, wf, cp, need_wparam, need_comp)
+        return dx, dw, dcomp, droot, dbias, None, None, None
+
+
 def target_block(edge_index: Tensor, edge_type: Tensor, rows: Tensor, num_nodes: int) -> Tuple[Tensor, Tensor]:
     """The edges of a graph of ``num_nodes`` nodes whose destination is one of ``rows`` (int64, unique, in [0, num_nodes)), with
     the destination relabelled to its position in ``rows``: ``conv((x, x[rows]), *target_block(edge_index, edge_type, rows, N))``
@@ -1178,6 +1226,51 @@ class RGCNConv(nn.Module):
             plans = self._bipartite_plans(edge_index, edge_type, n_src, n_dst, route)
             flags |= _lib.FLAG_SPLIT_PRODUCERS if route.split_producers else 0
         return _BipartiteFn.apply(x_src, x_dst, self.weight, self.comp, self.root, self.bias, plans, int(flags), r, self.out_channels)
+
+    def forward_block(self, x: Tensor, block, index=None) -> Tensor:
+        """``conv((x, x[:block.n_dst]), block.edge_index, block.edge_type)`` for a ``sampling.Block`` whose destinations are its
+        first ``n_dst`` source rows, on the kernels of ``csrc/rgcn_minibatch.hip``: ``x [n_src, in]`` float32 ->
+        ``[n_dst, out]``, mean or sum, full, basis or block weights, gradients to ``x`` (source side plus, in its first ``n_dst``
+        rows, the root term) and every parameter.  No graph plan is built and nothing is cached: ``index`` is the block's
+        ``sampling.block_index(block, num_relations, aggr)``, built here when not given; no order is required of the edges.
+        One GPU, 1..128 features per side, no fused activation.  Every refusal comes before anything is launched."""
+        if self.featureless:
+            raise NotImplementedError("featureless RGCNConv takes x = None or node indices: forward_block is not built for it")
+        if self.aggr == "max":
+            raise NotImplementedError("RGCNConv.forward_block aggregates by mean / sum only: aggr='max' is not built")
+        if self.xwide:
+            raise NotImplementedError(f"RGCNConv.forward_block takes 1..{NARROW_MAX_WIDTH} features per side: wide layers are not built")
+        if self.dist is not None:
+            raise NotImplementedError("RGCNConv.forward_block runs on one GPU: a dist context is not supported")
+        if self.in_channels_r != self.in_channels:
+            raise NotImplementedError(f"RGCNConv.forward_block reads the destinations' rows from x itself: a layer built with "
+                                      f"in_channels=({self.in_channels}, {self.in_channels_r}) is not supported")
+        if not isinstance(x, Tensor) or not torch.is_floating_point(x):
+            raise NotImplementedError("RGCNConv.forward_block takes float features x (no None / integer / pair input)")
+        if x.dtype != torch.float32:
+            raise ValueError(f"x must be float32, got {x.dtype}")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError(f"x must be [n_src, {self.in_channels}], got {tuple(x.shape)}")
+        n_src, n_dst = int(block.n_src), int(block.n_dst)
+        if n_dst > n_src:
+            raise ValueError(f"a block's destinations are its first source rows: n_dst ({n_dst}) exceeds n_src ({n_src})")
+        if x.shape[0] != n_src:
+            raise ValueError(f"x must hold the block's {n_src} source rows, got {x.shape[0]}")
+        ei, et = block.edge_index, block.edge_type
+        if ei.dim() != 2 or ei.shape[0] != 2 or et.dim() != 1 or ei.shape[1] != et.shape[0]:
+            raise ValueError(f"edge_index must be [2, E] and edge_type [E], got {tuple(ei.shape)} and {tuple(et.shape)}")
+        _require_gpu(x)
+        if ei.device != x.device or et.device != x.device:
+            raise RuntimeError(f"RGCNConv.forward_block: edge_index ({ei.device}) and edge_type ({et.device}) must be on the device "
+                               f"of x ({x.device})")
+        if index is None:
+            from .sampling import block_index
+            index = block_index(block, self.num_relations, self.aggr)
+        elif (index.n_src, index.n_dst, index.num_edges, index.num_relations, index.aggr) != \
+                (n_src, n_dst, int(et.shape[0]), self.num_relations, self.aggr) or index.device != x.device:
+            raise ValueError("index does not belong to this block and layer (sizes, relations, aggregation or device differ)")
+        _lib.load()
+        return _BlockFn.apply(x, self.weight, self.comp, self.root, self.bias, index, self.num_relations, self.out_channels)
 
     def _bipartite_plans(self, edge_index: Tensor, edge_type: Tensor, n_src: int, n_dst: int,
                          route: Optional["_Route"] = None) -> GraphPlans:

@@ -47,24 +47,31 @@ class _RGCNStack(nn.Module):
             return self.rgcn2(h, ei, et, _activation="sigmoid", _input_relu=True)
         return activation(self.rgcn2(h, ei, et, _input_relu=True))
 
-    def _tail_blocks(self, x: Tensor, blocks, activation: Callable) -> Tensor:
+    def _tail_blocks(self, x: Tensor, blocks, activation: Callable, block_kernels: bool = False) -> Tensor:
         """The same two layers over sampled blocks (sampling.NeighborSampler.sample): ``x`` holds the rows ``blocks[0].src_nodes``
         of the layer input, a block's destinations are its first ``n_dst`` source rows.  The bipartite layer fuses no
-        activation: both run as torch ops.  Returns the rows of ``blocks[1]``'s destinations, the seeds."""
+        activation: both run as torch ops.  ``block_kernels``: both layers through ``RGCNConv.forward_block`` (no graph plans).
+        Returns the rows of ``blocks[1]``'s destinations, the seeds."""
         b0, b1 = blocks
         if x.shape[0] != b0.n_src or b0.n_dst != b1.n_src:
             raise ValueError(f"blocks do not chain: x has {x.shape[0]} rows, blocks[0] is {b0.n_src} -> {b0.n_dst}, "
                              f"blocks[1] is {b1.n_src} -> {b1.n_dst}")
+        if block_kernels:
+            return activation(self.rgcn2.forward_block(F.relu(self.rgcn1.forward_block(x, b0)), b1))
         h = F.relu(self.rgcn1((x, x[:b0.n_dst]), b0.edge_index, b0.edge_type))
         return activation(self.rgcn2((h, h[:b1.n_dst]), b1.edge_index, b1.edge_type))
 
-    def forward_blocks(self, blocks, activation: Callable) -> Tensor:
+    def forward_blocks(self, blocks, activation: Callable, block_kernels: bool = False) -> Tensor:
         """``forward`` on the two sampled blocks of a mini-batch: every model gathers the rows ``blocks[0].src_nodes`` of its
         embedding BEFORE its own pre-transform (``_block_input``), so that nothing runs over the whole graph.  Returns the seeds'
-        rows ``[blocks[1].n_dst, num_labels]``.  Eager torch activations; ``forward`` is untouched."""
+        rows ``[blocks[1].n_dst, num_labels]``.  Eager torch activations; ``forward`` is untouched.  ``block_kernels=True`` (off by
+        default): both layers run straight from their blocks on the kernels of csrc/rgcn_minibatch.hip (``RGCNConv.forward_block``,
+        DESIGN.md 15) instead of the bipartite layer on freshly built graph plans."""
+        if not isinstance(block_kernels, bool):
+            raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
         if len(blocks) != 2:
             raise ValueError(f"the models have two RGCN layers: forward_blocks takes 2 blocks, got {len(blocks)}")
-        return self._tail_blocks(self._block_input(blocks[0].src_nodes), blocks, activation)
+        return self._tail_blocks(self._block_input(blocks[0].src_nodes), blocks, activation, block_kernels)
 
     def _block_input(self, nodes: Tensor) -> Tensor:
         raise NotImplementedError

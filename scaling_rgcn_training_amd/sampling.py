@@ -30,6 +30,63 @@ class Block(NamedTuple):
     src_nodes: Tensor       # int64 [n_src] global node ids; src_nodes[:n_dst] are the destinations
 
 
+class BlockIndex:
+    """The index one mini-batch layer walks straight from a ``Block`` (csrc/rgcn_minibatch.hip): the block's edges
+    plus one root pseudo edge per destination, sorted by (relation, destination), cut into rows of at most 256 edges that lie
+    relation-major in tiles of 16, with the destination-major list of rows and the source-major list of (row, scale).  One index
+    serves ``RGCNConv.forward_block``'s forward, dX and d_weight; it is built once per (block, aggregation) by ``block_index``
+    and owns its arrays."""
+
+    def __init__(self, lib_index, aggr: str):
+        self._ix = lib_index
+        self.aggr = aggr
+        self.n_src, self.n_dst, self.num_edges = lib_index.n_src, lib_index.n_dst, lib_index.num_edges
+        self.num_relations, self.n_rows, self.n_tiles = lib_index.num_relations, lib_index.n_rows, lib_index.n_tiles
+        self.device = lib_index.arena.device
+
+    def __getattr__(self, name):      # tile_ptr, row_beg, row_cnt, row_dst, row_scale, edge_src, dst_ptr, dst_rows, src_ptr, ...
+        if name.startswith("_"):
+            raise AttributeError(name)
+        return getattr(self._ix, name)
+
+
+def check_block(block, num_relations: int, aggr: str = "mean") -> None:
+    """what ``block_index`` refuses on the host, before the library is loaded"""
+    if aggr not in ("mean", "sum", "add"):
+        raise ValueError(f"block_index aggregates by mean / sum (got {aggr!r})")
+    if isinstance(num_relations, bool) or not isinstance(num_relations, int) or num_relations < 1:
+        raise ValueError(f"num_relations must be an int >= 1 (got {num_relations!r})")
+    ei, et = block.edge_index, block.edge_type
+    if not torch.is_tensor(ei) or not torch.is_tensor(et) or ei.dim() != 2 or ei.shape[0] != 2 or et.dim() != 1 \
+            or ei.shape[1] != et.shape[0]:
+        raise ValueError("a block holds edge_index [2, E_b] and edge_type [E_b]")
+    if ei.dtype != torch.int64 or et.dtype != torch.int64:
+        raise ValueError(f"edge_index and edge_type must be int64 (got {ei.dtype}, {et.dtype})")
+    if block.n_src < 0 or block.n_dst < 0 or block.n_dst > block.n_src:
+        raise ValueError(f"a block's destinations are its first source rows: n_dst ({block.n_dst}) must lie in [0, n_src = {block.n_src}]")
+    if et.shape[0] and block.n_dst == 0:
+        raise ValueError(f"edge_index out of range: {int(et.shape[0])} edges into 0 destinations")
+    _need_gpu(ei, "block_index")
+    if et.device != ei.device:
+        raise RuntimeError(f"block_index: edge_type ({et.device}) must be on the device of edge_index ({ei.device})")
+
+
+def block_index(block: Block, num_relations: int, aggr: str = "mean") -> BlockIndex:
+    """Build the ``BlockIndex`` of ``block`` on its device: three radix sorts and one host synchronisation.  No order is required
+    of the block's edges; an id out of range raises (found on the device)."""
+    check_block(block, num_relations, aggr)
+    from . import _lib
+    aggr = "sum" if aggr == "add" else aggr
+    try:
+        ix = _lib.mb_index_build(block.edge_index, block.edge_type, block.n_src, block.n_dst, num_relations, mean=aggr == "mean")
+    except _lib.RgcnLibraryError as err:
+        if getattr(err, "status", 0) == _lib.ERR_GRAPH:
+            raise ValueError(f"edge_index / edge_type out of range: sources must lie in [0, {block.n_src}), destinations in "
+                             f"[0, {block.n_dst}), relations in [0, {num_relations})") from err
+        raise
+    return BlockIndex(ix, aggr)
+
+
 def check_fanouts(fanouts) -> List[int]:
     """a non-empty sequence of ints in {-1} u [1, 256]"""
     if isinstance(fanouts, (str, bytes)) or not isinstance(fanouts, Sequence) or len(fanouts) == 0:

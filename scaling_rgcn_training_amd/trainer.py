@@ -222,15 +222,19 @@ class Trainer:
         return cached[1]
 
     def train_minibatch(self, model: nn.Module, graph, loss_f: Callable, activation: Callable, batch_size: int,
-                        fanouts, sum_graph: bool = True, seed: int = 0) -> Tuple[List[float], List[float], List[float], List[float]]:
+                        fanouts, sum_graph: bool = True, seed: int = 0,
+                        block_kernels: bool = False) -> Tuple[List[float], List[float], List[float], List[float]]:
         """``train`` with neighbour sampling: per epoch the full-batch validation forward exactly as ``train`` does it (when
         ``not sum_graph``), then a seeded permutation of ``x_train`` cut into batches of ``batch_size`` (the last may be short)
         and ONE optimizer step per batch on the blocks ``NeighborSampler.sample(batch, fanouts, step seed)`` returns, through
         ``model.forward_blocks``.  The step seed is a fixed odd-multiplier combination of ``seed``, the epoch and the batch index
         (mod 2^63; the sampler mixes it): runs repeat, steps differ.  The epoch's
         loss is the mean over its batches.  Eager only -- block shapes change every step, nothing is captured.  Returns the four
-        lists of ``train``; ``self.last_batches`` holds the last epoch's batches (tensors of node ids)."""
+        lists of ``train``; ``self.last_batches`` holds the last epoch's batches (tensors of node ids).  ``block_kernels`` goes to
+        ``model.forward_blocks``: True runs both layers straight from their blocks (no graph plans)."""
         from .sampling import check_fanouts, check_sample_seed
+        if not isinstance(block_kernels, bool):
+            raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
             raise ValueError(f"batch_size must be an int >= 1 (got {batch_size!r})")
         fanouts = check_fanouts(fanouts)
@@ -267,7 +271,7 @@ class Trainer:
                 step_seed = (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
                 blocks = sampler.sample(batch, fanouts, step_seed)
                 optimizer.zero_grad()
-                out = model.forward_blocks(blocks, activation)
+                out = model.forward_blocks(blocks, activation, block_kernels) if block_kernels else model.forward_blocks(blocks, activation)
                 output = loss_f(out, targets[rows])
                 output.backward()
                 optimizer.step()
