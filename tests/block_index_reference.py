@@ -1,7 +1,7 @@
 """The index of one sampled block (csrc/rgcn_minibatch.hip) stated in CPU torch and Python integers, for
 tests/test_block_index_reference.py (checks it against a brute-force layer) and tests/test_gpu_block_index.py (checks the device
 arrays against it); ``walk``: the layer and its gradients computed by walking an index exactly as the kernels do, in the dtype of
-its inputs; ``cases``: the small blocks both tests share.  No tests here.
+its inputs; ``cases``: the small blocks both tests share; ``edge_cases``: the larger ones on the build's boundaries.  No tests here.
 
 The root is relation R with one pseudo edge i -> i per destination, appended behind the block's edges.  All M = E_b + n_dst edges
 are sorted stably by (relation, destination); a run of equal (relation, destination) is cut into rows of at most 256 consecutive
@@ -130,7 +130,11 @@ def walk(ix: RefIndex, x, weight, root, bias, g):
     dh = torch.bmm(gd[:, None, :], w[slot_rel].transpose(1, 2))[:, 0]
     src_of = torch.repeat_interleave(torch.arange(ix.n_src), (ix.src_ptr[1:] - ix.src_ptr[:-1]).long())
     dx = torch.zeros(ix.n_src, din, dtype=dt).index_add_(0, src_of, scale[ix.src_row.long()][:, None] * dh[ix.src_row.long()])
-    dw = torch.zeros(r + 1, din, dout, dtype=dt).index_add_(0, slot_rel, h[:, :, None] * gd[:, None, :])
+    # one product per relation over its slots (an index_add_ of 66,000 outer products, one after the other, is 3e-12 off at |d_root|
+    # of 600 in float64: the blocked product is not)
+    dw, tp = torch.zeros(r + 1, din, dout, dtype=dt), ix.tile_ptr.tolist()
+    for rel in torch.nonzero(tiles)[:, 0].tolist():
+        dw[rel] = h[16 * tp[rel]:16 * tp[rel + 1]].t() @ gd[16 * tp[rel]:16 * tp[rel + 1]]
     return out, {"x": dx, "weight": dw[:r], "root": dw[r], "bias": g.to(dt).sum(0)}
 
 
@@ -161,4 +165,65 @@ def cases():
     out["one_row"] = (*_shuffled([0] * 5, [0] * 5, [0, 1, 1, 0, 0], 4), 1, 1, 2)
     # 300 relations, three of them in use
     out["many_rel"] = (*_shuffled(rnd(50, 90), rnd(20, 90), [0] * 30 + [7] * 30 + [299] * 30, 5), 50, 20, 300)
+    return out
+
+
+def _random_block(n_src, n_dst, r, e, seed, hub=600, dup=20, rels=None, every_relation=False):
+    """``e`` edges in all: ``hub`` into destination 0 (relation ``rels[0]``), ``dup`` repeats of the first triples, the rest random
+    over ``rels`` (default: all ``r``; ``every_relation``: the first ``r`` random edges take relations 0 .. r - 1).  The last
+    source and the last destination are in use: their ids carry the top bit of the sort keys."""
+    g = torch.Generator().manual_seed(seed)
+    n = e - hub - dup
+    assert n >= max(2, dup) and (not every_relation or n >= r)
+    rels = torch.arange(r) if rels is None else torch.tensor(rels, dtype=torch.int64)
+    rnd = lambda hi, k: torch.randint(0, hi, (k,), generator=g)
+    src, dst, typ = rnd(n_src, n), rnd(n_dst, n), rels[rnd(len(rels), n)]
+    if every_relation:
+        typ[:r] = torch.arange(r)
+    src[0], dst[1] = n_src - 1, n_dst - 1
+    src = torch.cat([src, rnd(n_src, hub), src[:dup]])
+    dst = torch.cat([dst, torch.zeros(hub, dtype=torch.int64), dst[:dup]])
+    typ = torch.cat([typ, torch.full((hub,), int(rels[0])), typ[:dup]])
+    perm = torch.randperm(e, generator=g)
+    return torch.stack([src[perm], dst[perm]]), typ[perm], n_src, n_dst, r
+
+
+def edge_cases():
+    """name -> (edge_index, edge_type, n_src, n_dst, num_relations): the blocks that sit on the size, bit-width and pass-count
+    boundaries of the device build (csrc/rgcn_minibatch.hip on csrc/rgcn_sort_scan.h).  Kept apart from ``cases``: up to 86,000
+    edges.  A sort of b key bits takes ceil(b / 8) passes; bits_for(v) = bits that hold 0 .. v, at least 1."""
+    out = {}
+    # M = E_b + n_dst on both sides of one sort segment / one scan block (2,048) and of a four-segment sort workgroup (8,192):
+    # n_dst = 300, so E_b = M - 300
+    for m in (2047, 2048, 2049, 8191, 8192, 8193):
+        out[f"m{m}"] = _random_block(400, 300, 3, m - 300, seed=m)
+    # n_dst at and around a power of two: the keys' destination field is bits_for(n_dst - 1) = 1, 1, 8, 8, 9 bits wide, the dead
+    # key n_dst of the destination sort needs bits_for(n_dst) = 1, 2, 8, 9, 9 (a second pass from n_dst = 256 on)
+    for nd in (1, 2, 255, 256, 257):
+        out[f"ndst{nd}"] = _random_block(nd + 40, nd, 3, 1500, seed=100 + nd)
+    # R at and around a power of two, every relation in use: the root is relation R, bits_for(R) = 1, 2, 3, 8, 9, 9, 9, 10 bits
+    # on top of bits_for(299) = 9: 10 .. 12 bits, two passes, up to R = 4; 17 .. 19 bits, three passes, from R = 255 on.  R + 1 =
+    # 256, 257, 258, 512, 513 relations also put mb_rel_scan_kernel on both sides of one and of two trips of 256
+    for r in (1, 2, 4, 255, 256, 257, 511, 512):
+        out[f"rel{r}"] = _random_block(340, 300, r, 2500, seed=200 + r, every_relation=True)
+    # the first sort in THREE passes with both fields on a power of two: bits_for(256) + bits_for(257 - 1) = 9 + 9 = 18 bits
+    out["rel256_ndst257"] = _random_block(297, 257, 256, 2500, seed=300, every_relation=True)
+    # the first sort in FOUR passes: bits_for(65,536) + bits_for(299) = 17 + 9 = 26 bits; 65,537 relations are 257 trips of
+    # mb_rel_scan_kernel, rows in the first and in the last two
+    out["rel65536"] = _random_block(340, 300, 65536, 2500, seed=301, rels=[0, 1, 65534, 65535])
+    # the source sort: bits_for(n_src - 1) = 16 bits at 65,536 (two passes), 17 at 65,537 and 70,000 (three: the result lands in
+    # the other buffer pair); n_src + 1 entries of src_ptr are scanned in 33 / 35 blocks where M = 5,300 takes three
+    for ns in (65536, 65537, 70000):
+        out[f"nsrc{ns}"] = _random_block(ns, 300, 3, 5000, seed=400 + ns % 1000)
+    # the destination sort in three passes: bits_for(66,000) = 17 bits (and 2 + 17 = 19 bits, three passes, for the first sort)
+    out["ndst66000"] = _random_block(66000, 66000, 3, 20000, seed=500)
+    # runs of exactly 1, 512, 513 and 4,097 edges of relation 1 into destinations 0 .. 3: rows of (1), (256, 256), (256, 256, 1)
+    # and 16 x 256 + 1 -- 23 rows, two tiles; relation 0 random into destinations 4 .. 9, relation 2 empty
+    g = torch.Generator().manual_seed(600)
+    rnd = lambda hi, n: torch.randint(0, hi, (n,), generator=g).tolist()
+    lens = (1, 512, 513, 4097)
+    src = rnd(60, sum(lens)) + rnd(60, 50)
+    dst = [d for d, n in enumerate(lens) for _ in range(n)] + [4 + d for d in rnd(6, 50)]
+    typ = [1] * sum(lens) + [0] * 50
+    out["runs_1_512_513_4097"] = (*_shuffled(src, dst, typ, 6), 60, 10, 3)
     return out

@@ -1,7 +1,9 @@
 """C ABI of the mini-batch block kernels (rgcn_mb_*): the size queries, every refusal code of the header's table answered before
 anything is launched (workspace, arena, H, Z and every output keep their sentinel), served calls that write nothing outside their
-buffers (guard words around the workspace and the arena, sentinel tails behind H, Z, dH and every output), and ids out of range
-found on the device."""
+buffers (guard words around the workspace and the arena, sentinel tails behind H, Z, dH and every output), ids out of range
+found on the device, a served pass in which every leading dimension has a value of its own and the columns past ``round4(width)``
+are NaN on the way in and keep their sentinel on the way out, ``d_root == NULL``, and the table of d_weight slab counts behind
+``rgcn_mb_bwd_dw_workspace_bytes`` on either side of each of its clamps."""
 import ctypes as C
 
 import pytest
@@ -214,3 +216,106 @@ def test_bad_ids_are_found_on_the_device():
         assert c.out_ix.tile_ptr is None
     assert c.build(nd=0, ns=NS) == GRAPH          # edges into no destination
     assert c.build() == OK
+
+
+def _layer_reference(c):
+    x64, g64 = c.x[:, :DIN].double(), c.g[:, :DOUT].double()
+    ref, cond, _ = B.reference(x64, x64[:ND], c.ei, c.et, c.w.double(), c.root.double(), c.bias.double(), g64)
+    ref["x"], cond["x"] = ref["x_src"].copy(), cond["x_src"].copy()
+    ref["x"][:ND] += ref["x_dst"]
+    cond["x"][:ND] += cond["x_dst"]
+    return ref, cond
+
+
+def test_every_leading_dimension_its_own():
+    """ldx, ldh, lddh, lddx (in = 33, round4 = 36) and ldz, ldo, ldg (out = 100) all differ: a kernel that steps through one buffer
+    with another's stride reads NaN or leaves sentinels inside a result"""
+    from oracle.tolerance import assert_close
+    c = Call()
+    ldx, ldh, lddh, lddx = c.ldi + 8, c.ldi + 4, c.ldi + 12, c.ldi + 16
+    ldz, ldo, ldg = c.ldo + 12, c.ldo + 4, c.ldo + 8
+    assert (c.ldi, c.ldo) == (36, 100) and len({ldx, ldh, lddh, lddx}) == 4 and len({ldz, ldo, ldg}) == 3
+    f32 = dict(dtype=torch.float32, device=DEV)
+    x = torch.full((NS, ldx), float("nan"))
+    x[:, :c.ldi] = c.x                                  # (columns 33 .. 35 are zeros, as the ABI requires)
+    g = torch.full((ND, ldg), float("nan"))
+    g[:, :c.ldo] = c.g
+    x, g = x.to(DEV), g.to(DEV)
+    full = lambda rows, ld: torch.full((rows + TAIL, ld), SENTF, **f32)
+    h, z, out, dh, dx = full(c.slots, ldh), full(c.slots, ldz), full(ND, ldo), full(c.slots, lddh), full(NS, lddx)
+    assert c.fwd(x=x.data_ptr(), ldx=ldx, h=h.data_ptr(), ldh=ldh, z=z.data_ptr(), ldz=ldz, out=out.data_ptr(), ldo=ldo) == OK
+    assert c.bwd_dx(g=g.data_ptr(), ldg=ldg, dh=dh.data_ptr(), lddh=lddh, dx=dx.data_ptr(), lddx=lddx) == OK
+    assert c.bwd_dw(h=h.data_ptr(), ldh=ldh, g=g.data_ptr(), ldg=ldg) == OK
+    torch.cuda.synchronize()
+    for name, t, rows, r4 in (("h", h, c.slots, c.ldi), ("z", z, c.slots, c.ldo), ("out", out, ND, c.ldo), ("dh", dh, c.slots, c.ldi),
+                              ("dx", dx, NS, c.ldi)):
+        assert bool((t[rows:] == SENTF).all()) and bool((t[:, r4:] == SENTF).all()), f"{name}: written outside its rows or columns"
+        assert bool(torch.isfinite(t[:rows, :r4]).all()) and not bool((t[:rows, :r4] == SENTF).any()), f"{name}: NaN read or a gap left"
+    assert bool((c.dw[NREL * DIN * DOUT:] == SENTF).all()) and bool((c.droot[DIN * DOUT:] == SENTF).all())
+    assert bool((c.ws_dw[:GUARD] == SENT8).all()) and bool((c.ws_dw[GUARD + c.need_dw:] == SENT8).all())
+    assert bool((x[:, c.ldi:] != x[:, c.ldi:]).all()) and bool((g[:, c.ldo:] != g[:, c.ldo:]).all())      # (the inputs are as they were)
+    ref, cond = _layer_reference(c)
+    assert_close(out[:ND, :DOUT].cpu().numpy(), ref["out"], cond["out"], "rgcn_mb_fwd, own strides")
+    assert_close(dx[:NS, :DIN].cpu().numpy(), ref["x"], cond["x"], "rgcn_mb_bwd_dx, own strides")
+    assert_close(c.dw[:NREL * DIN * DOUT].view(NREL, DIN, DOUT).cpu().numpy(), ref["weight"], cond["weight"], "rgcn_mb_bwd_dw, own strides")
+    assert_close(c.droot[:DIN * DOUT].view(DIN, DOUT).cpu().numpy(), ref["root"], cond["root"], "rgcn_mb_bwd_dw root, own strides")
+
+
+def test_d_weight_without_d_root():
+    from oracle.tolerance import assert_close
+    c = Call()
+    assert c.fwd() == OK and c.bwd_dw(droot=None) == OK
+    torch.cuda.synchronize()
+    assert bool((c.droot == SENTF).all()), "d_root written though NULL was passed"
+    assert bool((c.dw[NREL * DIN * DOUT:] == SENTF).all())
+    assert bool((c.ws_dw[:GUARD] == SENT8).all()) and bool((c.ws_dw[GUARD + c.need_dw:] == SENT8).all())
+    ref, cond = _layer_reference(c)
+    assert_close(c.dw[:NREL * DIN * DOUT].view(NREL, DIN, DOUT).cpu().numpy(), ref["weight"], cond["weight"], "rgcn_mb_bwd_dw, d_root NULL")
+
+
+def _slabs(n_tiles, nrel, din, dout):
+    """slabs per relation of a d_weight launch: about eight tiles each, the partials at most 2^24 floats (64 MiB), at most 64, at least 1"""
+    return max(1, min(-(-n_tiles // (8 * nrel)), 2 ** 24 // (nrel * din * dout), 64))
+
+
+def test_the_slab_table():
+    """host only: the query launches nothing, and the refused rgcn_mb_bwd_dw neither"""
+    c = Call()
+    qd = c.lib.rgcn_mb_bwd_dw_workspace_bytes
+
+    def query(n_tiles, nrel, din, dout):          # (an index that states these counts: 16 n_tiles edges make room for its slots)
+        return qd(c.struct_with(num_edges=16 * n_tiles, n_rows=16 * n_tiles, n_tiles=n_tiles, num_relations=nrel - 1), din, dout)
+
+    def nbytes(slabs, nrel, din, dout):
+        return nrel * slabs * din * dout * 4 if slabs > 1 else 0
+
+    pins = (
+        # about eight tiles a slab: S = 1 up to 8 nrel tiles, 2 one tile past them
+        (1, 4, 16, 16, 1), (32, 4, 16, 16, 1), (33, 4, 16, 16, 2), (64, 4, 16, 16, 2), (65, 4, 16, 16, 3), (0, 4, 16, 16, 1),
+        (16, 2, 1, 1, 1), (17, 2, 1, 1, 2), (8 * 601, 601, 16, 13, 1), (8 * 601 + 1, 601, 16, 13, 2),
+        # the cap: 63 slabs at 8 nrel 63 tiles, 64 from one tile more, and no more than 64 ever
+        (2016, 4, 33, 100, 63), (2017, 4, 33, 100, 64), (2048, 4, 33, 100, 64), (2049, 4, 33, 100, 64), (10 ** 6, 4, 33, 100, 64),
+        (1026, 2, 16, 16, 64), (1008, 2, 16, 16, 63),
+        # 64 MiB of partials: 2^24 // (21 * 128 * 128) = 48 where the tiles ask for 50; 47 and 48 below the clamp
+        (8400, 21, 128, 128, 48), (8065, 21, 128, 128, 48), (8064, 21, 128, 128, 48), (7896, 21, 128, 128, 47),
+        (8400, 21, 128, 127, 49), (8400, 21, 64, 128, 50),
+        # the floor: 1,025 * 128 * 128 > 2^24 leaves room for no slab at all: one, and no workspace; 512 relations: room for 2
+        (10 ** 6, 1025, 128, 128, 1), (10 ** 6, 1024, 128, 128, 1), (10 ** 6, 512, 128, 128, 2), (10 ** 6, 513, 128, 128, 1),
+        (10 ** 6, 65537, 16, 16, 1), (10 ** 6, 65536, 16, 16, 1), (10 ** 6, 32768, 16, 16, 2),
+    )
+    for n_tiles, nrel, din, dout, slabs in pins:
+        assert _slabs(n_tiles, nrel, din, dout) == slabs, (n_tiles, nrel, din, dout)
+        assert query(n_tiles, nrel, din, dout) == nbytes(slabs, nrel, din, dout), (n_tiles, nrel, din, dout, slabs)
+    for nrel in (2, 5, 21, 300, 1025):
+        for din, dout in ((1, 1), (16, 16), (33, 100), (64, 64), (128, 128)):
+            for n_tiles in (0, 1, 8 * nrel - 1, 8 * nrel, 8 * nrel + 1, 500 * nrel, 504 * nrel + 1, 512 * nrel, 512 * nrel + 1, 10 ** 6):
+                assert query(n_tiles, nrel, din, dout) == nbytes(_slabs(n_tiles, nrel, din, dout), nrel, din, dout), (n_tiles, nrel, din, dout)
+    assert query(33, 4, 16, 16) == 4 * 2 * 16 * 16 * 4 and query(8400, 21, 128, 128) == 21 * 48 * 128 * 128 * 4
+    # a workspace one byte short at S = 64 is refused before anything is launched
+    ix = c.struct_with(num_edges=16 * 2017, n_rows=c.good.n_rows, n_tiles=2017)
+    need = qd(ix, DIN, DOUT)
+    assert need == (NREL + 1) * 64 * DIN * DOUT * 4
+    ws = torch.full((need,), SENT8, dtype=torch.uint8, device=DEV)
+    assert c.bwd_dw(ix=ix, ws=ws.data_ptr(), ws_bytes=need - 1) == WS
+    c.untouched()
+    assert bool((ws == SENT8).all())

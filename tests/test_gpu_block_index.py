@@ -1,6 +1,10 @@
 """The device-built index of a sampled block (rgcn_mb_index_build through sampling.block_index) against its CPU statement
 (tests/block_index_reference.py): every array ``torch.equal``, on the reference's own cases, a block made by ``NeighborSampler``,
-the same block with its edges permuted (the index sorts them itself), and 300 relations with most of them empty."""
+the same block with its edges permuted (the index sorts them itself), 300 relations with most of them empty, and the reference's
+``edge_cases``: M = E_b + n_dst on both sides of a 2,048-key sort segment / scan block and of a four-segment sort workgroup, n_dst
+and R at powers of two (one more key bit for the root relation and for the destination sort's dead key), three and four passes
+of the first sort, a third pass of the source and of the destination sort, up to 513 and 65,537 relations through the relation
+scan's trips of 256, and runs of exactly 1, 512, 513 and 4,097 edges."""
 import pytest
 import torch
 
@@ -11,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 CASES = X.cases()
+EDGE = X.edge_cases()
 
 
 def _same(block, r, aggr="mean"):
@@ -31,6 +36,18 @@ def _same(block, r, aggr="mean"):
 def test_index_equals_the_reference(name, aggr):
     ei, et, n_src, n_dst, r = CASES[name]
     _same((ei, et, n_src, n_dst), r, aggr)
+
+
+@pytest.mark.parametrize("aggr", ["mean", "sum"])
+@pytest.mark.parametrize("name", sorted(EDGE))
+def test_index_equals_the_reference_at_the_edges(name, aggr):
+    ei, et, n_src, n_dst, r = EDGE[name]      # (the arithmetic that puts each block on its boundary: X.edge_cases)
+    got = _same((ei, et, n_src, n_dst), r, aggr)
+    if name.startswith("m"):
+        assert got.num_edges + got.n_dst == int(name[1:])
+    if name == "runs_1_512_513_4097":         # relation 1: rows (1), (256, 256), (256, 256, 1), 16 x (256) + (1), in that order
+        t = got.tile_ptr.tolist()
+        assert got.row_cnt[16 * t[1]:16 * t[2]].tolist() == [1, 256, 256, 256, 256, 1] + [256] * 16 + [1] + [0] * 9
 
 
 def test_sampled_block_and_its_permutation():
