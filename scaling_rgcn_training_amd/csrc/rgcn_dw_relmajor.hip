@@ -5,6 +5,7 @@
 //   rgcn_dw_direct_kernel 64 x 64, large walks: no ring, every wave gathers its own rows into registers
 //   rgcn_dw_reduce_kernel fixed-order compensated sum of the slabs -> d_weight / d_root / d_bias
 #include "rgcn_kernels_shared.h"
+#include "rgcn_launch.h"
 
 namespace rgcn {
 
@@ -771,25 +772,10 @@ static int launch_dw(const DwArgs& a, int nblocks, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-template <int KP>
-static int dispatch_dw_np(int NP, const DwArgs& a, int nb, hipStream_t s) {
-    switch (NP) {
-        case 16: return launch_dw<KP, 16>(a, nb, s);
-        case 32: return launch_dw<KP, 32>(a, nb, s);
-        case 64: return launch_dw<KP, 64>(a, nb, s);
-        case 128: return launch_dw<KP, 128>(a, nb, s);
-    }
-    return RGCN_ERR_WIDTH;
-}
-
 static int dispatch_dw(int KP, int NP, const DwArgs& a, int nb, hipStream_t s) {
-    switch (KP) {
-        case 16: return dispatch_dw_np<16>(NP, a, nb, s);
-        case 32: return dispatch_dw_np<32>(NP, a, nb, s);
-        case 64: return dispatch_dw_np<64>(NP, a, nb, s);
-        case 128: return dispatch_dw_np<128>(NP, a, nb, s);
-    }
-    return RGCN_ERR_WIDTH;
+    return for_padded_width(KP, [&](auto kp) {
+        return for_padded_width(NP, [&](auto np) { return launch_dw<decltype(kp)::value, decltype(np)::value>(a, nb, s); });
+    });
 }
 
 static size_t dw_slab_floats(int num_rel, int KP, int NP) {

@@ -16,6 +16,7 @@
 // Bytes per row (in -> out): 8 + 4 in gathered, 4 out written, 4 + 4 out read again: HBM-bound when the graph is larger than
 // the caches, launch-bound on the reference's datasets.
 #include "rgcn_kernels_shared.h"
+#include "rgcn_launch.h"
 
 namespace rgcn {
 
@@ -271,18 +272,6 @@ __global__ void __launch_bounds__(256) rgcn_ep_segment_sum_kernel(const EpSumArg
     *(f32x4*)(a.out + (size_t)seg * a.ldo + 4 * piece) = v;
 }
 
-template <int KP>
-static int ep_dispatch_np(int NP, const EpArgs& a, int blocks, hipStream_t s) {
-    switch (NP) {
-        case 16: hipLaunchKernelGGL((rgcn_ep_transform_kernel<KP, 16>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 32: hipLaunchKernelGGL((rgcn_ep_transform_kernel<KP, 32>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 64: hipLaunchKernelGGL((rgcn_ep_transform_kernel<KP, 64>), dim3(blocks), dim3(256), 0, s, a); break;
-        case 128: hipLaunchKernelGGL((rgcn_ep_transform_kernel<KP, 128>), dim3(blocks), dim3(256), 0, s, a); break;
-        default: return RGCN_ERR_WIDTH;
-    }
-    return (int)hipGetLastError();
-}
-
 }  // namespace rgcn
 
 using namespace rgcn;
@@ -326,13 +315,12 @@ extern "C" int rgcn_ep_transform(const rgcn_edge_units_t* units, const float* x,
         hipLaunchKernelGGL(rgcn_ep_transform3_kernel, dim3(blocks), dim3(256), 0, s, a);
         return (int)hipGetLastError();
     }
-    switch (KP) {
-        case 16: return ep_dispatch_np<16>(NP, a, blocks, s);
-        case 32: return ep_dispatch_np<32>(NP, a, blocks, s);
-        case 64: return ep_dispatch_np<64>(NP, a, blocks, s);
-        case 128: return ep_dispatch_np<128>(NP, a, blocks, s);
-    }
-    return RGCN_ERR_WIDTH;
+    return for_padded_width(KP, [&](auto kp) {
+        return for_padded_width(NP, [&](auto np) {
+            hipLaunchKernelGGL((rgcn_ep_transform_kernel<decltype(kp)::value, decltype(np)::value>), dim3(blocks), dim3(256), 0, s, a);
+            return (int)hipGetLastError();
+        });
+    });
 }
 
 extern "C" int rgcn_ep_segment_sum(const float* in, int ldin, const int32_t* seg_ptr, const int32_t* seg_idx, const float* seg_w,
@@ -364,15 +352,9 @@ extern "C" int rgcn_ep_segment_sum(const float* in, int ldin, const int32_t* seg
     a.final_level = final_level;
     const int ld4 = (width + 3) / 4;
     a.width4 = ld4;
-    const int G = ld4 <= 4 ? 4 : (ld4 <= 8 ? 8 : (ld4 <= 16 ? 16 : 32));
-    const long waves = ((long)n_out + 64 / G - 1) / (64 / G);
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
     hipStream_t s = (hipStream_t)stream;
-    switch (G) {
-        case 4: hipLaunchKernelGGL(rgcn_ep_segment_sum_kernel<4>, dim3(blocks), dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL(rgcn_ep_segment_sum_kernel<8>, dim3(blocks), dim3(256), 0, s, a); break;
-        case 16: hipLaunchKernelGGL(rgcn_ep_segment_sum_kernel<16>, dim3(blocks), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(rgcn_ep_segment_sum_kernel<32>, dim3(blocks), dim3(256), 0, s, a); break;
-    }
-    return (int)hipGetLastError();
+    return launch_row_groups(ld4, n_out, [&](auto g, dim3 grid) {
+        hipLaunchKernelGGL(rgcn_ep_segment_sum_kernel<decltype(g)::value>, grid, dim3(256), 0, s, a);
+        return (int)hipGetLastError();
+    });
 }

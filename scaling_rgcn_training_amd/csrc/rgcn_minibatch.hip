@@ -27,7 +27,9 @@
 //   mb_dw_kernel          dW[rel] = H_rel^T g[destinations of rel's rows] on the same MFMA; a relation's tiles in S slabs (S fixed
 //                         per launch), slabs added in slab order by mb_dw_reduce_kernel
 // No float atomics anywhere: the same block and inputs give the same bits.
+#include <initializer_list>
 #include "rgcn_common.h"
+#include "rgcn_launch.h"
 #include "rgcn_sort_scan.h"
 
 namespace rgcn_mb {
@@ -241,24 +243,19 @@ struct IndexArrays {
 
 static IndexArrays carve_arrays(void* base, const Sizes& sz, u64 n_src, u64 n_dst, u64 num_rel) {
     IndexArrays w;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void* p = base ? (char*)base + off : nullptr;
-        off += align_up(nbytes);
-        return p;
-    };
-    w.tile_ptr = (u32*)take((num_rel + 2) * 4);
-    w.row_beg = (u32*)take(sz.rows_cap * 4);
-    w.row_cnt = (u32*)take(sz.rows_cap * 4);
-    w.row_dst = (u32*)take(sz.rows_cap * 4);
-    w.row_scale = (float*)take(sz.rows_cap * 4);
-    w.edge_src = (u32*)take(sz.total * 4);
-    w.dst_ptr = (u32*)take((n_dst + 1) * 4);
-    w.dst_rows = (u32*)take(sz.total * 4);
-    w.src_ptr = (u32*)take((n_src + 1) * 4);
-    w.src_row = (u32*)take(sz.total * 4);
-    w.src_scale = (float*)take(sz.total * 4);
-    w.bytes = off;
+    Arena ar(base);
+    w.tile_ptr = ar.take<u32>(num_rel + 2);
+    w.row_beg = ar.take<u32>(sz.rows_cap);
+    w.row_cnt = ar.take<u32>(sz.rows_cap);
+    w.row_dst = ar.take<u32>(sz.rows_cap);
+    w.row_scale = ar.take<float>(sz.rows_cap);
+    w.edge_src = ar.take<u32>(sz.total);
+    w.dst_ptr = ar.take<u32>(n_dst + 1);
+    w.dst_rows = ar.take<u32>(sz.total);
+    w.src_ptr = ar.take<u32>(n_src + 1);
+    w.src_row = ar.take<u32>(sz.total);
+    w.src_scale = ar.take<float>(sz.total);
+    w.bytes = ar.bytes();
     return w;
 }
 
@@ -272,42 +269,31 @@ struct BuildWorkspace {
 
 static BuildWorkspace carve_build(void* base, const Sizes& sz, u64 n_src, u64 n_dst, u64 num_rel) {
     BuildWorkspace w;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void* p = base ? (char*)base + off : nullptr;
-        off += align_up(nbytes);
-        return p;
-    };
+    Arena ar(base);
     const u64 m = sz.total;
     const u32 nseg = sort_segments((u32)m);
-    w.res = (Results*)take(sizeof(Results));
-    w.sb.k[0] = (u64*)take(m * 8);
-    w.sb.k[1] = (u64*)take(m * 8);
-    w.sb.v[0] = (u32*)take(m * 4);
-    w.sb.v[1] = (u32*)take(m * 4);
-    w.sb.hist = (u32*)take(((size_t)256 * nseg + 1) * 4);
+    w.res = ar.take<Results>(1);
+    w.sb.k[0] = ar.take<u64>(m);
+    w.sb.k[1] = ar.take<u64>(m);
+    w.sb.v[0] = ar.take<u32>(m);
+    w.sb.v[1] = ar.take<u32>(m);
+    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
     u64 scan_len = (u64)256 * nseg;
     if (m > scan_len) scan_len = m;
     if (n_src + 1 > scan_len) scan_len = n_src + 1;
     if (n_dst + 1 > scan_len) scan_len = n_dst + 1;
-    w.sb.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
-    w.flag = (u32*)take(m * 4);
-    w.run_id = (u32*)take(m * 4);
-    w.run_start = (u32*)take((m + 1) * 4);
-    w.row_id = (u32*)take(m * 4);
-    w.esrc = (u32*)take(m * 4);
-    w.pos_slot = (u32*)take(m * 4);
-    w.pos_scale = (float*)take(m * 4);
-    w.row_slot = (u32*)take(m * 4);
-    w.rel_start = (u32*)take((num_rel + 2) * 4);
-    w.bytes = off;
+    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.flag = ar.take<u32>(m);
+    w.run_id = ar.take<u32>(m);
+    w.run_start = ar.take<u32>(m + 1);
+    w.row_id = ar.take<u32>(m);
+    w.esrc = ar.take<u32>(m);
+    w.pos_slot = ar.take<u32>(m);
+    w.pos_scale = ar.take<float>(m);
+    w.row_slot = ar.take<u32>(m);
+    w.rel_start = ar.take<u32>(num_rel + 2);
+    w.bytes = ar.bytes();
     return w;
-}
-
-static int read_results(const Results* dev, Results* host, hipStream_t s) {
-    hipError_t e = hipMemcpyAsync(host, dev, sizeof(Results), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return (int)e;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -447,41 +433,21 @@ __global__ void __launch_bounds__(256) mb_sum_kernel(const SumArgs a) {
 }
 
 static int launch_sum(const SumArgs& a, hipStream_t s) {
-    const int ld4 = a.width4;
-    const int G = ld4 <= 4 ? 4 : (ld4 <= 8 ? 8 : (ld4 <= 16 ? 16 : 32));
-    const u64 waves = ((u64)a.n_out + 64 / G - 1) / (64 / G);
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
-    switch (G) {
-        case 4: hipLaunchKernelGGL(mb_sum_kernel<4>, dim3(blocks), dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL(mb_sum_kernel<8>, dim3(blocks), dim3(256), 0, s, a); break;
-        case 16: hipLaunchKernelGGL(mb_sum_kernel<16>, dim3(blocks), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(mb_sum_kernel<32>, dim3(blocks), dim3(256), 0, s, a); break;
-    }
-    return (int)hipGetLastError();
-}
-
-template <int KP, bool BWD>
-static int transform_np(int NP, const TransformArgs& a, hipStream_t s) {
-    const dim3 grid((a.n_tiles + 3u) / 4u), block(256);
-    switch (NP) {
-        case 16: hipLaunchKernelGGL((mb_transform_kernel<KP, 16, BWD>), grid, block, 0, s, a); break;
-        case 32: hipLaunchKernelGGL((mb_transform_kernel<KP, 32, BWD>), grid, block, 0, s, a); break;
-        case 64: hipLaunchKernelGGL((mb_transform_kernel<KP, 64, BWD>), grid, block, 0, s, a); break;
-        case 128: hipLaunchKernelGGL((mb_transform_kernel<KP, 128, BWD>), grid, block, 0, s, a); break;
-        default: return RGCN_ERR_WIDTH;
-    }
-    return (int)hipGetLastError();
+    return rgcn::launch_row_groups(a.width4, a.n_out, [&](auto g, dim3 grid) {
+        hipLaunchKernelGGL(mb_sum_kernel<decltype(g)::value>, grid, dim3(256), 0, s, a);
+        return (int)hipGetLastError();
+    });
 }
 
 template <bool BWD>
 static int launch_transform(int KP, int NP, const TransformArgs& a, hipStream_t s) {
-    switch (KP) {
-        case 16: return transform_np<16, BWD>(NP, a, s);
-        case 32: return transform_np<32, BWD>(NP, a, s);
-        case 64: return transform_np<64, BWD>(NP, a, s);
-        case 128: return transform_np<128, BWD>(NP, a, s);
-    }
-    return RGCN_ERR_WIDTH;
+    const dim3 grid((a.n_tiles + 3u) / 4u), block(256);
+    return rgcn::for_padded_width(KP, [&](auto kp) {
+        return rgcn::for_padded_width(NP, [&](auto np) {
+            hipLaunchKernelGGL((mb_transform_kernel<decltype(kp)::value, decltype(np)::value, BWD>), grid, block, 0, s, a);
+            return (int)hipGetLastError();
+        });
+    });
 }
 
 // d_weight.  Workgroup (relation, slab): its four waves share the row tiles of the slab and split the 16 x 16 tiles of the
@@ -563,19 +529,6 @@ __global__ void mb_dw_reduce_kernel(const DwArgs a) {
     }
 }
 
-template <int KP>
-static int dw_np(int NP, const DwArgs& a, hipStream_t s) {
-    const dim3 grid(a.nrel * (u32)a.slabs), block(256);
-    switch (NP) {
-        case 16: hipLaunchKernelGGL((mb_dw_kernel<KP, 16>), grid, block, 0, s, a); break;
-        case 32: hipLaunchKernelGGL((mb_dw_kernel<KP, 32>), grid, block, 0, s, a); break;
-        case 64: hipLaunchKernelGGL((mb_dw_kernel<KP, 64>), grid, block, 0, s, a); break;
-        case 128: hipLaunchKernelGGL((mb_dw_kernel<KP, 128>), grid, block, 0, s, a); break;
-        default: return RGCN_ERR_WIDTH;
-    }
-    return (int)hipGetLastError();
-}
-
 // slabs per relation of a d_weight launch: about eight tiles per workgroup, at most 64, the partials at most 64 MiB
 static int dw_slabs(int64_t n_tiles, int64_t nrel, int din, int dout) {
     int64_t s = (n_tiles + 8 * nrel - 1) / (8 * nrel);
@@ -596,6 +549,33 @@ static int check_index(const rgcn_mb_index_t* ix) {
                             !ix->src_row || !ix->src_scale))
         return RGCN_ERR_NULL;
     return RGCN_OK;
+}
+
+// what the three layer entries check first, in this order: the index, the widths, then every (leading dimension, width) pair
+struct Stride {
+    int ld, width;
+};
+static int check_layer(const rgcn_mb_index_t* ix, int din, int dout, std::initializer_list<Stride> strides) {
+    int st = check_index(ix);
+    if (st != RGCN_OK) return st;
+    if (din < 1 || din > RGCN_MAX_WIDTH || dout < 1 || dout > RGCN_MAX_WIDTH) return RGCN_ERR_PLAN;
+    for (const Stride& t : strides)
+        if ((st = rgcn::check_stride(t.ld, t.width)) != RGCN_OK) return st;
+    return RGCN_OK;
+}
+
+// the fields of TransformArgs that come from the index: the same for both directions
+static TransformArgs transform_args(const rgcn_mb_index_t* ix) {
+    TransformArgs a;
+    a.tile_ptr = (const u32*)ix->tile_ptr;
+    a.row_beg = ix->row_beg;
+    a.row_cnt = (const u32*)ix->row_cnt;
+    a.row_dst = (const u32*)ix->row_dst;
+    a.row_scale = ix->row_scale;
+    a.edge_src = (const u32*)ix->edge_src;
+    a.nrel = (u32)ix->num_relations + 1u;
+    a.n_tiles = (u32)ix->n_tiles;
+    return a;
 }
 
 }  // namespace rgcn_mb
@@ -669,9 +649,7 @@ extern "C" int rgcn_mb_index_build(const int64_t* src, int64_t src_stride, const
                        ws.sb.k[0], ws.sb.v[0], ws.esrc, ia.src_ptr, ws.res);
     const int c = radix_sort_pairs(ws.sb, M, bits_for((u64)R) + db, s);
     const u64* keys = ws.sb.k[c];
-    hipLaunchKernelGGL(head_flags_kernel, gm, blk, 0, s, keys, M, 0, ws.flag);
-    exclusive_scan(ws.flag, ws.run_id, M, ws.sb.sums, s);
-    hipLaunchKernelGGL(run_ids_kernel, gm, blk, 0, s, ws.run_id, ws.flag, M);
+    run_ids(keys, M, 0, ws.flag, ws.run_id, ws.sb.sums, s);
     hipLaunchKernelGGL(mb_run_start_kernel, gm, blk, 0, s, ws.flag, ws.run_id, M, ws.run_start);
     hipLaunchKernelGGL(mb_row_flags_kernel, gm, blk, 0, s, keys, ws.run_id, ws.run_start, M, db, ws.flag, ia.dst_ptr);
     exclusive_scan(ws.flag, ws.row_id, M, ws.sb.sums, s);
@@ -702,11 +680,7 @@ extern "C" int rgcn_mb_index_build(const int64_t* src, int64_t src_stride, const
     fa.mean = ix.mean;
     hipLaunchKernelGGL(mb_fill_kernel, gm, blk, 0, s, fa);
     // the later sorts start in the pair the first one did not end in (nothing reads the first sort's pairs after the fill)
-    SortBufs sb2 = ws.sb;
-    sb2.k[0] = ws.sb.k[c ^ 1];
-    sb2.k[1] = ws.sb.k[c];
-    sb2.v[0] = ws.sb.v[c ^ 1];
-    sb2.v[1] = ws.sb.v[c];
+    const SortBufs sb2 = from_pair(ws.sb, c ^ 1);
     hipLaunchKernelGGL(mb_dst_pairs_kernel, gm, blk, 0, s, ws.row_slot, ia.row_dst, ws.res, M, nd, sb2.k[0], sb2.v[0]);
     const int c2 = radix_sort_pairs(sb2, M, bits_for((u64)nd), s);
     hipLaunchKernelGGL(mb_copy_kernel, gm, blk, 0, s, sb2.v[c2], M, ia.dst_rows);
@@ -717,7 +691,7 @@ extern "C" int rgcn_mb_index_build(const int64_t* src, int64_t src_stride, const
     exclusive_scan(ia.src_ptr, ia.src_ptr, ns + 1u, ws.sb.sums, s);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     Results r;
-    if ((st = read_results(ws.res, &r, s)) != 0) return st;
+    if ((st = read_back(ws.res, &r, s)) != 0) return st;
     if (r.error & kErrRange) return RGCN_ERR_GRAPH;
     if (r.error & kErrInternal) return RGCN_ERR_PLAN;
     ix.n_rows = (int64_t)r.n_rows;
@@ -728,31 +702,18 @@ extern "C" int rgcn_mb_index_build(const int64_t* src, int64_t src_stride, const
 
 extern "C" int rgcn_mb_fwd(const rgcn_mb_index_t* index, const float* x, int ldx, int din, const float* packed_w, const float* bias,
                            float* h, int ldh, float* z, int ldz, float* out, int ldo, int dout, void* stream) {
-    int st = check_index(index);
+    int st = check_layer(index, din, dout, {{ldx, din}, {ldh, din}, {ldz, dout}, {ldo, dout}});
     if (st != RGCN_OK) return st;
-    if (din < 1 || din > RGCN_MAX_WIDTH || dout < 1 || dout > RGCN_MAX_WIDTH) return RGCN_ERR_PLAN;
-    if ((st = rgcn::check_stride(ldx, din)) != RGCN_OK) return st;
-    if ((st = rgcn::check_stride(ldh, din)) != RGCN_OK) return st;
-    if ((st = rgcn::check_stride(ldz, dout)) != RGCN_OK) return st;
-    if ((st = rgcn::check_stride(ldo, dout)) != RGCN_OK) return st;
     if (index->n_dst == 0) return RGCN_OK;
     if (!x || !packed_w || !h || !z || !out) return RGCN_ERR_NULL;
     if (index->n_tiles <= 0) return RGCN_ERR_PLAN;
     if ((st = rgcn::check_device()) != RGCN_OK) return st;
     hipStream_t s = (hipStream_t)stream;
-    TransformArgs a;
-    a.tile_ptr = (const u32*)index->tile_ptr;
-    a.row_beg = index->row_beg;
-    a.row_cnt = (const u32*)index->row_cnt;
-    a.row_dst = (const u32*)index->row_dst;
-    a.row_scale = index->row_scale;
-    a.edge_src = (const u32*)index->edge_src;
+    TransformArgs a = transform_args(index);
     a.x = x;
     a.wp = packed_w;
     a.h = h;
     a.z = z;
-    a.nrel = (u32)index->num_relations + 1u;
-    a.n_tiles = (u32)index->n_tiles;
     a.ldx = ldx;
     a.k4 = (din + 3) / 4;
     a.ldh = ldh;
@@ -776,31 +737,19 @@ extern "C" int rgcn_mb_fwd(const rgcn_mb_index_t* index, const float* x, int ldx
 
 extern "C" int rgcn_mb_bwd_dx(const rgcn_mb_index_t* index, const float* g, int ldg, int dout, const float* packed_wt, float* dh,
                               int lddh, float* dx, int lddx, int din, void* stream) {
-    int st = check_index(index);
+    int st = check_layer(index, din, dout, {{ldg, dout}, {lddh, din}, {lddx, din}});
     if (st != RGCN_OK) return st;
-    if (din < 1 || din > RGCN_MAX_WIDTH || dout < 1 || dout > RGCN_MAX_WIDTH) return RGCN_ERR_PLAN;
-    if ((st = rgcn::check_stride(ldg, dout)) != RGCN_OK) return st;
-    if ((st = rgcn::check_stride(lddh, din)) != RGCN_OK) return st;
-    if ((st = rgcn::check_stride(lddx, din)) != RGCN_OK) return st;
     if (index->n_src == 0) return RGCN_OK;
     if (!dx) return RGCN_ERR_NULL;
     if (index->n_tiles > 0 && (!g || !packed_wt || !dh)) return RGCN_ERR_NULL;
     if ((st = rgcn::check_device()) != RGCN_OK) return st;
     hipStream_t s = (hipStream_t)stream;
     if (index->n_tiles > 0) {
-        TransformArgs a;
-        a.tile_ptr = (const u32*)index->tile_ptr;
-        a.row_beg = index->row_beg;
-        a.row_cnt = (const u32*)index->row_cnt;
-        a.row_dst = (const u32*)index->row_dst;
-        a.row_scale = index->row_scale;
-        a.edge_src = (const u32*)index->edge_src;
+        TransformArgs a = transform_args(index);
         a.x = g;
         a.wp = packed_wt;
         a.h = nullptr;
         a.z = dh;
-        a.nrel = (u32)index->num_relations + 1u;
-        a.n_tiles = (u32)index->n_tiles;
         a.ldx = ldg;
         a.k4 = (dout + 3) / 4;
         a.ldh = 0;
@@ -833,11 +782,8 @@ extern "C" size_t rgcn_mb_bwd_dw_workspace_bytes(const rgcn_mb_index_t* index, i
 
 extern "C" int rgcn_mb_bwd_dw(const rgcn_mb_index_t* index, const float* h, int ldh, int din, const float* g, int ldg, int dout,
                               float* d_weight, float* d_root, void* workspace, size_t workspace_bytes, void* stream) {
-    int st = check_index(index);
+    int st = check_layer(index, din, dout, {{ldh, din}, {ldg, dout}});
     if (st != RGCN_OK) return st;
-    if (din < 1 || din > RGCN_MAX_WIDTH || dout < 1 || dout > RGCN_MAX_WIDTH) return RGCN_ERR_PLAN;
-    if ((st = rgcn::check_stride(ldh, din)) != RGCN_OK) return st;
-    if ((st = rgcn::check_stride(ldg, dout)) != RGCN_OK) return st;
     if (!d_weight && !d_root) return RGCN_OK;
     if (index->n_tiles > 0 && (!h || !g)) return RGCN_ERR_NULL;
     const int64_t nrel = (int64_t)index->num_relations + 1;
@@ -865,13 +811,13 @@ extern "C" int rgcn_mb_bwd_dw(const rgcn_mb_index_t* index, const float* h, int 
     a.din4 = (din + 3) / 4;
     a.dout4 = (dout + 3) / 4;
     // (an index without tiles has tile_ptr all zeros: every workgroup stores its zeros)
-    switch (rgcn::padded_width(din)) {
-        case 16: st = dw_np<16>(rgcn::padded_width(dout), a, s); break;
-        case 32: st = dw_np<32>(rgcn::padded_width(dout), a, s); break;
-        case 64: st = dw_np<64>(rgcn::padded_width(dout), a, s); break;
-        case 128: st = dw_np<128>(rgcn::padded_width(dout), a, s); break;
-        default: st = RGCN_ERR_WIDTH;
-    }
+    const dim3 grid(a.nrel * (u32)a.slabs), block(256);
+    st = rgcn::for_padded_width(rgcn::padded_width(din), [&](auto kp) {
+        return rgcn::for_padded_width(rgcn::padded_width(dout), [&](auto np) {
+            hipLaunchKernelGGL((mb_dw_kernel<decltype(kp)::value, decltype(np)::value>), grid, block, 0, s, a);
+            return (int)hipGetLastError();
+        });
+    });
     if (st != 0 || slabs == 1) return st;
     const size_t total = (size_t)nrel * din * dout;
     const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);

@@ -22,7 +22,7 @@
 
 namespace rgcn_planner {
 
-using namespace rgcn_sort_scan;      // u64 / u32, bits_for, radix_sort_pairs, exclusive_scan, head flags / run ids, read_u32
+using namespace rgcn_sort_scan;      // u64 / u32, bits_for, radix_sort_pairs, exclusive_scan, head flags / run ids, Arena, read_back
 
 // ------------------------------------------------------------------------------------------------
 // keys
@@ -786,28 +786,23 @@ struct Workspace {
 // nmax: most elements any step sorts (edges + owned nodes, or edges alone for the weights)
 static Workspace carve(void* base, u64 nmax, u64 gmax) {
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void* p = base ? (char*)base + off : nullptr;
-        off += align_up(nbytes);
-        return p;
-    };
+    Arena ar(base);
     const u32 nseg = sort_segments((u32)nmax);
-    w.ctr = (Counters*)take(sizeof(Counters));
-    w.sb.k[0] = (u64*)take(nmax * 8);
-    w.sb.k[1] = (u64*)take(nmax * 8);
-    w.sb.v[0] = (u32*)take(nmax * 4);
-    w.sb.v[1] = (u32*)take(nmax * 4);
-    w.sb.hist = (u32*)take(((size_t)256 * nseg + 1) * 4);
+    w.ctr = ar.take<Counters>(1);
+    w.sb.k[0] = ar.take<u64>(nmax);
+    w.sb.k[1] = ar.take<u64>(nmax);
+    w.sb.v[0] = ar.take<u32>(nmax);
+    w.sb.v[1] = ar.take<u32>(nmax);
+    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
     const u64 scan_len = nmax + 1 > (u64)256 * nseg ? nmax + 1 : (u64)256 * nseg;
-    w.sb.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
-    w.scan_a = (u32*)take((nmax + 1) * 4);
-    w.scan_b = (u32*)take((nmax + 1) * 4);
-    w.gstart = (u32*)take((gmax + 1) * 4);
-    w.gkey = (u32*)take((gmax + 1) * 4);
-    w.gch = (u32*)take((gmax + 1) * 4);
-    w.gun = (u32*)take((gmax + 1) * 4);
-    w.bytes = off;
+    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.scan_a = ar.take<u32>(nmax + 1);
+    w.scan_b = ar.take<u32>(nmax + 1);
+    w.gstart = ar.take<u32>(gmax + 1);
+    w.gkey = ar.take<u32>(gmax + 1);
+    w.gch = ar.take<u32>(gmax + 1);
+    w.gun = ar.take<u32>(gmax + 1);
+    w.bytes = ar.bytes();
     return w;
 }
 
@@ -869,13 +864,11 @@ extern "C" int rgcn_edge_weights(const rgcn_graph_t* g, int aggr_sum, float* w, 
                        (u32)g->num_nodes, (u32)g->num_relations, ws.sb.k[0], ws.sb.v[0], ws.ctr);
     const int bits = bits_for((u64)g->num_nodes * (u64)g->num_relations - 1);
     const int cur = radix_sort_pairs(ws.sb, (u32)E, bits, s);
-    hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.sb.k[cur], (u32)E, 0, ws.scan_a);
-    exclusive_scan(ws.scan_a, ws.scan_b, (u32)E, ws.sb.sums, s);
+    run_ids(ws.sb.k[cur], (u32)E, 0, ws.scan_a, ws.scan_b, ws.sb.sums, s);
     u32 n_runs = 0, err = 0;
-    if ((st = read_u32(ws.sb.sums + scan_blocks((u32)E), &n_runs, s)) != 0) return st;
-    if ((st = read_u32(&ws.ctr->error, &err, s)) != 0) return st;
+    if ((st = read_back(ws.sb.sums + scan_blocks((u32)E), &n_runs, s)) != 0) return st;
+    if ((st = read_back(&ws.ctr->error, &err, s)) != 0) return st;
     if (err) return RGCN_ERR_GRAPH;
-    hipLaunchKernelGGL(run_ids_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.scan_b, ws.scan_a, (u32)E);
     u32* rstart = (u32*)ws.sb.k[cur ^ 1];        // the sort's spare key buffer: E + 1 words fit into E 8-byte keys
     hipLaunchKernelGGL(run_start_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.sb.k[cur], (u32)E, ws.scan_b, rstart, n_runs);
     hipLaunchKernelGGL(weights_out_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.sb.v[cur], (u32)E, ws.scan_b, rstart, w);
@@ -933,8 +926,8 @@ extern "C" int rgcn_plan_build_begin(const rgcn_graph_t* g, const float* w, int 
                            n_own, ws.sb.k[0], ws.sb.v[0], ws.ctr);
     }
     u32 owned = 0, err = 0;
-    if ((st = read_u32(&ws.ctr->owned_edges, &owned, s)) != 0) return st;
-    if ((st = read_u32(&ws.ctr->error, &err, s)) != 0) return st;
+    if ((st = read_back(&ws.ctr->owned_edges, &owned, s)) != 0) return st;
+    if ((st = read_back(&ws.ctr->error, &err, s)) != 0) return st;
     if (err) return RGCN_ERR_GRAPH;
     const u32 n = n_own + owned;
     // ---- sort by (tile, relation, row in tile, gathered node), merge duplicate triples -------------------------
@@ -942,25 +935,23 @@ extern "C" int rgcn_plan_build_begin(const rgcn_graph_t* g, const float* w, int 
     hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(n)), dim3(256), 0, s, ws.sb.k[cur], n, 0, ws.scan_a);
     exclusive_scan(ws.scan_a, ws.scan_b, n, ws.sb.sums, s);
     u32 n_unique = 0;
-    if ((st = read_u32(ws.sb.sums + scan_blocks(n), &n_unique, s)) != 0) return st;
+    if ((st = read_back(ws.sb.sums + scan_blocks(n), &n_unique, s)) != 0) return st;
     const int ub = cur ^ 1;
     hipLaunchKernelGGL(merge_kernel, dim3(grid_for(n)), dim3(256), 0, s, ws.sb.k[cur], ws.sb.v[cur], n, ws.scan_b, ws.sb.k[ub],
                        ws.sb.v[ub]);
     // ---- groups = runs of equal (tile, relation) ------------------------------------------------------------------
-    hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(n_unique)), dim3(256), 0, s, ws.sb.k[ub], n_unique, kl.gshift(), ws.scan_a);
-    exclusive_scan(ws.scan_a, ws.scan_b, n_unique, ws.sb.sums, s);
-    hipLaunchKernelGGL(run_ids_kernel, dim3(grid_for(n_unique)), dim3(256), 0, s, ws.scan_b, ws.scan_a, n_unique);   // scan_b = group id
+    run_ids(ws.sb.k[ub], n_unique, kl.gshift(), ws.scan_a, ws.scan_b, ws.sb.sums, s);   // scan_b = group id
     u32 n_groups = 0;
-    if ((st = read_u32(ws.sb.sums + scan_blocks(n_unique), &n_groups, s)) != 0) return st;
+    if ((st = read_back(ws.sb.sums + scan_blocks(n_unique), &n_groups, s)) != 0) return st;
     if ((u64)n_groups + 1 > gmax) return RGCN_ERR_PLAN;
     hipLaunchKernelGGL(group_start_kernel, dim3(grid_for(n_unique)), dim3(256), 0, s, ws.sb.k[ub], n_unique, kl.gshift(), ws.scan_b,
                        ws.gstart, ws.gkey, n_groups);
     hipLaunchKernelGGL(group_sizes_kernel, dim3(grid_for(n_groups)), dim3(256), 0, s, ws.gstart, n_groups, (u32)chunk, cap, (u32)layout, ws.gch, ws.gun);
     u32 n_chunks = 0, n_units = 0;
     exclusive_scan(ws.gun, ws.gun, n_groups, ws.sb.sums, s);
-    if ((st = read_u32(ws.sb.sums + scan_blocks(n_groups), &n_units, s)) != 0) return st;
+    if ((st = read_back(ws.sb.sums + scan_blocks(n_groups), &n_units, s)) != 0) return st;
     exclusive_scan(ws.gch, ws.gch, n_groups, ws.sb.sums, s);                  // gch = chunk_base from here on
-    if ((st = read_u32(ws.sb.sums + scan_blocks(n_groups), &n_chunks, s)) != 0) return st;
+    if ((st = read_back(ws.sb.sums + scan_blocks(n_groups), &n_chunks, s)) != 0) return st;
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     memset(sizes, 0, sizeof(*sizes));
     // (layout 2: the plan struct reports tiles of at most 32,768 nodes -- nothing walks them, the kernels' argument checks do)
@@ -1056,7 +1047,7 @@ extern "C" int rgcn_plan_build_finish(const rgcn_plan_sizes_t* sizes, void* work
     plan->n_units = (int32_t)bs.n_units;
     if (bs.layout == 5) {      // units the pairs left over: data-dependent -- this layout's _finish SYNCHRONISES the stream
         u32 nu = 0;
-        const int st = read_u32(ws.sb.sums + scan_blocks(bs.n_chunks), &nu, s);
+        const int st = read_back(ws.sb.sums + scan_blocks(bs.n_chunks), &nu, s);
         if (st != 0) return st;
         plan->n_units = (int32_t)nu;
     }

@@ -5,6 +5,7 @@
 // (d_root = x_dst^T g is rgcn_rows_dw, on the streaming kernel of rgcn_dw_root.hip.)
 // Exact fp32 (v_mfma_f32_16x16x4_f32), no atomics, fixed summation orders: bit-reproducible.
 #include "rgcn_common.h"
+#include "rgcn_launch.h"
 
 namespace rgcn {
 
@@ -150,10 +151,5 @@ extern "C" int rgcn_rows_transform(const float* x, int ldx, int din, const float
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(kRowsTfThreads), lds, s, a);
         return (int)hipGetLastError();
     };
-    switch (padded_width(din)) {
-        case 16: return launch(rgcn_rows_transform_kernel<1>);
-        case 32: return launch(rgcn_rows_transform_kernel<2>);
-        case 64: return launch(rgcn_rows_transform_kernel<4>);
-        default: return launch(rgcn_rows_transform_kernel<8>);
-    }
+    return for_padded_width(padded_width(din), [&](auto kp) { return launch(rgcn_rows_transform_kernel<decltype(kp)::value / 16>); });
 }

@@ -95,22 +95,17 @@ struct IndexWorkspace {
 
 static IndexWorkspace carve_index(void* base, u64 num_edges, u64 n_nodes) {
     IndexWorkspace w;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void* p = base ? (char*)base + off : nullptr;
-        off += align_up(nbytes);
-        return p;
-    };
+    Arena ar(base);
     const u32 nseg = sort_segments((u32)num_edges);
-    w.res = (Results*)take(sizeof(Results));
-    w.sb.k[0] = (u64*)take(num_edges * 8);
-    w.sb.k[1] = (u64*)take(num_edges * 8);
-    w.sb.v[0] = (u32*)take(num_edges * 4);
-    w.sb.v[1] = (u32*)take(num_edges * 4);
-    w.sb.hist = (u32*)take(((size_t)256 * nseg + 1) * 4);
+    w.res = ar.take<Results>(1);
+    w.sb.k[0] = ar.take<u64>(num_edges);
+    w.sb.k[1] = ar.take<u64>(num_edges);
+    w.sb.v[0] = ar.take<u32>(num_edges);
+    w.sb.v[1] = ar.take<u32>(num_edges);
+    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
     const u64 scan_len = n_nodes + 1 > (u64)256 * nseg ? n_nodes + 1 : (u64)256 * nseg;
-    w.sb.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
-    w.bytes = off;
+    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.bytes = ar.bytes();
     return w;
 }
 
@@ -302,28 +297,17 @@ static u64 hop_cap(int64_t num_dst, int fanout, int64_t num_edges) {      // the
 
 static HopWorkspace carve_hop(void* base, u64 n_dst, u64 cap, u64 n_nodes) {
     HopWorkspace w;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void* p = base ? (char*)base + off : nullptr;
-        off += align_up(nbytes);
-        return p;
-    };
+    Arena ar(base);
     const u64 n_words = (n_nodes + 31) / 32;
-    w.res = (Results*)take(sizeof(Results));
-    w.cnt = (u32*)take((n_dst + 1) * 4);
-    w.sel = (u32*)take(cap * 4);
-    w.bits = (u32*)take(n_words * 4);
-    w.wcnt = (u32*)take((n_words + 1) * 4);
+    w.res = ar.take<Results>(1);
+    w.cnt = ar.take<u32>(n_dst + 1);
+    w.sel = ar.take<u32>(cap);
+    w.bits = ar.take<u32>(n_words);
+    w.wcnt = ar.take<u32>(n_words + 1);
     const u64 scan_len = n_dst + 1 > n_words + 1 ? n_dst + 1 : n_words + 1;
-    w.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
-    w.bytes = off;
+    w.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.bytes = ar.bytes();
     return w;
-}
-
-static int read_results(const Results* dev, Results* host, hipStream_t s) {
-    hipError_t e = hipMemcpyAsync(host, dev, sizeof(Results), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return (int)e;
 }
 
 static int check_hop_scalars(const rgcn_sample_index_t* ix, int64_t num_dst, int fanout, int64_t seed, int hop) {
@@ -366,7 +350,7 @@ extern "C" int rgcn_sample_index_build(const rgcn_graph_t* g, uint32_t* ptr_out,
     exclusive_scan(ptr_out, ptr_out, N + 1u, ws.sb.sums, s);      // in-degrees -> ptr, ptr[N] = E
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     Results r;
-    int st = read_results(ws.res, &r, s);
+    int st = read_back(ws.res, &r, s);
     if (st != 0) return st;
     return r.error ? RGCN_ERR_GRAPH : RGCN_OK;
 }
@@ -435,7 +419,7 @@ extern "C" int rgcn_sample_hop(const rgcn_sample_index_t* ix, const int64_t* dst
     hipLaunchKernelGGL(hop_reset_dst_kernel, dim3(grid_for(nd)), dim3(256), 0, s, dst_nodes, nd, N, node_map);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     Results r;
-    if ((st = read_results(ws.res, &r, s)) != 0) return st;
+    if ((st = read_back(ws.res, &r, s)) != 0) return st;
     if (r.error & kErrRange) return RGCN_ERR_GRAPH;
     if (r.error & kErrDuplicate) return RGCN_ERR_ARG;
     *num_edges_out = (int64_t)r.num_edges;

@@ -18,6 +18,7 @@
 // Bytes per segment row: 16 (indices, weight) + width * 4 gathered in the forward; + 3 width * 4 read and width * 4 written in
 // the backward.  No atomics, no LDS; rows are addressed with 64-bit offsets (any number of rows).
 #include "rgcn_kernels_shared.h"
+#include "rgcn_launch.h"
 
 namespace rgcn {
 
@@ -134,8 +135,6 @@ __global__ void __launch_bounds__(256) rgcn_segment_max_bwd_kernel(const SegMaxB
     *(f32x4*)(a.c + (size_t)q * a.ldc + 4 * piece) = r;
 }
 
-static int lanes_per_row(int width4) { return width4 <= 4 ? 4 : (width4 <= 8 ? 8 : (width4 <= 16 ? 16 : 32)); }
-
 }  // namespace rgcn
 
 using namespace rgcn;
@@ -162,17 +161,11 @@ extern "C" int rgcn_segment_max(const float* in, const float* in_t, int ldin, co
     a.width = width;
     a.width4 = (width + 3) / 4;
     a.n_out = n_out;
-    const int G = lanes_per_row(a.width4);
-    const long waves = ((long)n_out + 64 / G - 1) / (64 / G);
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
     hipStream_t s = (hipStream_t)stream;
-    switch (G) {
-        case 4: hipLaunchKernelGGL(rgcn_segment_max_kernel<4>, dim3(blocks), dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL(rgcn_segment_max_kernel<8>, dim3(blocks), dim3(256), 0, s, a); break;
-        case 16: hipLaunchKernelGGL(rgcn_segment_max_kernel<16>, dim3(blocks), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(rgcn_segment_max_kernel<32>, dim3(blocks), dim3(256), 0, s, a); break;
-    }
-    return (int)hipGetLastError();
+    return launch_row_groups(a.width4, n_out, [&](auto g, dim3 grid) {
+        hipLaunchKernelGGL(rgcn_segment_max_kernel<decltype(g)::value>, grid, dim3(256), 0, s, a);
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" int rgcn_segment_max_bwd(const float* x, int ldx, const float* h, const float* t, int ldh, const float* dh, int lddh,
@@ -203,15 +196,9 @@ extern "C" int rgcn_segment_max_bwd(const float* x, int ldx, const float* h, con
     a.lddh = lddh;
     a.ldc = ldc;
     a.width4 = (width + 3) / 4;
-    const int G = lanes_per_row(a.width4);
-    const long waves = (n_rows + 64 / G - 1) / (64 / G);
-    const long blocks = (waves + 3) / 4;
     hipStream_t s = (hipStream_t)stream;
-    switch (G) {
-        case 4: hipLaunchKernelGGL(rgcn_segment_max_bwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL(rgcn_segment_max_bwd_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, a); break;
-        case 16: hipLaunchKernelGGL(rgcn_segment_max_bwd_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(rgcn_segment_max_bwd_kernel<32>, dim3((unsigned)blocks), dim3(256), 0, s, a); break;
-    }
-    return (int)hipGetLastError();
+    return launch_row_groups(a.width4, a.n_rows, [&](auto g, dim3 grid) {
+        hipLaunchKernelGGL(rgcn_segment_max_bwd_kernel<decltype(g)::value>, grid, dim3(256), 0, s, a);
+        return (int)hipGetLastError();
+    });
 }

@@ -1,7 +1,8 @@
 // rgcn_sort_scan.h -- the integer building blocks the device-side builders share (rgcn_plan.hip: graph plans; rgcn_summary.hip:
-// node partitions and quotient graphs): a stable LSD radix sort of (u64 key, u32 value) pairs, an exclusive scan of u32, head
-// flags / run ids over sorted keys, and the small host helpers around them.  gfx950 only.  Everything has internal linkage: every
-// including source gets its own copy of the kernels.
+// node partitions and quotient graphs; rgcn_sample.hip: in-edge index and fan-out hops; rgcn_minibatch.hip: block indices): a stable
+// LSD radix sort of (u64 key, u32 value) pairs, an exclusive scan of u32, head flags / run ids over sorted keys, and the host
+// plumbing of a builder: carving a workspace (Arena), the other pair of the sort buffers (from_pair), the one read-back of a
+// build's scalars (read_back).  gfx950 only.  Everything has internal linkage: every including source gets its own copy of the kernels.
 //
 //   sort      LSD radix sort, 8-bit digits, stable: per wave-segment digit histograms -> one exclusive scan -> scatter
 //             with wave-level multi-split ranking (ballots), no cross-wave traffic inside a pass
@@ -235,8 +236,42 @@ static __global__ void run_ids_kernel(u32* __restrict__ ex, const u32* __restric
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 static u32 grid_for(u64 n, int threads = 256) { return (u32)((n + threads - 1) / threads); }
 
-static inline int read_u32(const u32* dev, u32* host, hipStream_t s) {
-    hipError_t e = hipMemcpyAsync(host, dev, sizeof(u32), hipMemcpyDeviceToHost, s);
+// ids[i] = index of the run of equal (key >> shift) that element i of the sorted keys lies in; flag keeps the head flags, the
+// number of runs lands in sums[scan_blocks(n)] (device)
+static void run_ids(const u64* keys, u32 n, int shift, u32* flag, u32* ids, u32* sums, hipStream_t s) {
+    hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(n)), dim3(256), 0, s, keys, n, shift, flag);
+    exclusive_scan(flag, ids, n, sums, s);
+    hipLaunchKernelGGL(run_ids_kernel, dim3(grid_for(n)), dim3(256), 0, s, ids, flag, n);
+}
+
+// the SortBufs whose pair 0 is pair `cur` of b: where a sort left its result becomes the next sort's input
+static SortBufs from_pair(const SortBufs& b, int cur) {
+    SortBufs r = b;
+    r.k[0] = b.k[cur];
+    r.k[1] = b.k[cur ^ 1];
+    r.v[0] = b.v[cur];
+    r.v[1] = b.v[cur ^ 1];
+    return r;
+}
+
+// A workspace handed out front to back in 256-byte aligned pieces.  A null base sizes it: every take is nullptr, bytes() the total.
+struct Arena {
+    char* base;
+    size_t off = 0;
+    explicit Arena(void* b) : base((char*)b) {}
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += align_up(count * sizeof(T));
+        return p;
+    }
+    size_t bytes() const { return off; }
+};
+
+// *host = *dev once the stream's work is done: the copy and the synchronisation of a builder's scalars
+template <class T>
+static int read_back(const T* dev, T* host, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return (int)e;
 }

@@ -298,30 +298,25 @@ struct Workspace {
 
 static Workspace carve(void* base, u64 num_keys, u64 n_nodes) {
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t nbytes) {
-        void* p = base ? (char*)base + off : nullptr;
-        off += align_up(nbytes);
-        return p;
-    };
+    Arena ar(base);
     const u64 kmax = num_keys > n_nodes ? num_keys : n_nodes;
     const u32 nseg = sort_segments((u32)kmax);
-    w.res = (Results*)take(sizeof(Results));
-    w.sb.k[0] = (u64*)take(kmax * 8);
-    w.sb.k[1] = (u64*)take(kmax * 8);
-    w.sb.v[0] = (u32*)take(kmax * 4);
-    w.sb.v[1] = (u32*)take(kmax * 4);
-    w.sb.hist = (u32*)take(((size_t)256 * nseg + 1) * 4);
+    w.res = ar.take<Results>(1);
+    w.sb.k[0] = ar.take<u64>(kmax);
+    w.sb.k[1] = ar.take<u64>(kmax);
+    w.sb.v[0] = ar.take<u32>(kmax);
+    w.sb.v[1] = ar.take<u32>(kmax);
+    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
     const u64 scan_len = kmax + 1 > (u64)256 * nseg ? kmax + 1 : (u64)256 * nseg;
-    w.sb.sums = (u32*)take(((size_t)scan_blocks((u32)scan_len) + 2) * 4);
-    w.scan_a = (u32*)take((kmax + 1) * 4);
-    w.scan_b = (u32*)take((kmax + 1) * 4);
-    w.scan_c = (u32*)take((kmax + 1) * 4);
-    w.sig_lo = (u64*)take(n_nodes * 8);
-    w.sig_hi = (u64*)take(n_nodes * 8);
-    w.node_a = (u32*)take((n_nodes + 1) * 4);
-    w.node_b = (u32*)take((n_nodes + 1) * 4);
-    w.bytes = off;
+    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.scan_a = ar.take<u32>(kmax + 1);
+    w.scan_b = ar.take<u32>(kmax + 1);
+    w.scan_c = ar.take<u32>(kmax + 1);
+    w.sig_lo = ar.take<u64>(n_nodes);
+    w.sig_hi = ar.take<u64>(n_nodes);
+    w.node_a = ar.take<u32>(n_nodes + 1);
+    w.node_b = ar.take<u32>(n_nodes + 1);
+    w.bytes = ar.bytes();
     return w;
 }
 
@@ -333,22 +328,6 @@ static int check_graph(const rgcn_graph_t* g) {
     if (g->num_edges < 0 || g->num_nodes <= 0 || g->num_relations <= 0 || g->num_relations > kMaxRelations) return RGCN_ERR_PLAN;
     if (g->num_edges > 0 && (!g->src || !g->dst || !g->type)) return RGCN_ERR_NULL;
     return RGCN_OK;
-}
-
-// the SortBufs whose pair 0 is pair `cur` of b: where a sort left its result becomes the next sort's input
-static SortBufs from_pair(const SortBufs& b, int cur) {
-    SortBufs r = b;
-    r.k[0] = b.k[cur];
-    r.k[1] = b.k[cur ^ 1];
-    r.v[0] = b.v[cur];
-    r.v[1] = b.v[cur ^ 1];
-    return r;
-}
-
-static int read_results(const Results* dev, Results* host, hipStream_t s) {
-    hipError_t e = hipMemcpyAsync(host, dev, sizeof(Results), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return (int)e;
 }
 
 }  // namespace rgcn_summary
@@ -399,9 +378,7 @@ extern "C" int rgcn_summary_round(const rgcn_graph_t* g, int direction, const in
             elem_bits = kl.elem_bits();      // (1 .. 63: the owner has at least one bit)
         } else {
             const int c1 = radix_sort_pairs(ws.sb, M, kl.elem_bits(), s);
-            hipLaunchKernelGGL(head_flags_kernel, dim3(grid_for(M)), dim3(256), 0, s, ws.sb.k[c1], M, 0, ws.scan_a);
-            exclusive_scan(ws.scan_a, ws.scan_b, M, ws.sb.sums, s);
-            hipLaunchKernelGGL(run_ids_kernel, dim3(grid_for(M)), dim3(256), 0, s, ws.scan_b, ws.scan_a, M);
+            run_ids(ws.sb.k[c1], M, 0, ws.scan_a, ws.scan_b, ws.sb.sums, s);
             // the owners sit in v[c1]; the second sort's input goes to the other pair
             hipLaunchKernelGGL(rank_keys_kernel, dim3(grid_for(M)), dim3(256), 0, s, ws.sb.v[c1], ws.scan_b, M, ws.sb.k[c1 ^ 1],
                                ws.sb.v[c1 ^ 1]);
@@ -428,7 +405,7 @@ extern "C" int rgcn_summary_round(const rgcn_graph_t* g, int direction, const in
                        ws.sb.sums + scan_blocks(N), ws.res);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     Results r;
-    if ((st = read_results(ws.res, &r, s)) != 0) return st;
+    if ((st = read_back(ws.res, &r, s)) != 0) return st;
     if (r.error) return RGCN_ERR_GRAPH;
     *num_blocks_out = (int32_t)r.count;
     return RGCN_OK;
@@ -487,7 +464,7 @@ extern "C" int rgcn_summary_quotient(const rgcn_graph_t* g, const int32_t* block
     hipLaunchKernelGGL(publish_count_kernel, dim3(1), dim3(1), 0, s, ws.sb.sums + scan_blocks(E), ws.res);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     Results r;
-    if ((st = read_results(ws.res, &r, s)) != 0) return st;
+    if ((st = read_back(ws.res, &r, s)) != 0) return st;
     if (r.error) return RGCN_ERR_GRAPH;
     const u32 n_runs = r.count;      // 1 .. E
     hipLaunchKernelGGL(quot_emit_kernel, dim3(grid_for(E)), dim3(256), 0, s, sorted, edge, bsrc_of_edge, ws.scan_a, ws.scan_b, E, kl,

@@ -3,6 +3,7 @@
 // rgcn_tile_fp32_wide.hip (64 / 128): two translation units so that the library builds in under a minute.
 #pragma once
 #include "rgcn_kernels_shared.h"
+#include "rgcn_launch.h"
 
 namespace rgcn {
 
@@ -640,13 +641,7 @@ static int launch_tile(const TileArgs& a, int n_tiles, int chunk, hipStream_t st
 }
 template <int KP>
 static int dispatch_tile_np(int NP, const TileArgs& a, int n_tiles, int chunk, hipStream_t s) {
-    switch (NP) {
-        case 16: return launch_tile<KP, 16>(a, n_tiles, chunk, s);
-        case 32: return launch_tile<KP, 32>(a, n_tiles, chunk, s);
-        case 64: return launch_tile<KP, 64>(a, n_tiles, chunk, s);
-        case 128: return launch_tile<KP, 128>(a, n_tiles, chunk, s);
-    }
-    return RGCN_ERR_WIDTH;
+    return for_padded_width(NP, [&](auto np) { return launch_tile<KP, decltype(np)::value>(a, n_tiles, chunk, s); });
 }
 
 

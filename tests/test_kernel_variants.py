@@ -72,8 +72,9 @@ def test_mirror_constants_match_sources():
     # tile-major dW geometry
     assert int(_one("rgcn_dw_tile.hip", r"constexpr int kDwTileT = (\d+);")) == K.DW_TILE_T
     assert int(_one("rgcn_dw_tile.hip", r"constexpr int kDwTileMaxRel = (\d+);")) == K.DW_TILE_MAX_REL
-    # edge-parallel segment sum: G thresholds
-    g = _one("rgcn_ep.hip", r"const int G = ld4 <= (\d+) \? (\d+) : \(ld4 <= (\d+) \? (\d+) : \(ld4 <= (\d+) \? (\d+) : (\d+)\)\);")
+    # edge-parallel segment sum: G thresholds (the rule every row-group launch shares, rgcn_launch.h)
+    g = _one("rgcn_launch.h", r"inline int lanes_per_row\(int width4\) \{ return width4 <= (\d+) \? (\d+) : \(width4 <= (\d+) \? (\d+) : \(width4 <= (\d+) \? (\d+) : (\d+)\)\); \}")
+    assert re.search(r"rgcn_ep_segment_sum\(.*?return launch_row_groups\(ld4, n_out,", _src("rgcn_ep.hip"), re.S)
     assert tuple(map(int, g)) == tuple(v for pair in K.SEGSUM_G for v in pair) + (K.SEGSUM_G_MAX,)
 
 
