@@ -43,6 +43,12 @@ __host__ __device__ inline u64 fmix64(u64 x) {      // MurmurHash3's 64-bit fina
 constexpr u64 kSeedA = 0x9E3779B97F4A7C15ull, kSeedB = 0xD1B54A32D192ED03ull;
 __host__ __device__ inline u64 elem_word_a(u64 e) { return fmix64(e + kSeedA); }
 __host__ __device__ inline u64 elem_word_b(u64 e) { return fmix64(fmix64(e ^ kSeedB) + kSeedA); }
+// The words of a node's OWN block come from seeds of their own.  With the elements' words a node of block x whose one element is
+// the integer y and a node of block y whose one element is x -- two nodes that point at each other's block -- had one signature:
+// word(y) ^ word(x) and word(y) + word(x) do not tell which of the two is the block.
+constexpr u64 kSeedOwnA = 0xA0761D6478BD642Full, kSeedOwnB = 0xE7037ED1A0B428DBull;
+__host__ __device__ inline u64 own_word_a(u64 b) { return fmix64(b + kSeedOwnA); }
+__host__ __device__ inline u64 own_word_b(u64 b) { return fmix64(fmix64(b ^ kSeedOwnB) + kSeedOwnA); }
 
 // ------------------------------------------------------------------------------------------------
 // keys of a refinement round
@@ -147,7 +153,7 @@ __global__ void fold_kernel(u64* __restrict__ sig_lo, u64* __restrict__ sig_hi, 
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
     const u64 own = (u64)(u32)block[i];
-    const u64 lo = fmix64(sig_lo[i] ^ elem_word_a(own)), hi = fmix64(sig_hi[i] + elem_word_b(own));
+    const u64 lo = fmix64(sig_lo[i] ^ own_word_a(own)), hi = fmix64(sig_hi[i] + own_word_b(own));
     sig_lo[i] = lo;
     sig_hi[i] = hi;
     keys[i] = lo;

@@ -69,6 +69,40 @@ def test_quotient_counts_and_order():
     assert qi.tolist() == [[1, 0], [0, 1]] and qt.tolist() == [0, 1] and qm.tolist() == [2, 3]
 
 
+def _equal(a, b, what):
+    assert a.block.dtype == b.block.dtype == torch.int64 and torch.equal(a.block, b.block), what
+    assert (a.num_blocks, a.rounds, a.counts, a.converged) == (b.num_blocks, b.rounds, b.counts, b.converged), what
+
+
+@pytest.mark.parametrize("direction", ("out", "in", "in_out"))
+@pytest.mark.parametrize("k", (1, 3, None))
+def test_the_sparse_oracle_equals_the_set_oracle(direction, k):
+    """graphs where most nodes own no edge (the form tests/test_gpu_summary_edges.py uses at 2^24 nodes), with and without an
+    initial partition whose ids are neither dense nor in canonical order; then the path and the hub graph"""
+    for seed, (n, pool, e, r) in enumerate(((600, 40, 150, 3), (900, 25, 60, 2), (70, 70, 200, 5))):
+        g = torch.Generator().manual_seed(seed)
+        nodes = torch.randperm(n, generator=g)[:pool]
+        nodes[0], nodes[1] = 0, n - 1                                    # (twice in the pool at worst)
+        ei = nodes[torch.randint(0, pool, (2, e), generator=g)]
+        et = torch.randint(0, r, (e,), generator=g)
+        ei[:, :5] = ei[:, 5:10]                                          # duplicate edges
+        et[:5] = et[5:10]
+        ei[1, 10:14] = ei[0, 10:14]                                      # self-loops
+        initial = 9 - torch.arange(n) % 7 * 3 % 10
+        for init in (None, initial):
+            want = R.node_partition(ei, et, n, r, k=k, direction=direction, initial=init)
+            _equal(R.node_partition_sparse(ei, et, n, r, k=k, direction=direction, initial=init), want, (seed, init is None))
+        assert want.num_blocks > 7                                       # the edges split the initial blocks
+    ei, et = R.path_graph(10)
+    _equal(R.node_partition_sparse(ei, et, 10, 1, k=k, direction=direction),
+           R.node_partition(ei, et, 10, 1, k=k, direction=direction), "path")
+    _equal(R.node_partition_sparse(ei, et, 10, 1, k=None, direction=direction, max_rounds=6),
+           R.node_partition(ei, et, 10, 1, k=None, direction=direction, max_rounds=6), "path, cut short")
+    ei, et, n, init, _ = R.hub_graph(deg=50, lead=5)
+    _equal(R.node_partition_sparse(ei, et, n, 1, k=k, direction=direction, initial=init),
+           R.node_partition(ei, et, n, 1, k=k, direction=direction, initial=init), "hub")
+
+
 def test_hub_graph_is_what_it_says():
     ei, et, n, init, (h1, h2, h3) = R.hub_graph(deg=50, lead=5)
     p = R.node_partition(ei, et, n, 1, k=1, direction="out", initial=init)
