@@ -566,6 +566,36 @@ size_t rgcn_mb_bwd_dw_workspace_bytes(const rgcn_mb_index_t* index, int din, int
 int rgcn_mb_bwd_dw(const rgcn_mb_index_t* index, const float* h, int ldh, int din, const float* g, int ldg, int dout, float* d_weight,
                    float* d_root, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sparse embedding rows: a row-wise Adam step on the rows a mini-batch gathered (csrc/rgcn_emb_rows.hip) -------
+ * table / exp_avg / exp_avg_sq: `planes` planes of [num_nodes][ld] floats, plane_stride ELEMENTS apart (planes = 1: an nn.Embedding
+ * weight; planes = S: a stacked [S, N, emb] parameter); row_step [num_nodes]: the steps every row has taken, shared by the planes.
+ * nodes [n_rows]: int64 node ids; grad: `planes` planes of [n_rows][ldg], grad_plane_stride elements apart: one gradient row per
+ * position of `nodes`.  For every node n that `nodes` lists:
+ *   g = the sum of the gradient rows of every position that lists n, added in ascending position order;  g += weight_decay * p
+ *   t = ++row_step[n];   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2
+ *   p -= lr * (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps)
+ * which is torch.optim.Adam (L2 weight decay, no amsgrad) applied to that row alone with the row's own step count: a row listed on
+ * every step evolves as under the dense optimizer.  Rows that are not listed are NOT READ AND NOT WRITTEN: no momentum carry-over
+ * and no weight decay for them.  1 - beta^t is accurate to fp32 rounding (-expm1f(t ln beta), ln beta taken in double).
+ * assume_unique != 0: the caller guarantees distinct ids (a sampler's src_nodes); no sort, no workspace.  With duplicates the
+ *   result for those rows is unspecified, but nothing outside the listed rows is written.
+ * assume_unique == 0: (id, position) pairs are sorted by id in `workspace` (rgcn_emb_adam_rows_workspace_bytes) and every run of
+ *   equal ids is one update.
+ * An id outside [0, num_nodes) writes nothing and adds 1 to *bad_ids (a device word the caller zeroes and reads when it next
+ * synchronises; may be NULL).  The call is asynchronous: it allocates nothing and reads nothing back.  No float atomics: the same
+ * inputs give the same bits.  All row addressing is in 64-bit element offsets on plain pointers (planes * num_nodes * ld may pass
+ * 2^31).  Whole 16-byte pieces of a row move as such when ld, ldg, the plane strides and the four float bases are 16-byte
+ * aligned; anything else goes element by element.
+ * Refusals, before any launch: NULL table / moments / row_step (or nodes / grad with n_rows > 0): RGCN_ERR_NULL; width outside
+ * 1 .. ld or > ldg, planes < 1, a negative count or stride, beta outside [0, 1), eps <= 0, lr < 0, weight_decay < 0:
+ * RGCN_ERR_ARG; n_rows > 0xFFFF0000: RGCN_ERR_PLAN; with assume_unique == 0 a workspace smaller than the query:
+ * RGCN_ERR_WORKSPACE.  n_rows == 0 launches nothing. */
+size_t rgcn_emb_adam_rows_workspace_bytes(int64_t n_rows, int32_t num_nodes);   /* 0 on bad arguments; 0 is also right for assume_unique callers */
+int rgcn_emb_adam_rows(float* table, float* exp_avg, float* exp_avg_sq, int32_t* row_step, int planes, int64_t plane_stride,
+                       int32_t num_nodes, int width, int ld, const int64_t* nodes, int64_t n_rows, const float* grad,
+                       int64_t grad_plane_stride, int ldg, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int assume_unique, int32_t* bad_ids, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

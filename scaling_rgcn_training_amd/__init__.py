@@ -16,6 +16,7 @@ Sub-modules:
 * ``sampling`` -- ``NeighborSampler``: fan-out neighbour sampling on the GPU into the layered bipartite ``Block`` lists that
   ``forward_blocks`` / ``Trainer.train_minibatch`` walk; ``block_index`` / ``BlockIndex``: the index ``RGCNConv.forward_block``
   runs a layer from, straight from a block, without graph plans
+* ``sparse_optim`` -- ``RowAdam``: Adam on the embedding rows a mini-batch step gathered, nothing else of the table is touched
 
 There is no CPU compute path: the layer raises if the HIP library or a GPU is missing.
 """
@@ -44,4 +45,7 @@ def __getattr__(name):
     if name in ("NeighborSampler", "Block", "BlockIndex", "block_index"):
         from . import sampling
         return getattr(sampling, name)
+    if name == "RowAdam":
+        from .sparse_optim import RowAdam
+        return RowAdam
     raise AttributeError(name)

@@ -74,7 +74,7 @@ class RgcnPlanSizes(C.Structure):
 
 def _prototypes() -> dict:
     """name -> (restype, [argtypes]) of every entry point of include/rgcn_mi355x.h, as load() installs them"""
-    vp, i32, u32, i64, sz, lng = C.c_void_p, C.c_int, C.c_uint, C.c_int64, C.c_size_t, C.c_long
+    vp, i32, u32, i64, sz, lng, f32 = C.c_void_p, C.c_int, C.c_uint, C.c_int64, C.c_size_t, C.c_long, C.c_float
     plan, units, graph, sizes, pint = (C.POINTER(RgcnPlanStruct), C.POINTER(RgcnEdgeUnits), C.POINTER(RgcnGraphStruct),
                                        C.POINTER(RgcnPlanSizes), C.POINTER(C.c_int))
     return {
@@ -134,6 +134,9 @@ def _prototypes() -> dict:
         "rgcn_mb_bwd_dx": (i32, [C.POINTER(RgcnMbIndex), vp, i32, i32, vp, vp, i32, vp, i32, i32, vp]),
         "rgcn_mb_bwd_dw_workspace_bytes": (sz, [C.POINTER(RgcnMbIndex), i32, i32]),
         "rgcn_mb_bwd_dw": (i32, [C.POINTER(RgcnMbIndex), vp, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+        "rgcn_emb_adam_rows_workspace_bytes": (sz, [i64, i32]),
+        "rgcn_emb_adam_rows": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, f32, i32, vp, vp,
+                                     sz, vp]),
     }
 
 
@@ -579,6 +582,53 @@ def mb_bwd_dw(ix: MbIndex, h: torch.Tensor, din: int, g: torch.Tensor, dout: int
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
         check(lib.rgcn_mb_bwd_dw(C.byref(ix.struct), h.data_ptr(), h.stride(0), din, g.data_ptr(), g.stride(0), dout, _ptr(d_weight),
                                  _ptr(d_root), _ptr(ws), nbytes, _stream(g)), "rgcn_mb_bwd_dw")
+
+
+# ---- sparse embedding rows (rgcn_emb_rows.hip) --------------------------------------------------------------------------
+def emb_adam_rows_workspace_bytes(n_rows: int, num_nodes: int) -> int:
+    return int(load().rgcn_emb_adam_rows_workspace_bytes(int(n_rows), int(num_nodes)))
+
+
+def emb_adam_rows(table: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, row_step: torch.Tensor, nodes: torch.Tensor,
+                  grad: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                  assume_unique: bool = False, bad_ids: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> None:
+    """rgcn_emb_adam_rows on device tensors: ``table`` [N, E] or [S, N, E] (fp32, last dimension contiguous, updated in place),
+    its moments with the table's strides, ``row_step`` int32 [N], ``nodes`` int64 [n], ``grad`` [n, E] or [S, n, E], ``bad_ids``
+    int32 [1] or None.  ``workspace``: uint8, at least ``emb_adam_rows_workspace_bytes`` unless ``assume_unique`` (allocated
+    here when it is missing).  Asynchronous on the current stream of the table's device."""
+    lib, dev = load(), table.device
+    if table.dim() not in (2, 3) or grad.dim() != table.dim():
+        raise RgcnLibraryError(f"rgcn_emb_adam_rows: table is [N, E] or [S, N, E] and grad has as many dimensions "
+                               f"(got {tuple(table.shape)}, {tuple(grad.shape)})")
+    for name, t, dtype in (("table", table, torch.float32), ("exp_avg", exp_avg, torch.float32), ("exp_avg_sq", exp_avg_sq, torch.float32),
+                           ("grad", grad, torch.float32), ("row_step", row_step, torch.int32), ("nodes", nodes, torch.int64)):
+        if t.device != dev or t.dtype != dtype:
+            raise RgcnLibraryError(f"rgcn_emb_adam_rows: {name} must be {dtype} on {dev} (got {t.dtype} on {t.device})")
+    planes = int(table.shape[0]) if table.dim() == 3 else 1
+    n_nodes, width, n = int(table.shape[-2]), int(table.shape[-1]), int(nodes.shape[0])
+    for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t.shape != table.shape or t.stride() != table.stride():
+            raise RgcnLibraryError(f"rgcn_emb_adam_rows: {name} must have the table's shape and strides")
+    if (table.stride(-1) != 1 and width > 1) or (grad.stride(-1) != 1 and width > 1):
+        raise RgcnLibraryError("rgcn_emb_adam_rows: the last dimension of table and grad must be contiguous")
+    if nodes.dim() != 1 or (n > 1 and nodes.stride(0) != 1) or not row_step.is_contiguous() or int(row_step.shape[0]) != n_nodes:
+        raise RgcnLibraryError("rgcn_emb_adam_rows: nodes must be a contiguous vector and row_step a contiguous [N]")
+    if int(grad.shape[-2]) != n or int(grad.shape[-1]) != width or (planes > 1 and int(grad.shape[0]) != planes):
+        raise RgcnLibraryError(f"rgcn_emb_adam_rows: grad {tuple(grad.shape)} does not hold one row of {width} per listed node ({n})")
+    if n == 0:      # (nothing to do; an empty tensor has no address to pass)
+        return
+    nbytes = 0
+    with torch.cuda.device(dev):
+        if not assume_unique:
+            if workspace is None:
+                workspace = torch.empty(lib.rgcn_emb_adam_rows_workspace_bytes(n, n_nodes), dtype=torch.uint8, device=dev)
+            nbytes = int(workspace.numel())
+        check(lib.rgcn_emb_adam_rows(table.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), row_step.data_ptr(), planes,
+                                     table.stride(0) if table.dim() == 3 else 0, n_nodes, width, table.stride(-2), nodes.data_ptr(), n,
+                                     grad.data_ptr(), grad.stride(0) if grad.dim() == 3 else 0, grad.stride(-2), lr, beta1, beta2, eps,
+                                     weight_decay, int(bool(assume_unique)), _ptr(bad_ids),
+                                     None if assume_unique else workspace.data_ptr(), nbytes, _stream(table)), "rgcn_emb_adam_rows")
 
 
 # ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------

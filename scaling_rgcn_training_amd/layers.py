@@ -73,7 +73,38 @@ class _RGCNStack(nn.Module):
             raise ValueError(f"the models have two RGCN layers: forward_blocks takes 2 blocks, got {len(blocks)}")
         return self._tail_blocks(self._block_input(blocks[0].src_nodes), blocks, activation, block_kernels)
 
+    def forward_blocks_from_rows(self, blocks, activation: Callable, embedding_rows: Tensor, block_kernels: bool = False) -> Tensor:
+        """``forward_blocks`` without the gather through autograd (whose backward fills a table-sized gradient): ``embedding_rows``
+        is the leaf ``self.embedding_rows(blocks[0].src_nodes)`` returned; the pre-transform starts from it and its ``.grad`` is
+        the gradient of exactly those rows.  The same output as ``forward_blocks``, bit for bit.  (A method of its
+        own: ``forward_blocks`` keeps its signature.)"""
+        if not isinstance(block_kernels, bool):
+            raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
+        if len(blocks) != 2:
+            raise ValueError(f"the models have two RGCN layers: forward_blocks_from_rows takes 2 blocks, got {len(blocks)}")
+        if not torch.is_tensor(embedding_rows) or embedding_rows.dim() < 2 or embedding_rows.shape[-2] != blocks[0].n_src:
+            raise ValueError(f"embedding_rows must hold one row per source node of blocks[0] ({blocks[0].n_src})")
+        return self._tail_blocks(self._pre_transform(embedding_rows), blocks, activation, block_kernels)
+
     def _block_input(self, nodes: Tensor) -> Tensor:
+        """``_pre_transform`` of the rows ``nodes`` gathered from the table through autograd"""
+        raise NotImplementedError
+
+    def embedding_table(self) -> Tensor:
+        """the embedding table: ``[N, E]``, or the ``[S, N, E]`` parameter of the attention model"""
+        emb = self.embedding
+        return emb.weight if isinstance(emb, nn.Embedding) else emb
+
+    def embedding_rows(self, nodes: Tensor) -> Tensor:
+        """The rows ``nodes`` of the DETACHED embedding table as a leaf that requires a gradient: ``[n, E]`` (``[S, n, E]`` in the
+        attention model).  Given to ``forward_blocks_from_rows(blocks, activation, rows)``, ``rows.grad`` after the backward is one gradient
+        row per entry of ``nodes`` -- what ``sparse_optim.RowAdam.step(nodes, rows.grad)`` takes -- and no table-sized gradient
+        is ever allocated."""
+        table = self.embedding_table().detach()
+        return (table[:, nodes] if table.dim() == 3 else table[nodes]).requires_grad_(True)
+
+    def _pre_transform(self, rows: Tensor) -> Tensor:
+        """gathered embedding rows -> the input rows of rgcn1 (identity, MLP or attention)"""
         raise NotImplementedError
 
     def override_params(self, weight_1: Tensor, bias_1: Tensor, root_1: Tensor, weight_2: Tensor,
@@ -101,6 +132,9 @@ class Emb_Layers(_RGCNStack):
     def _block_input(self, nodes: Tensor) -> Tensor:
         return self.embedding(nodes)
 
+    def _pre_transform(self, rows: Tensor) -> Tensor:
+        return rows
+
     def reset_embedding(self, num_nodes: int, emb_dim: int) -> None:
         self.embedding = nn.Embedding(num_nodes, emb_dim)
 
@@ -124,7 +158,9 @@ class Emb_ATT_Layers(_RGCNStack):
         return self._tail(attn_output[0], training_data, activation)
 
     def _block_input(self, nodes: Tensor) -> Tensor:
-        emb = self.embedding[:, nodes]      # the node axis: attention runs over the S axis of the gathered nodes only
+        return self._pre_transform(self.embedding[:, nodes])
+
+    def _pre_transform(self, emb: Tensor) -> Tensor:      # [S, n, emb]: attention runs over the S axis of the gathered nodes only
         attn_output, _ = self.att(emb, emb, emb, average_attn_weights=True)
         return attn_output[0]
 
@@ -153,7 +189,10 @@ class Emb_MLP_Layers(_RGCNStack):
         return self._tail(x, training_data, activation)
 
     def _block_input(self, nodes: Tensor) -> Tensor:
-        return self.lin2(torch.tanh(self.lin1(self.embedding(nodes))))
+        return self._pre_transform(self.embedding(nodes))
+
+    def _pre_transform(self, rows: Tensor) -> Tensor:
+        return self.lin2(torch.tanh(self.lin1(rows)))
 
     def load_embedding(self, embedding: Tensor, freeze: bool = True) -> None:
         self.embedding = nn.Embedding.from_pretrained(embedding, freeze=freeze)

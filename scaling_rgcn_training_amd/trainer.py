@@ -105,7 +105,7 @@ class Trainer:
     HIPGRAPH_AUTO_MAX_EDGES = 2_000_000
 
     def __init__(self, data, hidden_l: int, epochs: int, emb_dim: int, lr: float, weight_d: float,
-                 eval_no_grad: bool = True, verbose: bool = True, hipgraph="auto"):
+                 eval_no_grad: bool = True, verbose: bool = True, hipgraph="auto", sparse_embedding: bool = False):
         self.data = data
         self.hidden_l, self.epochs, self.emb_dim, self.lr, self.weight_d = hidden_l, epochs, emb_dim, lr, weight_d
         self.sumModel: nn.Module = None
@@ -117,6 +117,11 @@ class Trainer:
         self.hipgraph = hipgraph
         self.last_train_mode = None
         self.last_batches = []      # train_minibatch: the batches (node ids) of the last epoch
+        # train_minibatch: True makes a step touch only the embedding rows it gathered (sparse_optim.RowAdam on the table, DESIGN.md
+        # 16); rows a step did not gather then do not move.  An option of the trainer: train_minibatch keeps its signature.
+        if not isinstance(sparse_embedding, bool):
+            raise ValueError(f"sparse_embedding must be a bool (got {sparse_embedding!r})")
+        self.sparse_embedding = sparse_embedding
 
     def transfer_weights(self, orgModel: nn.Module, grad: bool) -> None:
         s = self.sumModel
@@ -231,10 +236,20 @@ class Trainer:
         (mod 2^63; the sampler mixes it): runs repeat, steps differ.  The epoch's
         loss is the mean over its batches.  Eager only -- block shapes change every step, nothing is captured.  Returns the four
         lists of ``train``; ``self.last_batches`` holds the last epoch's batches (tensors of node ids).  ``block_kernels`` goes to
-        ``model.forward_blocks``: True runs both layers straight from their blocks (no graph plans)."""
+        ``model.forward_blocks``: True runs both layers straight from their blocks (no graph plans).
+        With ``self.sparse_embedding`` (``Trainer(..., sparse_embedding=True)``; off by default) and a trainable embedding: a step touches only the embedding
+        rows it gathered.  ``torch.optim.Adam`` runs over every parameter but the table, ``sparse_optim.RowAdam`` (same ``lr`` and
+        ``weight_d``) over the table's rows ``blocks[0].src_nodes``, on the gradient of ``model.embedding_rows``; no table-sized
+        gradient exists.  THE SEMANTICS DIFFER from the dense optimizer: a row that a step did not gather does not move in that
+        step -- no momentum carry-over and no weight decay for it -- and every row's bias correction counts the row's own steps.
+        ``RowAdam.check()`` (ids out of range) runs once per epoch, beside the loss read-back.  With a frozen embedding the flag
+        changes nothing."""
         from .sampling import check_fanouts, check_sample_seed
         if not isinstance(block_kernels, bool):
             raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
+        sparse_embedding = getattr(self, "sparse_embedding", False)
+        if not isinstance(sparse_embedding, bool):
+            raise ValueError(f"Trainer.sparse_embedding must be a bool (got {sparse_embedding!r})")
         if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
             raise ValueError(f"batch_size must be an int >= 1 (got {batch_size!r})")
         fanouts = check_fanouts(fanouts)
@@ -249,7 +264,14 @@ class Trainer:
         n_train = int(x_train.shape[0])
         self.last_train_mode = "eager"
         self.last_batches = []
-        optimizer = torch.optim.Adam(model.parameters(), lr=self.lr, weight_decay=self.weight_d)
+        row_adam = None
+        table = model.embedding_table() if sparse_embedding else None
+        if table is not None and table.requires_grad:
+            from .sparse_optim import RowAdam
+            row_adam = RowAdam(table, lr=self.lr, weight_decay=self.weight_d)
+            optimizer = torch.optim.Adam([p for p in model.parameters() if p is not table], lr=self.lr, weight_decay=self.weight_d)
+        else:
+            optimizer = torch.optim.Adam(model.parameters(), lr=self.lr, weight_decay=self.weight_d)
         perm_gen = torch.Generator().manual_seed(seed)
         accuracies, losses, f1_ws, f1_ms = [], [], [], []
         for epoch in range(self.epochs):
@@ -271,13 +293,21 @@ class Trainer:
                 step_seed = (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
                 blocks = sampler.sample(batch, fanouts, step_seed)
                 optimizer.zero_grad()
-                out = model.forward_blocks(blocks, activation, block_kernels) if block_kernels else model.forward_blocks(blocks, activation)
+                if row_adam is not None:
+                    emb_rows = model.embedding_rows(blocks[0].src_nodes)
+                    out = model.forward_blocks_from_rows(blocks, activation, emb_rows, block_kernels)
+                else:
+                    out = model.forward_blocks(blocks, activation, block_kernels) if block_kernels else model.forward_blocks(blocks, activation)
                 output = loss_f(out, targets[rows])
                 output.backward()
                 optimizer.step()
+                if row_adam is not None:
+                    row_adam.step(blocks[0].src_nodes, emb_rows.grad, assume_unique=True)
                 batch_losses.append(output.detach())
                 batches.append(batch)
             loss_value = float(torch.stack(batch_losses).mean().item()) if batch_losses else float("nan")
+            if row_adam is not None:
+                row_adam.check()
             losses.append(loss_value)
             self.last_batches = batches
             if self.verbose and epoch % 10 == 0:
