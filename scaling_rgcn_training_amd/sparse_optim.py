@@ -53,7 +53,10 @@ class RowAdam:
             nodes = nodes.long()
         nodes = nodes.contiguous()
         grad_rows = grad_rows.detach()
-        if grad_rows.shape[-1] > 1 and grad_rows.stride(-1) != 1:
+        # the kernel takes any row and plane stride that keeps rows apart; a last dimension that is not contiguous, and rows or
+        # planes that overlap (an expanded view has stride 0), are copied
+        e = grad_rows.shape[-1]
+        if (e > 1 and grad_rows.stride(-1) != 1) or any(grad_rows.stride(d) < e for d in range(grad_rows.dim() - 1)):
             grad_rows = grad_rows.contiguous()
         n = int(nodes.shape[0])
         if not assume_unique and n > 0:

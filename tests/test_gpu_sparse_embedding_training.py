@@ -2,7 +2,8 @@
 training rows in batches of 32, fan-outs (3, 3), block kernels, 2 epochs, for the three models:
   * a by-hand twin -- the dense path's table gradient at ``src_nodes`` fed to the float64 row-wise Adam of
     tests/row_adam_reference.py, the other parameters under ``torch.optim.Adam`` -- ends with the trained table, per row within
-    (steps of the row) x (2^-22 max|p| + 2^-18 lr);
+    (steps of the row) x (2^-22 max|p| + 2^-18 lr); the same twin without block kernels (``emb``, ``att``) and with batches of 48,
+    whose last one holds 16 rows (``emb``);
   * rows outside the union of every step's ``src_nodes`` keep their bits at ``weight_d = 0.01`` (under the dense optimizer they move);
   * after the first step the other parameters equal the dense run's bit for bit at ``weight_d = 0``;
   * with a frozen embedding the flag changes nothing; ``forward_blocks`` is today's output and ``forward_blocks_from_rows``
@@ -62,21 +63,21 @@ def _model(kind, freeze=False):
     return model
 
 
-def _train(model, wd, sparse, epochs=EPOCHS, loss_f=None):
+def _train(model, wd, sparse, epochs=EPOCHS, loss_f=None, batch_size=BATCH, block_kernels=True):
     from scaling_rgcn_training_amd.trainer import Trainer, bce_loss
     gobj = _graph()
     kw = dict(sparse_embedding=True) if sparse else {}
     tr = Trainer(None, HID, epochs=epochs, emb_dim=EMB, lr=LR, weight_d=wd, verbose=False, **kw)
     assert tr.sparse_embedding is sparse
     torch.manual_seed(5)                 # the attention model's dropout
-    _, losses, _, _ = tr.train_minibatch(model, gobj, loss_f or bce_loss, torch.sigmoid, batch_size=BATCH, fanouts=FANOUTS,
-                                         sum_graph=True, seed=SEED, block_kernels=True)
+    _, losses, _, _ = tr.train_minibatch(model, gobj, loss_f or bce_loss, torch.sigmoid, batch_size=batch_size, fanouts=FANOUTS,
+                                         sum_graph=True, seed=SEED, block_kernels=block_kernels)
     torch.cuda.synchronize()
     assert len(losses) == epochs and all(np.isfinite(losses))
     return tr
 
 
-def _steps(epochs=EPOCHS):
+def _steps(epochs=EPOCHS, batch_size=BATCH):
     """(epoch, rows of x_train, their node ids, blocks) of every step of ``train_minibatch(seed=SEED)``: the trainer's permutation
     and step seeds, the sampler asked again"""
     from scaling_rgcn_training_amd.sampling import NeighborSampler
@@ -88,8 +89,8 @@ def _steps(epochs=EPOCHS):
     out = []
     for epoch in range(epochs):
         perm = torch.randperm(64, generator=perm_gen).to(dev)
-        for b, start in enumerate(range(0, 64, BATCH)):
-            rows = perm[start:start + BATCH]
+        for b, start in enumerate(range(0, 64, batch_size)):
+            rows = perm[start:start + batch_size]
             step_seed = (SEED * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
             out.append((epoch, rows, x_train[rows], sampler.sample(x_train[rows], FANOUTS, step_seed)))
     return out
@@ -121,11 +122,9 @@ def _union():
     return listed, [batch.cpu() for epoch, _, batch, _ in steps if epoch == EPOCHS - 1]
 
 
-@pytest.mark.parametrize("kind", KINDS)
-def test_by_hand_twin(kind):
+def _by_hand_twin(kind, trained, batch_size=BATCH, block_kernels=True):
     from scaling_rgcn_training_amd.trainer import bce_loss
     dev = torch.device("cuda:0")
-    _, trained, _ = _sparse_run(kind)
     model = _model(kind).to(dev)
     table = model.embedding_table()
     ref = [table.detach().cpu().double().numpy().copy(), np.zeros(tuple(table.shape)), np.zeros(tuple(table.shape)),
@@ -133,13 +132,13 @@ def test_by_hand_twin(kind):
     hyper = {k: float(np.float32(v)) for k, v in dict(lr=LR, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01).items()}
     opt = torch.optim.Adam([p for p in model.parameters() if p is not table], lr=LR, weight_decay=0.01)
     targets = _graph().training_data.y_train.to(dev).to(torch.float32)
-    steps = _steps()
+    steps = _steps(batch_size=batch_size)
     torch.manual_seed(5)
     model.train()
     for _, rows, _, blocks in steps:
         opt.zero_grad()
         table.grad = None
-        bce_loss(model.forward_blocks(blocks, torch.sigmoid, True), targets[rows]).backward()      # the dense path
+        bce_loss(model.forward_blocks(blocks, torch.sigmoid, block_kernels), targets[rows]).backward()      # the dense path
         opt.step()
         src = blocks[0].src_nodes
         assert row_adam_step(*ref, src.cpu().numpy(), _rows(table.grad, src).cpu().double().numpy(), hyper) == 0
@@ -149,9 +148,33 @@ def test_by_hand_twin(kind):
     per_row = tolerance(ref[3].astype(np.float64), np.abs(ref[0]).max(), LR)[:, None]
     err = np.abs(trained.double().numpy() - ref[0])
     touched = ref[3] > 0
-    print(f"twin {kind}: {int(touched.sum())} rows touched, max error {err.max():.3e}, "
-          f"largest error / tolerance {np.max(err[..., touched, :] / per_row[touched]):.3f}")
+    print(f"twin {kind} batch_size={batch_size} block_kernels={block_kernels}: {int(touched.sum())} rows touched, "
+          f"max error {err.max():.3e}, largest error / tolerance {np.max(err[..., touched, :] / per_row[touched]):.3f}")
     assert np.all(err <= per_row)
+    return steps
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_by_hand_twin(kind):
+    _, trained, _ = _sparse_run(kind)
+    _by_hand_twin(kind, trained)
+
+
+@pytest.mark.parametrize("kind", ["emb", "att"])
+def test_by_hand_twin_without_block_kernels(kind):
+    """``forward_blocks_from_rows(..., block_kernels=False)``: the layers run on their graph-plan kernels, the table on RowAdam"""
+    model = _model(kind)
+    _train(model, 0.01, True, block_kernels=False)
+    _by_hand_twin(kind, _table(model).cpu(), block_kernels=False)
+
+
+def test_by_hand_twin_with_a_short_last_batch():
+    """batches of 48 over the 64 training rows: every epoch ends with a batch of 16"""
+    model = _model("emb")
+    tr = _train(model, 0.01, True, batch_size=48)
+    assert [len(b) for b in tr.last_batches] == [48, 16]
+    steps = _by_hand_twin("emb", _table(model).cpu(), batch_size=48)
+    assert [len(rows) for _, rows, _, _ in steps] == [48, 16, 48, 16]
 
 
 @pytest.mark.parametrize("kind", KINDS)
