@@ -496,6 +496,54 @@ int rgcn_sample_hop(const rgcn_sample_index_t* index, const int64_t* dst_nodes, 
                     uint32_t* node_map, int64_t* edge_src_out, int64_t* edge_dst_out, int64_t* edge_type_out, int64_t* src_nodes_out,
                     void* workspace, size_t workspace_bytes, int64_t* num_edges_out, int64_t* num_src_out, void* stream);
 
+/* ---- neighbour sampling with one fan-out PER RELATION (csrc/rgcn_sample.hip) ------------------------------------
+ * RGCNConv normalises per (destination, relation), so the sampling unit here is the RUN: the in-edges of one destination v with
+ * one relation t.  Additions to the calls above, which are unchanged; RGCN_ABI_VERSION stays.
+ * Relation index: the edges sorted stably by (destination, relation); a run is the maximal group of sorted edges with one (v, t),
+ * its edges in input order (duplicate triples stay distinct).  run_ptr[v] .. run_ptr[v + 1] are the runs of v, ascending in t;
+ * run_beg[q] .. run_beg[q + 1] the positions of run q in the sorted edge list, run_type[q] its relation; src the sorted edges'
+ * sources.  Limits as above: num_edges <= 0xFFFF0000, num_relations <= 65536 (RGCN_ERR_PLAN beyond).
+ * Hop: fanouts is a HOST array of num_relations entries, each in {-1, 0} u [1, 256]: -1 takes a run whole, 0 takes nothing of
+ * that relation.  A run of length d of destination v and relation t is taken whole when fanouts[t] == -1 or d <= fanouts[t],
+ * otherwise a uniform fanouts[t]-subset of its positions 0 .. d-1 by the Floyd loop above, the generator keyed per relation too:
+ *   key      = mix(seed + 0x9E3779B97F4A7C15 * (hop + 1))
+ *   kv       = mix(mix(key + v) + 0xD1B54A32D192ED03 * (t + 1))
+ *   r        = mix(kv + j);   draw(j) = ((r >> 32) * (j + 1)) >> 32
+ * so the choice depends on (seed, hop, v, t) alone -- not on the batch, not on the other entries of fanouts.  The block:
+ * src_nodes as above; edges ordered by destination position, then relation, then ascending position in the run.
+ * cap, the most edges a block can hold: num_edges if any entry is -1, else min(num_edges, num_dst * sum of the positive entries).
+ * Both calls allocate nothing and synchronise the stream once.  Errors as above: an id or a destination out of range
+ * RGCN_ERR_GRAPH, a destination listed twice RGCN_ERR_ARG (found on the device: outputs unspecified, nothing written outside them,
+ * node_map reset); a fan-out entry outside its domain, seed < 0, hop < 0, num_dst < 0 or > num_nodes: RGCN_ERR_ARG before any
+ * launch. */
+typedef struct rgcn_sample_rel_index {
+    const uint32_t* run_ptr;   /* [num_nodes + 1] */
+    const uint32_t* run_beg;   /* [num_runs + 1] */
+    const int32_t* run_type;   /* [num_runs] (may be NULL when num_edges == 0) */
+    const int32_t* src;        /* [num_edges] (may be NULL when num_edges == 0) */
+    int64_t num_edges;
+    int64_t num_runs;
+    int32_t num_nodes;
+    int32_t num_relations;
+} rgcn_sample_rel_index_t;
+
+/* Bytes of scratch (0 on bad arguments, a fan-out entry outside its domain included). */
+size_t rgcn_sample_rel_index_workspace_bytes(int64_t num_edges, int32_t num_nodes);
+size_t rgcn_sample_hop_rel_workspace_bytes(int64_t num_dst, const int32_t* fanouts, int32_t num_relations, int64_t num_edges,
+                                           int64_t num_runs, int32_t num_nodes);
+
+/* run_ptr_out [num_nodes + 1]; run_beg_out [num_edges + 1] and run_type_out [num_edges] (the worst case: every edge a run of its
+ * own), of which num_runs + 1 / num_runs entries are written; src_out [num_edges]; *num_runs_out (host).  run_type_out / src_out
+ * may be NULL when num_edges == 0. */
+int rgcn_sample_rel_index_build(const rgcn_graph_t* graph, uint32_t* run_ptr_out, uint32_t* run_beg_out, int32_t* run_type_out,
+                                int32_t* src_out, void* workspace, size_t workspace_bytes, int64_t* num_runs_out, void* stream);
+
+/* One hop; node_map and the outputs as rgcn_sample_hop, sized by this call's cap. */
+int rgcn_sample_hop_rel(const rgcn_sample_rel_index_t* index, const int64_t* dst_nodes, int64_t num_dst, const int32_t* fanouts,
+                        int64_t seed, int hop, uint32_t* node_map, int64_t* edge_src_out, int64_t* edge_dst_out,
+                        int64_t* edge_type_out, int64_t* src_nodes_out, void* workspace, size_t workspace_bytes,
+                        int64_t* num_edges_out, int64_t* num_src_out, void* stream);
+
 /* ---- mini-batch layers: a bipartite R-GCN layer straight from a sampled block (csrc/rgcn_minibatch.hip) ----------
  * ("block" in this header already means block-diagonal weights: hence rgcn_mb_.)  For a block of E_b edges (strided int64 src /
  * dst / type, src in [0, n_src), dst in [0, n_dst), type in [0, R)) whose destinations are its first n_dst source rows

@@ -57,6 +57,12 @@ class RgcnSampleIndex(C.Structure):
                 ("num_edges", C.c_int64), ("num_nodes", C.c_int32), ("num_relations", C.c_int32)]
 
 
+class RgcnSampleRelIndex(C.Structure):
+    """struct rgcn_sample_rel_index: the (destination, relation) run index of a graph (rgcn_sample_rel_index_build)"""
+    _fields_ = [("run_ptr", C.c_void_p), ("run_beg", C.c_void_p), ("run_type", C.c_void_p), ("src", C.c_void_p),
+                ("num_edges", C.c_int64), ("num_runs", C.c_int64), ("num_nodes", C.c_int32), ("num_relations", C.c_int32)]
+
+
 class RgcnMbIndex(C.Structure):
     """struct rgcn_mb_index: the index of one sampled block (rgcn_mb_index_build)"""
     _fields_ = [("tile_ptr", C.c_void_p), ("row_beg", C.c_void_p), ("row_cnt", C.c_void_p), ("row_dst", C.c_void_p),
@@ -127,6 +133,11 @@ def _prototypes() -> dict:
         "rgcn_sample_index_build": (i32, [graph, vp, vp, vp, vp, sz, vp]),
         "rgcn_sample_hop": (i32, [C.POINTER(RgcnSampleIndex), vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, sz,
                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
+        "rgcn_sample_rel_index_workspace_bytes": (sz, [i64, i32]),
+        "rgcn_sample_hop_rel_workspace_bytes": (sz, [i64, vp, i32, i64, i64, i32]),
+        "rgcn_sample_rel_index_build": (i32, [graph, vp, vp, vp, vp, vp, sz, C.POINTER(C.c_int64), vp]),
+        "rgcn_sample_hop_rel": (i32, [C.POINTER(RgcnSampleRelIndex), vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, vp, sz,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
         "rgcn_mb_index_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_mb_index_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_mb_index_build": (i32, [vp, i64, vp, i64, vp, i64, i64, i64, i64, i32, i32, vp, sz, vp, sz, C.POINTER(RgcnMbIndex), vp]),
@@ -495,6 +506,64 @@ def sample_hop(ix: RgcnSampleIndex, dst_nodes: torch.Tensor, fanout: int, seed: 
         check(lib.rgcn_sample_hop(C.byref(ix), dst_nodes.data_ptr() if nd else None, nd, int(fanout), int(seed), int(hop),
                                   node_map.data_ptr(), edges[0].data_ptr(), edges[1].data_ptr(), edges[2].data_ptr(),
                                   nodes.data_ptr(), ws.data_ptr(), nbytes, C.byref(ne), C.byref(ns), _stream(ws)), "rgcn_sample_hop")
+    eb, nsrc = int(ne.value), int(ns.value)
+    if eb == cap:      # (no copy where the worst case was met)
+        return edges[:2, :eb], edges[2, :eb], nodes[:nsrc].clone()
+    return edges[:2, :eb].clone(), edges[2, :eb].clone(), nodes[:nsrc].clone()
+
+
+def sample_rel_index_build(graph: RgcnGraphStruct, device):
+    """(struct rgcn_sample_rel_index, (run_ptr uint32-as-int32 [N + 1], run_beg [num_runs + 1], run_type int32 [num_runs],
+    src int32 [E])) of rgcn_sample_rel_index_build"""
+    lib = load()
+    e, n = int(graph.num_edges), int(graph.num_nodes)
+    nbytes = lib.rgcn_sample_rel_index_workspace_bytes(e, n)
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_sample_rel_index_workspace_bytes: bad arguments")
+    nr = C.c_int64(-1)
+    with torch.cuda.device(device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        run_ptr = torch.empty(n + 1, dtype=torch.int32, device=device)
+        run_beg = torch.empty(e + 1, dtype=torch.int32, device=device)      # (sized for the worst case: every edge its own run)
+        run_type = torch.empty(max(e, 1), dtype=torch.int32, device=device)
+        src = torch.empty(max(e, 1), dtype=torch.int32, device=device)
+        check(lib.rgcn_sample_rel_index_build(C.byref(graph), run_ptr.data_ptr(), run_beg.data_ptr(), run_type.data_ptr(),
+                                              src.data_ptr(), ws.data_ptr(), nbytes, C.byref(nr), _stream(ws)),
+              "rgcn_sample_rel_index_build")
+    runs = int(nr.value)
+    if runs < e:      # (keep what was written, not the worst case)
+        run_beg, run_type = run_beg[:runs + 1].clone(), run_type[:max(runs, 1)].clone()
+    ix = RgcnSampleRelIndex(run_ptr.data_ptr(), run_beg.data_ptr(), run_type.data_ptr(), src.data_ptr(), e, runs, n,
+                            int(graph.num_relations))
+    return ix, (run_ptr, run_beg, run_type, src)
+
+
+def sample_hop_rel_cap(num_dst: int, fanouts, num_edges: int) -> int:
+    """`cap` of a per-relation hop: E if an entry is -1, else min(E, num_dst * sum of the positive entries)"""
+    if any(k < 0 for k in fanouts):
+        return num_edges
+    return min(num_edges, num_dst * sum(fanouts))
+
+
+def sample_hop_rel(ix: RgcnSampleRelIndex, dst_nodes: torch.Tensor, fanouts, seed: int, hop: int, node_map: torch.Tensor):
+    """one hop with a fan-out per relation (rgcn_sample_hop_rel); ``fanouts``: ``num_relations`` ints, validated by the caller;
+    returns what ``sample_hop`` returns"""
+    lib, dev = load(), dst_nodes.device
+    nd, e, n, r = int(dst_nodes.shape[0]), int(ix.num_edges), int(ix.num_nodes), int(ix.num_relations)
+    fan = (C.c_int32 * r)(*[int(k) for k in fanouts])
+    cap = sample_hop_rel_cap(nd, fan, e)
+    nbytes = lib.rgcn_sample_hop_rel_workspace_bytes(nd, fan, r, e, int(ix.num_runs), n)
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_sample_hop_rel_workspace_bytes: bad arguments")
+    ne, ns = C.c_int64(-1), C.c_int64(-1)
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        edges = torch.empty(3, max(cap, 1), dtype=torch.int64, device=dev)      # rows: src, dst, type
+        nodes = torch.empty(max(nd + min(cap, n), 1), dtype=torch.int64, device=dev)
+        check(lib.rgcn_sample_hop_rel(C.byref(ix), dst_nodes.data_ptr() if nd else None, nd, fan, int(seed), int(hop),
+                                      node_map.data_ptr(), edges[0].data_ptr(), edges[1].data_ptr(), edges[2].data_ptr(),
+                                      nodes.data_ptr(), ws.data_ptr(), nbytes, C.byref(ne), C.byref(ns), _stream(ws)),
+              "rgcn_sample_hop_rel")
     eb, nsrc = int(ne.value), int(ns.value)
     if eb == cap:      # (no copy where the worst case was met)
         return edges[:2, :eb], edges[2, :eb], nodes[:nsrc].clone()

@@ -24,6 +24,9 @@
 //   reset     the map entries written (destinations, new sources) go back to "none"
 //   read      error bits, E_b and the number of new sources: the one copy and the one synchronisation of a hop
 //
+// Per-relation fan-outs (rgcn_sample_rel_index_build, rgcn_sample_hop_rel): a second index, sorted by
+// (destination, relation), and a hop whose sampling unit is a (destination, relation) run -- further down, before the C ABI.
+//
 // All integer work: no float, no waiting between workgroups, every loop bounded by k, d or the grid.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,8 +48,10 @@ struct Results {        // device-resident scalars of one call: what the host re
     u32 error;          // kErr* bits
     u32 num_edges;      // E_b
     u32 num_new;        // sources that are no destination
-    u32 reserved;
+    u32 aux;            // relation index build: the number of runs; per-relation hop: the number of sampled units
 };
+
+constexpr u64 kRelMul = 0xD1B54A32D192ED03ull;      // the per-relation term of the generator's key
 
 __host__ __device__ inline u64 mix(u64 z) {      // splitmix64's finaliser
     z ^= z >> 30;
@@ -147,21 +152,12 @@ __global__ void hop_count_kernel(const int64_t* __restrict__ dst_nodes, u32 n_ds
     cnt[i] = c;
 }
 
-// One wave per destination; a wave whose destination is taken whole (or counts nothing) leaves at once: off[i + 1] - off[i] is k
-// exactly where d > k.  Slot t (0 .. k-1) of the chosen set lives in
-// register t / 64 of lane t % 64.  Floyd: for j = d-k .. d-1: t = draw(j) in [0, j]; add j if t is chosen already, else t.
+// Floyd's k-subset of the positions 0 .. d-1 (d > k >= 1) by one wave, stored ascending at out[0 .. k-1]: for j = d-k .. d-1:
+// t = draw(j) in [0, j]; add j if t is chosen already, else t.  Slot t (0 .. k-1) of the chosen set lives in register t / 64 of
+// lane t % 64 (k <= 64 * REGS, a run-time value); the membership test is one compare per register and a ballot; the rank of a
+// chosen position = chosen positions below it (k broadcasts).  Every lane of the wave must call it with the same d, k, kv.
 template <int REGS>
-__global__ void hop_floyd_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, const u32* __restrict__ ptr, u32 k,
-                                 u64 key, const u32* __restrict__ off, u32* __restrict__ sel) {
-    const u32 i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const u32 lane = threadIdx.x & 63u;
-    if (i >= n_dst) return;
-    const u32 base = off[i];
-    if (off[i + 1] - base != k) return;
-    const int64_t v = dst_nodes[i];      // (in range and listed once: it has edges)
-    const u32 d = ptr[v + 1] - ptr[v];
-    if (d <= k) return;
-    const u64 kv = mix(key + (u64)v);
+__device__ inline void floyd_wave(u32 d, u32 k, u64 kv, u32 lane, u32* __restrict__ out) {
     u32 c[REGS];
 #pragma unroll
     for (int r = 0; r < REGS; ++r) c[r] = kNone;      // (positions stay below 0xFFFF0000: no position equals an empty slot)
@@ -177,7 +173,6 @@ __global__ void hop_floyd_kernel(const int64_t* __restrict__ dst_nodes, u32 n_ds
         for (int r = 0; r < REGS; ++r)
             if ((u32)r == (t >> 6) && lane == (t & 63u)) c[r] = val;
     }
-    // rank of a chosen position = chosen positions below it: the block's edges of a destination ascend by in-edge position
     u32 rank[REGS];
 #pragma unroll
     for (int r = 0; r < REGS; ++r) rank[r] = 0u;
@@ -193,7 +188,23 @@ __global__ void hop_floyd_kernel(const int64_t* __restrict__ dst_nodes, u32 n_ds
     }
 #pragma unroll
     for (int r = 0; r < REGS; ++r)
-        if ((u32)r * 64u + lane < k) sel[base + rank[r]] = c[r];
+        if ((u32)r * 64u + lane < k) out[rank[r]] = c[r];
+}
+
+// One wave per destination; a wave whose destination is taken whole (or counts nothing) leaves at once: off[i + 1] - off[i] is k
+// exactly where d > k.  The block's edges of a destination ascend by in-edge position.
+template <int REGS>
+__global__ void hop_floyd_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, const u32* __restrict__ ptr, u32 k,
+                                 u64 key, const u32* __restrict__ off, u32* __restrict__ sel) {
+    const u32 i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const u32 lane = threadIdx.x & 63u;
+    if (i >= n_dst) return;
+    const u32 base = off[i];
+    if (off[i + 1] - base != k) return;
+    const int64_t v = dst_nodes[i];      // (in range and listed once: it has edges)
+    const u32 d = ptr[v + 1] - ptr[v];
+    if (d <= k) return;
+    floyd_wave<REGS>(d, k, mix(key + (u64)v), lane, sel + base);
 }
 
 // destination position of block edge e: the last i with off[i] <= e (off has n_dst + 1 entries, off[n_dst] = E_b > e)
@@ -317,6 +328,273 @@ static int check_hop_scalars(const rgcn_sample_index_t* ix, int64_t num_dst, int
     return RGCN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// per-relation fan-outs: the relation index and its hop
+// ------------------------------------------------------------------------------------------------
+// Relation index (once per graph, on the first per-relation hop):
+//   keys      dst * R + type per edge (u64), value = edge id; ids out of range set the error bit and the key 0
+//   sort      one stable sort over bits_for(N-1) + bits_for(R-1) bits: the edges of a (dst, type) run keep the input order
+//   heads     head flags over the sorted keys, scan: a head's run number; it writes run_beg / run_type and counts its node's runs
+//   run_ptr   exclusive scan of the runs per node (num_nodes + 1 entries)
+//   gather    src of the sorted edges as int32
+// Hop: the sampling unit is a (destination position, run) pair.
+//   mark      as the scalar hop
+//   units     runs per destination (a node listed twice: error, counts nothing) -> scan -> unit offsets, U units
+//   count     one thread per unit: min(d, k[type]); its destination and run, kept for the steps below; the units with d > k > 0
+//             go to the work list (one atomic per tile of 1,024 units) -> scan -> edge offsets, E_b
+//   floyd     waves stride over the WORK LIST only: a unit taken whole never sees a wave.  floyd_wave<REGS>, REGS from the
+//             largest positive fan-out, the unit's own k a run-time value; the key also mixes the relation
+//   expand    one thread per block edge: unit by binary search in the edge offsets
+//   frontier / relabel / reset / read: the scalar hop's kernels
+__global__ void rel_keys_kernel(const int64_t* __restrict__ src, int64_t src_stride, const int64_t* __restrict__ dst,
+                                int64_t dst_stride, const int64_t* __restrict__ typ, int64_t typ_stride, u32 num_edges, u32 n_nodes,
+                                u32 num_rel, u64* __restrict__ keys, u32* __restrict__ vals, Results* __restrict__ res) {
+    const u32 e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= num_edges) return;
+    const int64_t sv = src[(u64)e * src_stride], dv = dst[(u64)e * dst_stride], t = typ[(u64)e * typ_stride];
+    const bool bad = t < 0 || t >= (int64_t)num_rel || sv < 0 || sv >= (int64_t)n_nodes || dv < 0 || dv >= (int64_t)n_nodes;
+    if (bad) atomicOr(&res->error, kErrRange);
+    keys[e] = bad ? 0ull : (u64)dv * num_rel + (u64)t;
+    vals[e] = e;
+}
+
+// ids[i]: the run of sorted edge i (run_ids).  run_cnt has num_nodes + 1 zeroed entries; run_beg num_runs + 1 <= E + 1.
+__global__ void rel_heads_kernel(const u64* __restrict__ keys, const u32* __restrict__ flag, const u32* __restrict__ ids,
+                                 u32 num_edges, u32 num_rel, u32* __restrict__ run_cnt, u32* __restrict__ run_beg,
+                                 int32_t* __restrict__ run_type, Results* __restrict__ res) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_edges) return;
+    const u32 q = ids[i];
+    if (flag[i] != 0u) {
+        const u64 key = keys[i];
+        const u64 v = key / num_rel;      // (< n_nodes: the key kernel checked the ranges)
+        run_beg[q] = i;
+        run_type[q] = (int32_t)(key - v * num_rel);
+        atomicAdd(&run_cnt[v], 1u);
+    }
+    if (i == num_edges - 1u) {
+        run_beg[q + 1u] = num_edges;
+        res->aux = q + 1u;
+    }
+}
+
+__global__ void rel_gather_kernel(const u32* __restrict__ edge, u32 num_edges, const int64_t* __restrict__ src, int64_t src_stride,
+                                  u32 n_nodes, int32_t* __restrict__ src_sorted) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_edges) return;
+    const int64_t sv = src[(u64)edge[i] * src_stride];
+    src_sorted[i] = (sv < 0 || sv >= (int64_t)n_nodes) ? 0 : (int32_t)sv;      // (else: the error bit is set already)
+}
+
+static IndexWorkspace carve_rel_index(void* base, u64 num_edges, u64 n_nodes) {
+    IndexWorkspace w;
+    Arena ar(base);
+    const u32 nseg = sort_segments((u32)num_edges);
+    w.res = ar.take<Results>(1);
+    w.sb.k[0] = ar.take<u64>(num_edges);      // (after the sort the pair that does not hold the result holds flags and run ids)
+    w.sb.k[1] = ar.take<u64>(num_edges);
+    w.sb.v[0] = ar.take<u32>(num_edges);
+    w.sb.v[1] = ar.take<u32>(num_edges);
+    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
+    u64 scan_len = n_nodes + 1 > (u64)256 * nseg ? n_nodes + 1 : (u64)256 * nseg;
+    if (num_edges > scan_len) scan_len = num_edges;
+    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.bytes = ar.bytes();
+    return w;
+}
+
+struct RelFanouts {      // what the host learns from a fan-out vector before any launch
+    int kmax;           // the largest positive entry (0: none)
+    bool any_all;       // an entry is -1
+    u64 sum;            // sum of max(k[t], 0)
+};
+
+static int check_rel_fanouts(const int32_t* fanouts, int32_t num_rel, RelFanouts* f) {
+    f->kmax = 0;
+    f->any_all = false;
+    f->sum = 0;
+    for (int32_t t = 0; t < num_rel; ++t) {
+        const int32_t k = fanouts[t];
+        if (k < -1 || k > kMaxFanout) return RGCN_ERR_ARG;
+        if (k == -1) f->any_all = true;
+        if (k > 0) f->sum += (u64)k;
+        if (k > f->kmax) f->kmax = k;
+    }
+    return RGCN_OK;
+}
+
+static u64 rel_cap(int64_t num_dst, const RelFanouts& f, int64_t num_edges) {      // the most edges a block can hold
+    if (f.any_all) return (u64)num_edges;
+    const u64 c = (u64)num_dst * f.sum;
+    return c < (u64)num_edges ? c : (u64)num_edges;
+}
+
+static u64 rel_ucap(int64_t num_dst, int64_t num_runs, int32_t num_rel) {      // the most units a hop can hold
+    const u64 c = (u64)num_dst * (u64)num_rel;
+    return c < (u64)num_runs ? c : (u64)num_runs;
+}
+
+// ucnt has n_dst + 1 entries (the last one 0: its scan is U).  A node has at most R runs and the runs of distinct nodes are
+// distinct: U <= ucap whatever the list holds.
+__global__ void rel_units_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, u32 n_nodes, const u32* __restrict__ run_ptr,
+                                 const u32* __restrict__ map, u32* __restrict__ ucnt, Results* __restrict__ res) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_dst) return;
+    u32 c = 0u;
+    if (i < n_dst) {
+        const int64_t v = dst_nodes[i];
+        if (v >= 0 && v < (int64_t)n_nodes) {
+            if (map[v] != i) atomicOr(&res->error, kErrDuplicate);
+            else c = run_ptr[v + 1] - run_ptr[v];
+        }
+    }
+    ucnt[i] = c;
+}
+
+// ecnt has ucap + 1 entries, the ones from U on 0 (its scan's last entry is E_b).  A workgroup walks tiles of 1,024 units, four per
+// thread, and appends the tile's sampled units to the work list with ONE atomic: ballots number them inside a wave, LDS across the
+// waves.  (One atomic per wave was measured first: on 889,245 units of which 13,490 are sampled this kernel took 108 us, 90 of them
+// the 12,000 returning atomics on one word)  The order of the work list is arbitrary, what it leads to is not.
+constexpr int kCountItems = 4;
+constexpr u32 kCountTile = 256u * kCountItems;
+__global__ void rel_count_kernel(const int64_t* __restrict__ dst_nodes, u32 n_dst, const u32* __restrict__ run_ptr,
+                                 const u32* __restrict__ run_beg, const int32_t* __restrict__ run_type,
+                                 const int32_t* __restrict__ fan, const u32* __restrict__ uoff, u32 ucap, u32* __restrict__ ecnt,
+                                 u32* __restrict__ udst, u32* __restrict__ urun, u32* __restrict__ work, Results* __restrict__ res) {
+    __shared__ u32 wave_tot[4];
+    __shared__ u32 tile_base;
+    const u32 units = uoff[n_dst] < ucap ? uoff[n_dst] : ucap;
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const u64 below = (1ull << lane) - 1ull;
+    for (u64 tile = (u64)blockIdx.x * kCountTile; tile <= ucap; tile += (u64)gridDim.x * kCountTile) {      // (uniform per workgroup)
+        u32 slot[kCountItems], in_wave = 0u;
+        bool sampled[kCountItems];
+#pragma unroll
+        for (int j = 0; j < kCountItems; ++j) {
+            const u64 u = tile + (u64)j * 256u + threadIdx.x;
+            u32 c = 0u;
+            sampled[j] = false;
+            if (u < units) {
+                const u32 i = owner_of(uoff, n_dst, (u32)u);
+                const int64_t v = dst_nodes[i];      // (in range and listed once: it has runs)
+                const u32 q = run_ptr[v] + ((u32)u - uoff[i]);
+                const u32 d = run_beg[q + 1] - run_beg[q];
+                const int32_t k = fan[run_type[q]];
+                c = (k < 0 || d <= (u32)k) ? d : (u32)k;
+                sampled[j] = k > 0 && d > (u32)k;
+                udst[u] = i;
+                urun[u] = q;
+            }
+            if (u <= ucap) ecnt[u] = c;
+            const u64 m = __ballot(sampled[j]);
+            slot[j] = in_wave + (u32)__popcll(m & below);
+            in_wave += (u32)__popcll(m);
+        }
+        if (lane == 0u) wave_tot[wave] = in_wave;
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            const u32 tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+            tile_base = tot != 0u ? atomicAdd(&res->aux, tot) : 0u;
+        }
+        __syncthreads();
+        u32 base = tile_base;
+        for (u32 w = 0; w < wave; ++w) base += wave_tot[w];
+#pragma unroll
+        for (int j = 0; j < kCountItems; ++j)
+            if (sampled[j]) work[base + slot[j]] = (u32)(tile + (u64)j * 256u + threadIdx.x);
+        __syncthreads();      // (the next tile writes wave_tot and tile_base again)
+    }
+}
+
+// The waves of the grid stride over the work list: only units with d > k > 0 are on it.
+template <int REGS>
+__global__ void rel_floyd_kernel(const int64_t* __restrict__ dst_nodes, const u32* __restrict__ run_beg,
+                                 const int32_t* __restrict__ run_type, const int32_t* __restrict__ fan, u64 key,
+                                 const u32* __restrict__ udst, const u32* __restrict__ urun, const u32* __restrict__ eoff,
+                                 const u32* __restrict__ work, u32 ucap, const Results* __restrict__ res, u32* __restrict__ sel) {
+    const u32 n_work = res->aux < ucap ? res->aux : ucap;
+    const u64 waves = (u64)gridDim.x * (blockDim.x >> 6);
+    const u32 lane = threadIdx.x & 63u;
+    for (u64 w = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < n_work; w += waves) {
+        const u32 u = work[w], q = urun[u];
+        const u64 v = (u64)dst_nodes[udst[u]];
+        const u32 d = run_beg[q + 1] - run_beg[q];
+        const u32 t = (u32)run_type[q];
+        const u32 k = (u32)fan[t];
+        const u64 kv = mix(mix(key + v) + kRelMul * ((u64)t + 1ull));
+        floyd_wave<REGS>(d, k, kv, lane, sel + eoff[u]);
+    }
+}
+
+// sel[e]: in: the position in its run of a sampled unit's edge (rel_floyd_kernel); out: the edge's GLOBAL source
+__global__ void rel_expand_kernel(const u32* __restrict__ uoff, u32 n_dst, u32 ucap, const u32* __restrict__ run_beg,
+                                  const int32_t* __restrict__ run_type, const int32_t* __restrict__ src_sorted,
+                                  const u32* __restrict__ eoff, const u32* __restrict__ udst, const u32* __restrict__ urun,
+                                  const u32* __restrict__ map, u32* __restrict__ sel, u32* __restrict__ bits,
+                                  int64_t* __restrict__ edge_dst, int64_t* __restrict__ edge_type, Results* __restrict__ res) {
+    const u32 units = uoff[n_dst] < ucap ? uoff[n_dst] : ucap;
+    const u32 total = eoff[ucap];
+    const u64 stride = (u64)gridDim.x * blockDim.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) res->num_edges = total;
+    for (u64 e64 = (u64)blockIdx.x * blockDim.x + threadIdx.x; e64 < total; e64 += stride) {
+        const u32 e = (u32)e64;
+        const u32 u = owner_of(eoff, units, e);      // (eoff[units] = E_b > e)
+        const u32 first = eoff[u], count = eoff[u + 1] - first;
+        const u32 q = urun[u];
+        const u32 begin = run_beg[q], d = run_beg[q + 1] - begin;
+        const u32 p = count == d ? e - first : sel[e];
+        const u32 s = (u32)src_sorted[(u64)begin + p];
+        edge_dst[e] = (int64_t)udst[u];
+        edge_type[e] = (int64_t)run_type[q];
+        sel[e] = s;
+        if (map[s] == kNone) atomicOr(&bits[s >> 5], 1u << (s & 31u));
+    }
+}
+
+constexpr u32 kFloydGridMax = 4096;      // workgroups (of four waves) that stride over the work list
+
+struct HopRelWorkspace {
+    Results* res;
+    int32_t* fan;   // R: the fan-out vector
+    u32* ucnt;      // n_dst + 1: runs per destination, scanned in place into unit offsets
+    u32* ecnt;      // ucap + 1: edges per unit, scanned in place into edge offsets
+    u32* udst;      // ucap: destination position of a unit
+    u32* urun;      // ucap: run of a unit
+    u32* work;      // ucap: the sampled units
+    u32* sel;       // cap
+    u32* bits;      // n_words
+    u32* wcnt;      // n_words + 1
+    u32* sums;
+    size_t bytes;
+};
+
+static HopRelWorkspace carve_hop_rel(void* base, u64 n_dst, u64 ucap, u64 cap, u64 n_nodes, u64 num_rel) {
+    HopRelWorkspace w;
+    Arena ar(base);
+    const u64 n_words = (n_nodes + 31) / 32;
+    w.res = ar.take<Results>(1);
+    w.fan = ar.take<int32_t>(num_rel);
+    w.ucnt = ar.take<u32>(n_dst + 1);
+    w.ecnt = ar.take<u32>(ucap + 1);
+    w.udst = ar.take<u32>(ucap);
+    w.urun = ar.take<u32>(ucap);
+    w.work = ar.take<u32>(ucap);
+    w.sel = ar.take<u32>(cap);
+    w.bits = ar.take<u32>(n_words);
+    w.wcnt = ar.take<u32>(n_words + 1);
+    u64 scan_len = n_dst + 1 > n_words + 1 ? n_dst + 1 : n_words + 1;
+    if (ucap + 1 > scan_len) scan_len = ucap + 1;
+    w.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.bytes = ar.bytes();
+    return w;
+}
+
+static int check_rel_sizes(int64_t num_edges, int64_t num_runs, int32_t num_nodes, int32_t num_rel) {
+    if (num_nodes <= 0 || num_edges < 0 || (u64)num_edges > kMaxKeys || num_runs < 0 || num_runs > num_edges) return RGCN_ERR_PLAN;
+    if (num_rel <= 0 || num_rel > kMaxRelations) return RGCN_ERR_PLAN;
+    return RGCN_OK;
+}
+
 }  // namespace rgcn_sample
 
 using namespace rgcn_sample;
@@ -420,6 +698,142 @@ extern "C" int rgcn_sample_hop(const rgcn_sample_index_t* ix, const int64_t* dst
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     Results r;
     if ((st = read_back(ws.res, &r, s)) != 0) return st;
+    if (r.error & kErrRange) return RGCN_ERR_GRAPH;
+    if (r.error & kErrDuplicate) return RGCN_ERR_ARG;
+    *num_edges_out = (int64_t)r.num_edges;
+    *num_src_out = (int64_t)nd + (int64_t)r.num_new;
+    return RGCN_OK;
+}
+
+// ---- per-relation fan-outs: the relation index and its hop ----------------------------------------------------
+extern "C" size_t rgcn_sample_rel_index_workspace_bytes(int64_t num_edges, int32_t num_nodes) {
+    if (num_edges < 0 || num_nodes <= 0 || (u64)num_edges > kMaxKeys) return 0;
+    return carve_rel_index(nullptr, (u64)num_edges, (u64)num_nodes).bytes;
+}
+
+extern "C" int rgcn_sample_rel_index_build(const rgcn_graph_t* g, uint32_t* run_ptr_out, uint32_t* run_beg_out, int32_t* run_type_out,
+                                           int32_t* src_out, void* workspace, size_t workspace_bytes, int64_t* num_runs_out,
+                                           void* stream) {
+    if (g == nullptr) return RGCN_ERR_NULL;
+    if (g->num_edges < 0 || g->num_nodes <= 0 || g->num_relations <= 0 || g->num_relations > kMaxRelations) return RGCN_ERR_PLAN;
+    if ((u64)g->num_edges > kMaxKeys) return RGCN_ERR_PLAN;
+    if (g->num_edges > 0 && (!g->src || !g->dst || !g->type || !run_type_out || !src_out)) return RGCN_ERR_NULL;
+    if (!run_ptr_out || !run_beg_out || !workspace || !num_runs_out) return RGCN_ERR_NULL;
+    const u32 E = (u32)g->num_edges, N = (u32)g->num_nodes, R = (u32)g->num_relations;
+    IndexWorkspace ws = carve_rel_index(workspace, E, N);
+    if (workspace_bytes < ws.bytes) return RGCN_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.res, 0, sizeof(Results), s);
+    if (e == hipSuccess) e = hipMemsetAsync(run_ptr_out, 0, ((size_t)N + 1) * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(run_beg_out, 0, 4, s);      // (a graph without edges: run_beg = [0])
+    if (e != hipSuccess) return (int)e;
+    if (E > 0) {
+        hipLaunchKernelGGL(rel_keys_kernel, dim3(grid_for(E)), dim3(256), 0, s, g->src, g->src_stride, g->dst, g->dst_stride, g->type,
+                           g->type_stride, E, N, R, ws.sb.k[0], ws.sb.v[0], ws.res);
+        const int c = radix_sort_pairs(ws.sb, E, bits_for((u64)N - 1) + bits_for((u64)R - 1), s);
+        u32* flag = (u32*)ws.sb.k[c ^ 1];      // the pair the sort left free: 8 B per edge
+        u32* ids = flag + E;
+        run_ids(ws.sb.k[c], E, 0, flag, ids, ws.sb.sums, s);
+        hipLaunchKernelGGL(rel_heads_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.sb.k[c], flag, ids, E, R, run_ptr_out, run_beg_out,
+                           run_type_out, ws.res);
+        hipLaunchKernelGGL(rel_gather_kernel, dim3(grid_for(E)), dim3(256), 0, s, ws.sb.v[c], E, g->src, g->src_stride, N, src_out);
+    }
+    exclusive_scan(run_ptr_out, run_ptr_out, N + 1u, ws.sb.sums, s);      // runs per node -> run_ptr, run_ptr[N] = num_runs
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    Results r;
+    int st = read_back(ws.res, &r, s);
+    if (st != 0) return st;
+    if (r.error) return RGCN_ERR_GRAPH;
+    *num_runs_out = (int64_t)r.aux;
+    return RGCN_OK;
+}
+
+extern "C" size_t rgcn_sample_hop_rel_workspace_bytes(int64_t num_dst, const int32_t* fanouts, int32_t num_relations,
+                                                      int64_t num_edges, int64_t num_runs, int32_t num_nodes) {
+    if (check_rel_sizes(num_edges, num_runs, num_nodes, num_relations) != RGCN_OK || !fanouts) return 0;
+    if (num_dst < 0 || num_dst > (int64_t)num_nodes) return 0;
+    RelFanouts f;
+    if (check_rel_fanouts(fanouts, num_relations, &f) != RGCN_OK) return 0;
+    return carve_hop_rel(nullptr, (u64)num_dst, rel_ucap(num_dst, num_runs, num_relations), rel_cap(num_dst, f, num_edges),
+                         (u64)num_nodes, (u64)num_relations).bytes;
+}
+
+extern "C" int rgcn_sample_hop_rel(const rgcn_sample_rel_index_t* ix, const int64_t* dst_nodes, int64_t num_dst,
+                                   const int32_t* fanouts, int64_t seed, int hop, uint32_t* node_map, int64_t* edge_src_out,
+                                   int64_t* edge_dst_out, int64_t* edge_type_out, int64_t* src_nodes_out, void* workspace,
+                                   size_t workspace_bytes, int64_t* num_edges_out, int64_t* num_src_out, void* stream) {
+    if (ix == nullptr || fanouts == nullptr) return RGCN_ERR_NULL;
+    int st = check_rel_sizes(ix->num_edges, ix->num_runs, ix->num_nodes, ix->num_relations);
+    if (st != RGCN_OK) return st;
+    RelFanouts f;
+    if ((st = check_rel_fanouts(fanouts, ix->num_relations, &f)) != RGCN_OK) return st;
+    if (seed < 0 || hop < 0 || num_dst < 0 || num_dst > (int64_t)ix->num_nodes) return RGCN_ERR_ARG;
+    if (!ix->run_ptr || !ix->run_beg || !node_map || !workspace || !num_edges_out || !num_src_out) return RGCN_ERR_NULL;
+    if (ix->num_edges > 0 && (!ix->run_type || !ix->src)) return RGCN_ERR_NULL;
+    const u64 cap = rel_cap(num_dst, f, ix->num_edges);
+    const u64 ucap64 = rel_ucap(num_dst, ix->num_runs, ix->num_relations);
+    if (num_dst > 0 && (!dst_nodes || !src_nodes_out)) return RGCN_ERR_NULL;
+    if (cap > 0 && (!edge_src_out || !edge_dst_out || !edge_type_out)) return RGCN_ERR_NULL;
+    const u32 N = (u32)ix->num_nodes, nd = (u32)num_dst, n_words = (N + 31u) / 32u, ucap = (u32)ucap64;
+    HopRelWorkspace ws = carve_hop_rel(workspace, nd, ucap, cap, N, (u64)ix->num_relations);
+    if (workspace_bytes < ws.bytes) return RGCN_ERR_WORKSPACE;
+    if (nd == 0) {
+        *num_edges_out = 0;
+        *num_src_out = 0;
+        return RGCN_OK;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(ws.res, 0, sizeof(Results), s);
+    if (e == hipSuccess) e = hipMemsetAsync(ws.bits, 0, (size_t)n_words * 4, s);
+    if (e != hipSuccess) return (int)e;
+    // the fan-outs: one copy; every return below waits for the stream, so the caller's array outlives it
+    e = hipMemcpyAsync(ws.fan, fanouts, (size_t)ix->num_relations * 4, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return (int)e;
+    }
+    const u64 key = mix((u64)seed + 0x9E3779B97F4A7C15ull * ((u64)hop + 1ull));
+
+    hipLaunchKernelGGL(hop_mark_kernel, dim3(grid_for(nd)), dim3(256), 0, s, dst_nodes, nd, N, node_map, src_nodes_out, ws.res);
+    hipLaunchKernelGGL(rel_units_kernel, dim3(grid_for((u64)nd + 1)), dim3(256), 0, s, dst_nodes, nd, N, ix->run_ptr, node_map, ws.ucnt,
+                       ws.res);
+    if (cap > 0 && ucap > 0) {      // (an index with edges has runs; every grid below has at least one workgroup)
+        exclusive_scan(ws.ucnt, ws.ucnt, nd + 1u, ws.sums, s);
+        u32 ug = grid_for((u64)ucap + 1, (int)kCountTile);      // one workgroup per tile of 1,024 units
+        if (ug > kEdgeGridMax) ug = kEdgeGridMax;
+        hipLaunchKernelGGL(rel_count_kernel, dim3(ug), dim3(256), 0, s, dst_nodes, nd, ix->run_ptr, ix->run_beg, ix->run_type, ws.fan,
+                           ws.ucnt, ucap, ws.ecnt, ws.udst, ws.urun, ws.work, ws.res);
+        exclusive_scan(ws.ecnt, ws.ecnt, ucap + 1u, ws.sums, s);
+        if (f.kmax > 0) {
+            u32 fg = grid_for((u64)ucap, 4);      // four waves per workgroup, one unit of the work list per wave and trip
+            if (fg > kFloydGridMax) fg = kFloydGridMax;
+            const dim3 grid(fg), block(256);
+#define RGCN_REL_FLOYD(REGS)                                                                                                      \
+    hipLaunchKernelGGL(rel_floyd_kernel<REGS>, grid, block, 0, s, dst_nodes, ix->run_beg, ix->run_type, ws.fan, key, ws.udst, ws.urun, \
+                       ws.ecnt, ws.work, ucap, ws.res, ws.sel)
+            if (f.kmax <= 64) RGCN_REL_FLOYD(1);
+            else if (f.kmax <= 128) RGCN_REL_FLOYD(2);
+            else if (f.kmax <= 192) RGCN_REL_FLOYD(3);
+            else RGCN_REL_FLOYD(4);
+#undef RGCN_REL_FLOYD
+        }
+        u32 eg = grid_for(cap);
+        if (eg > kEdgeGridMax) eg = kEdgeGridMax;
+        hipLaunchKernelGGL(rel_expand_kernel, dim3(eg), dim3(256), 0, s, ws.ucnt, nd, ucap, ix->run_beg, ix->run_type, ix->src, ws.ecnt,
+                           ws.udst, ws.urun, node_map, ws.sel, ws.bits, edge_dst_out, edge_type_out, ws.res);
+        hipLaunchKernelGGL(hop_popcount_kernel, dim3(grid_for((u64)n_words + 1)), dim3(256), 0, s, ws.bits, n_words, ws.wcnt);
+        exclusive_scan(ws.wcnt, ws.wcnt, n_words + 1u, ws.sums, s);
+        hipLaunchKernelGGL(hop_frontier_kernel, dim3(grid_for(n_words)), dim3(256), 0, s, ws.bits, n_words, ws.wcnt, nd, node_map,
+                           src_nodes_out, ws.res);
+        hipLaunchKernelGGL(hop_relabel_kernel, dim3(eg), dim3(256), 0, s, ws.ecnt, ucap, ws.sel, node_map, edge_src_out);
+        hipLaunchKernelGGL(hop_reset_new_kernel, dim3(grid_for(n_words)), dim3(256), 0, s, ws.bits, n_words, node_map);
+    }
+    hipLaunchKernelGGL(hop_reset_dst_kernel, dim3(grid_for(nd)), dim3(256), 0, s, dst_nodes, nd, N, node_map);
+    e = hipGetLastError();
+    Results r;
+    st = read_back(ws.res, &r, s);
+    if (e != hipSuccess) return (int)e;
+    if (st != 0) return st;
     if (r.error & kErrRange) return RGCN_ERR_GRAPH;
     if (r.error & kErrDuplicate) return RGCN_ERR_ARG;
     *num_edges_out = (int64_t)r.num_edges;

@@ -6,13 +6,16 @@ seed)`` returns one ``Block`` per model layer, sampled from the last layer back:
 ``blocks[i]`` the source nodes of ``blocks[i + 1]``.  A block's ``src_nodes`` start with its destinations, so a layer runs as
 ``conv((x, x[:block.n_dst]), block.edge_index, block.edge_type)`` with ``x`` the rows ``src_nodes`` of its input.
 
-The choice of a destination's in-edges is a pure function of ``(seed, layer, global node id)`` (a counter-based generator and
-Floyd's k-subset algorithm): it depends neither on the other nodes of the batch nor on launch geometry, and two calls return equal
-tensors.  There is no CPU path: every argument is checked on the host, then the HIP library does the work.
+A layer's fan-out is one int for all in-edges of a destination, or one int PER RELATION (a list / tuple: RGCNConv normalises per
+(destination, relation), so a pooled draw starves the rare relations of a hub).
+
+The choice of a destination's in-edges is a pure function of ``(seed, layer, global node id)`` -- and of the relation, with
+per-relation fan-outs -- (a counter-based generator and Floyd's k-subset algorithm): it depends neither on the other nodes of the
+batch nor on launch geometry, and two calls return equal tensors.  There is no CPU path: every argument is checked on the host, then the HIP library does the work.
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -87,14 +90,29 @@ def block_index(block: Block, num_relations: int, aggr: str = "mean") -> BlockIn
     return BlockIndex(ix, aggr)
 
 
-def check_fanouts(fanouts) -> List[int]:
-    """a non-empty sequence of ints in {-1} u [1, 256]"""
+def check_fanouts(fanouts, num_relations: Optional[int] = None) -> list:
+    """a non-empty sequence with one entry per layer: an int in {-1} u [1, 256] (one fan-out for all in-edges of a destination), or
+    a list / tuple of ints in {-1, 0} u [1, 256], one per relation (its length is checked against
+    ``num_relations`` where that is given).  Returns a list whose sequence entries are lists."""
     if isinstance(fanouts, (str, bytes)) or not isinstance(fanouts, Sequence) or len(fanouts) == 0:
-        raise ValueError(f"fanouts must be a non-empty sequence of ints, one per layer (got {fanouts!r})")
+        raise ValueError(f"fanouts must be a non-empty sequence, one entry per layer (got {fanouts!r})")
+    out = []
     for k in fanouts:
+        if isinstance(k, (list, tuple)):
+            if len(k) == 0 or (num_relations is not None and len(k) != num_relations):
+                raise ValueError(f"a per-relation fan-out takes one int per relation"
+                                 + (f" ({num_relations})" if num_relations is not None else "") + f", got {len(k)} entries")
+            for kt in k:
+                if isinstance(kt, bool) or not isinstance(kt, int) or not (-1 <= kt <= MAX_FANOUT):
+                    raise ValueError(f"a per-relation fan-out entry must be -1 (the whole run), 0 (nothing of that relation) or "
+                                     f"an int in 1 .. {MAX_FANOUT} (got {kt!r})")
+            out.append(list(k))
+            continue
         if isinstance(k, bool) or not isinstance(k, int) or not (k == -1 or 1 <= k <= MAX_FANOUT):
-            raise ValueError(f"a fan-out must be -1 (all in-edges) or an int in 1 .. {MAX_FANOUT} (got {k!r})")
-    return list(fanouts)
+            raise ValueError(f"a fan-out must be -1 (all in-edges), an int in 1 .. {MAX_FANOUT}, or a list / tuple with one "
+                             f"such int (or 0) per relation (got {k!r})")
+        out.append(k)
+    return out
 
 
 def check_seeds(seeds, num_nodes: int) -> None:
@@ -130,19 +148,36 @@ class NeighborSampler:
         graph, keep = _lib.graph_struct(edge_index, edge_type, num_nodes, num_relations)
         self._index, self._arrays = _lib.sample_index_build(graph, self.device)
         del keep
+        # the relation index is built from the caller's edges on the first per-relation hop: until then the sampler
+        # holds references to them and nothing more
+        self._edges = (edge_index, edge_type)
+        self._rel_index = self._rel_arrays = None
         # node id -> position in the block being built; all "none" (-1) between hops, which reset only what they wrote
         self._map = torch.full((num_nodes,), -1, dtype=torch.int32, device=self.device)
 
-    def sample(self, seeds: Tensor, fanouts: Sequence[int], seed: int = 0) -> List[Block]:
-        """``blocks[0 .. L-1]``, ``fanouts[i]`` belonging to model layer ``i``.  One host synchronisation per layer."""
+    def _relation_index(self):
+        if self._rel_index is None:
+            from . import _lib
+            graph, keep = _lib.graph_struct(self._edges[0], self._edges[1], self.num_nodes, self.num_relations)
+            self._rel_index, self._rel_arrays = _lib.sample_rel_index_build(graph, self.device)
+            del keep
+        return self._rel_index
+
+    def sample(self, seeds: Tensor, fanouts: Sequence, seed: int = 0) -> List[Block]:
+        """``blocks[0 .. L-1]``, ``fanouts[i]`` belonging to model layer ``i``: an int (at most that many in-edges per destination,
+        all relations pooled) or a list / tuple of ``num_relations`` ints (at most ``fanouts[i][t]`` in-edges per destination AND
+        relation ``t``; -1 all, 0 none).  The two may be mixed across layers.  One host synchronisation per layer."""
         from . import _lib
-        fanouts = check_fanouts(fanouts)
+        fanouts = check_fanouts(fanouts, getattr(self, "num_relations", None))
         seed = check_sample_seed(seed)
         check_seeds(seeds, self.num_nodes)
         dst = seeds.to(self.device).contiguous()
         blocks = []
         for i in reversed(range(len(fanouts))):
-            ei, et, src_nodes = _lib.sample_hop(self._index, dst, fanouts[i], seed, i, self._map)
+            if isinstance(fanouts[i], list):
+                ei, et, src_nodes = _lib.sample_hop_rel(self._relation_index(), dst, fanouts[i], seed, i, self._map)
+            else:
+                ei, et, src_nodes = _lib.sample_hop(self._index, dst, fanouts[i], seed, i, self._map)
             blocks.append(Block(ei, et, int(src_nodes.shape[0]), int(dst.shape[0]), src_nodes))
             dst = src_nodes
         return blocks[::-1]

@@ -232,7 +232,8 @@ class Trainer:
         """``train`` with neighbour sampling: per epoch the full-batch validation forward exactly as ``train`` does it (when
         ``not sum_graph``), then a seeded permutation of ``x_train`` cut into batches of ``batch_size`` (the last may be short)
         and ONE optimizer step per batch on the blocks ``NeighborSampler.sample(batch, fanouts, step seed)`` returns, through
-        ``model.forward_blocks``.  The step seed is a fixed odd-multiplier combination of ``seed``, the epoch and the batch index
+        ``model.forward_blocks``.  An entry of ``fanouts`` is an int or a list / tuple of ``model.rgcn1.num_relations`` ints, one fan-out
+        per relation.  The step seed is a fixed odd-multiplier combination of ``seed``, the epoch and the batch index
         (mod 2^63; the sampler mixes it): runs repeat, steps differ.  The epoch's
         loss is the mean over its batches.  Eager only -- block shapes change every step, nothing is captured.  Returns the four
         lists of ``train``; ``self.last_batches`` holds the last epoch's batches (tensors of node ids).  ``block_kernels`` goes to
@@ -255,6 +256,10 @@ class Trainer:
         fanouts = check_fanouts(fanouts)
         if len(fanouts) != 2:
             raise ValueError(f"the models have two RGCN layers: fanouts takes 2 entries, got {len(fanouts)}")
+        if any(isinstance(k, list) for k in fanouts):      # one fan-out per relation: the model knows how many
+            if model is None:
+                raise ValueError("per-relation fan-outs need the model: their length is the number of relations of its layers")
+            fanouts = check_fanouts(fanouts, int(model.rgcn1.num_relations))
         seed = check_sample_seed(seed)
         model = model.to(self.device)
         training_data = self._device_data(graph)
