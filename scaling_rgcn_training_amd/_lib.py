@@ -489,27 +489,31 @@ def sample_hop_cap(num_dst: int, fanout: int, num_edges: int) -> int:
     return num_edges if fanout < 0 else min(num_edges, num_dst * fanout)
 
 
-def sample_hop(ix: RgcnSampleIndex, dst_nodes: torch.Tensor, fanout: int, seed: int, hop: int, node_map: torch.Tensor):
-    """one hop (rgcn_sample_hop) -> (edge_index [2, E_b], edge_type [E_b], src_nodes [n_src]), int64 on the device of
-    ``dst_nodes`` (contiguous int64); ``node_map``: the sampler's persistent int32 [N] map, all -1 between calls"""
-    lib, dev = load(), dst_nodes.device
-    nd, e, n = int(dst_nodes.shape[0]), int(ix.num_edges), int(ix.num_nodes)
-    cap = sample_hop_cap(nd, int(fanout), e)
-    nbytes = lib.rgcn_sample_hop_workspace_bytes(nd, int(fanout), e, n)
+def _sample_hop(name: str, ix, dst_nodes: torch.Tensor, cap: int, nbytes: int, node_map: torch.Tensor, call):
+    """what both hops do around their C call; ``call(dst, nd, map, e_src, e_dst, e_type, nodes, ws, nbytes, ne, ns, stream)``"""
+    dev, nd, n = dst_nodes.device, int(dst_nodes.shape[0]), int(ix.num_nodes)
     if nbytes == 0:
-        raise RgcnLibraryError("rgcn_sample_hop_workspace_bytes: bad arguments")
+        raise RgcnLibraryError(f"{name}_workspace_bytes: bad arguments")
     ne, ns = C.c_int64(-1), C.c_int64(-1)
     with torch.cuda.device(dev):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         edges = torch.empty(3, max(cap, 1), dtype=torch.int64, device=dev)      # rows: src, dst, type
         nodes = torch.empty(max(nd + min(cap, n), 1), dtype=torch.int64, device=dev)
-        check(lib.rgcn_sample_hop(C.byref(ix), dst_nodes.data_ptr() if nd else None, nd, int(fanout), int(seed), int(hop),
-                                  node_map.data_ptr(), edges[0].data_ptr(), edges[1].data_ptr(), edges[2].data_ptr(),
-                                  nodes.data_ptr(), ws.data_ptr(), nbytes, C.byref(ne), C.byref(ns), _stream(ws)), "rgcn_sample_hop")
+        check(call(dst_nodes.data_ptr() if nd else None, nd, node_map.data_ptr(), edges[0].data_ptr(), edges[1].data_ptr(),
+                   edges[2].data_ptr(), nodes.data_ptr(), ws.data_ptr(), nbytes, C.byref(ne), C.byref(ns), _stream(ws)), name)
     eb, nsrc = int(ne.value), int(ns.value)
     if eb == cap:      # (no copy where the worst case was met)
         return edges[:2, :eb], edges[2, :eb], nodes[:nsrc].clone()
     return edges[:2, :eb].clone(), edges[2, :eb].clone(), nodes[:nsrc].clone()
+
+
+def sample_hop(ix: RgcnSampleIndex, dst_nodes: torch.Tensor, fanout: int, seed: int, hop: int, node_map: torch.Tensor):
+    """one hop (rgcn_sample_hop) -> (edge_index [2, E_b], edge_type [E_b], src_nodes [n_src]), int64 on the device of
+    ``dst_nodes`` (contiguous int64); ``node_map``: the sampler's persistent int32 [N] map, all -1 between calls"""
+    lib, nd, e, k = load(), int(dst_nodes.shape[0]), int(ix.num_edges), int(fanout)
+    nbytes = lib.rgcn_sample_hop_workspace_bytes(nd, k, e, int(ix.num_nodes))
+    return _sample_hop("rgcn_sample_hop", ix, dst_nodes, sample_hop_cap(nd, k, e), nbytes, node_map,
+                       lambda dst, n_dst, *rest: lib.rgcn_sample_hop(C.byref(ix), dst, n_dst, k, int(seed), int(hop), *rest))
 
 
 def sample_rel_index_build(graph: RgcnGraphStruct, device):
@@ -548,26 +552,11 @@ def sample_hop_rel_cap(num_dst: int, fanouts, num_edges: int) -> int:
 def sample_hop_rel(ix: RgcnSampleRelIndex, dst_nodes: torch.Tensor, fanouts, seed: int, hop: int, node_map: torch.Tensor):
     """one hop with a fan-out per relation (rgcn_sample_hop_rel); ``fanouts``: ``num_relations`` ints, validated by the caller;
     returns what ``sample_hop`` returns"""
-    lib, dev = load(), dst_nodes.device
-    nd, e, n, r = int(dst_nodes.shape[0]), int(ix.num_edges), int(ix.num_nodes), int(ix.num_relations)
+    lib, nd, e, r = load(), int(dst_nodes.shape[0]), int(ix.num_edges), int(ix.num_relations)
     fan = (C.c_int32 * r)(*[int(k) for k in fanouts])
-    cap = sample_hop_rel_cap(nd, fan, e)
-    nbytes = lib.rgcn_sample_hop_rel_workspace_bytes(nd, fan, r, e, int(ix.num_runs), n)
-    if nbytes == 0:
-        raise RgcnLibraryError("rgcn_sample_hop_rel_workspace_bytes: bad arguments")
-    ne, ns = C.c_int64(-1), C.c_int64(-1)
-    with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        edges = torch.empty(3, max(cap, 1), dtype=torch.int64, device=dev)      # rows: src, dst, type
-        nodes = torch.empty(max(nd + min(cap, n), 1), dtype=torch.int64, device=dev)
-        check(lib.rgcn_sample_hop_rel(C.byref(ix), dst_nodes.data_ptr() if nd else None, nd, fan, int(seed), int(hop),
-                                      node_map.data_ptr(), edges[0].data_ptr(), edges[1].data_ptr(), edges[2].data_ptr(),
-                                      nodes.data_ptr(), ws.data_ptr(), nbytes, C.byref(ne), C.byref(ns), _stream(ws)),
-              "rgcn_sample_hop_rel")
-    eb, nsrc = int(ne.value), int(ns.value)
-    if eb == cap:      # (no copy where the worst case was met)
-        return edges[:2, :eb], edges[2, :eb], nodes[:nsrc].clone()
-    return edges[:2, :eb].clone(), edges[2, :eb].clone(), nodes[:nsrc].clone()
+    nbytes = lib.rgcn_sample_hop_rel_workspace_bytes(nd, fan, r, e, int(ix.num_runs), int(ix.num_nodes))
+    return _sample_hop("rgcn_sample_hop_rel", ix, dst_nodes, sample_hop_rel_cap(nd, fan, e), nbytes, node_map,
+                       lambda dst, n_dst, *rest: lib.rgcn_sample_hop_rel(C.byref(ix), dst, n_dst, fan, int(seed), int(hop), *rest))
 
 
 # ---- mini-batch layers straight from a sampled block (rgcn_minibatch.hip; sampling.block_index / conv._BlockFn drive them) ------

@@ -30,8 +30,6 @@ namespace rgcn_emb {
 using namespace rgcn_sort_scan;
 using rgcn::f32x4;
 
-constexpr u64 kMaxKeys = 0xFFFF0000ull;      // the sort counts keys in u32, rounded up to whole 2,048-key segments
-
 struct RowArgs {
     float* table;
     float* exp_avg;
@@ -143,20 +141,6 @@ __global__ void __launch_bounds__(256) emb_adam_rows_kernel(const RowArgs a) {
     }
 }
 
-static SortBufs carve_sort(void* base, u64 n, size_t* bytes) {
-    SortBufs sb;
-    Arena ar(base);
-    const u32 nseg = sort_segments((u32)n);
-    sb.k[0] = ar.take<u64>(n);
-    sb.k[1] = ar.take<u64>(n);
-    sb.v[0] = ar.take<u32>(n);
-    sb.v[1] = ar.take<u32>(n);
-    sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
-    sb.sums = ar.take<u32>((size_t)scan_blocks(256u * nseg) + 2);
-    *bytes = ar.bytes();
-    return sb;
-}
-
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace rgcn_emb
@@ -165,9 +149,9 @@ using namespace rgcn_emb;
 
 extern "C" size_t rgcn_emb_adam_rows_workspace_bytes(int64_t n_rows, int32_t num_nodes) {
     if (n_rows <= 0 || num_nodes < 0 || (u64)n_rows > kMaxKeys) return 0;
-    size_t bytes;
-    carve_sort(nullptr, (u64)n_rows, &bytes);
-    return bytes;
+    Arena ar(nullptr);
+    take_sort_bufs(ar, (u64)n_rows);
+    return ar.bytes();
 }
 
 extern "C" int rgcn_emb_adam_rows(float* table, float* exp_avg, float* exp_avg_sq, int32_t* row_step, int planes, int64_t plane_stride,
@@ -185,9 +169,9 @@ extern "C" int rgcn_emb_adam_rows(float* table, float* exp_avg, float* exp_avg_s
     if (n_rows == 0) return RGCN_OK;
     SortBufs sb{};
     if (!assume_unique) {
-        size_t need;
-        sb = carve_sort(workspace, (u64)n_rows, &need);
-        if (workspace_bytes < need) return RGCN_ERR_WORKSPACE;
+        Arena ar(workspace);
+        sb = take_sort_bufs(ar, (u64)n_rows);
+        if (workspace_bytes < ar.bytes()) return RGCN_ERR_WORKSPACE;
         if (!workspace) return RGCN_ERR_NULL;
     }
     int st = rgcn::check_device();

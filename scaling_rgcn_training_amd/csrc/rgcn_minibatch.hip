@@ -38,7 +38,6 @@ using namespace rgcn_sort_scan;
 using rgcn::f32x4;
 
 constexpr u32 kErrRange = 1u, kErrInternal = 2u;
-constexpr u64 kMaxKeys = 0xFFFF0000ull;      // the sort counts keys in u32, rounded up to whole 2,048-key segments
 constexpr int64_t kMaxRelations = 65536;
 constexpr u32 kRowEdges = 256;               // most positions of one row
 constexpr int kMaxSlabs = 64;
@@ -271,18 +270,11 @@ static BuildWorkspace carve_build(void* base, const Sizes& sz, u64 n_src, u64 n_
     BuildWorkspace w;
     Arena ar(base);
     const u64 m = sz.total;
-    const u32 nseg = sort_segments((u32)m);
     w.res = ar.take<Results>(1);
-    w.sb.k[0] = ar.take<u64>(m);
-    w.sb.k[1] = ar.take<u64>(m);
-    w.sb.v[0] = ar.take<u32>(m);
-    w.sb.v[1] = ar.take<u32>(m);
-    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
-    u64 scan_len = (u64)256 * nseg;
-    if (m > scan_len) scan_len = m;
+    u64 scan_len = m;
     if (n_src + 1 > scan_len) scan_len = n_src + 1;
     if (n_dst + 1 > scan_len) scan_len = n_dst + 1;
-    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.sb = take_sort_bufs(ar, m, scan_len);
     w.flag = ar.take<u32>(m);
     w.run_id = ar.take<u32>(m);
     w.run_start = ar.take<u32>(m + 1);

@@ -787,15 +787,8 @@ struct Workspace {
 static Workspace carve(void* base, u64 nmax, u64 gmax) {
     Workspace w;
     Arena ar(base);
-    const u32 nseg = sort_segments((u32)nmax);
     w.ctr = ar.take<Counters>(1);
-    w.sb.k[0] = ar.take<u64>(nmax);
-    w.sb.k[1] = ar.take<u64>(nmax);
-    w.sb.v[0] = ar.take<u32>(nmax);
-    w.sb.v[1] = ar.take<u32>(nmax);
-    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
-    const u64 scan_len = nmax + 1 > (u64)256 * nseg ? nmax + 1 : (u64)256 * nseg;
-    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.sb = take_sort_bufs(ar, nmax, nmax + 1);
     w.scan_a = ar.take<u32>(nmax + 1);
     w.scan_b = ar.take<u32>(nmax + 1);
     w.gstart = ar.take<u32>(gmax + 1);

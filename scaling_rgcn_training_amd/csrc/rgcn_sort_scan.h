@@ -1,7 +1,7 @@
 // rgcn_sort_scan.h -- the integer building blocks the device-side builders share (rgcn_plan.hip: graph plans; rgcn_summary.hip:
 // node partitions and quotient graphs; rgcn_sample.hip: in-edge index and fan-out hops; rgcn_minibatch.hip: block indices): a stable
 // LSD radix sort of (u64 key, u32 value) pairs, an exclusive scan of u32, head flags / run ids over sorted keys, and the host
-// plumbing of a builder: carving a workspace (Arena), the other pair of the sort buffers (from_pair), the one read-back of a
+// plumbing of a builder: carving a workspace (Arena, take_sort_bufs), the other pair of the sort buffers (from_pair), the one read-back of a
 // build's scalars (read_back).  gfx950 only.  Everything has internal linkage: every including source gets its own copy of the kernels.
 //
 //   sort      LSD radix sort, 8-bit digits, stable: per wave-segment digit histograms -> one exclusive scan -> scatter
@@ -267,6 +267,22 @@ struct Arena {
     }
     size_t bytes() const { return off; }
 };
+
+constexpr u64 kMaxKeys = 0xFFFF0000ull;      // the sort counts keys in u32, rounded up to whole 2,048-key segments
+
+// The buffers of a sort of n keys, in this order; sums also serves the caller's own scans of up to longest_scan elements.
+static SortBufs take_sort_bufs(Arena& ar, u64 n, u64 longest_scan = 0) {
+    SortBufs b;
+    const u32 nseg = sort_segments((u32)n);
+    b.k[0] = ar.take<u64>(n);
+    b.k[1] = ar.take<u64>(n);
+    b.v[0] = ar.take<u32>(n);
+    b.v[1] = ar.take<u32>(n);
+    b.hist = ar.take<u32>((size_t)256 * nseg + 1);
+    const u64 scan_len = longest_scan > (u64)256 * nseg ? longest_scan : (u64)256 * nseg;
+    b.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    return b;
+}
 
 // *host = *dev once the stream's work is done: the copy and the synchronisation of a builder's scalars
 template <class T>

@@ -306,15 +306,8 @@ static Workspace carve(void* base, u64 num_keys, u64 n_nodes) {
     Workspace w;
     Arena ar(base);
     const u64 kmax = num_keys > n_nodes ? num_keys : n_nodes;
-    const u32 nseg = sort_segments((u32)kmax);
     w.res = ar.take<Results>(1);
-    w.sb.k[0] = ar.take<u64>(kmax);
-    w.sb.k[1] = ar.take<u64>(kmax);
-    w.sb.v[0] = ar.take<u32>(kmax);
-    w.sb.v[1] = ar.take<u32>(kmax);
-    w.sb.hist = ar.take<u32>((size_t)256 * nseg + 1);
-    const u64 scan_len = kmax + 1 > (u64)256 * nseg ? kmax + 1 : (u64)256 * nseg;
-    w.sb.sums = ar.take<u32>((size_t)scan_blocks((u32)scan_len) + 2);
+    w.sb = take_sort_bufs(ar, kmax, kmax + 1);
     w.scan_a = ar.take<u32>(kmax + 1);
     w.scan_b = ar.take<u32>(kmax + 1);
     w.scan_c = ar.take<u32>(kmax + 1);
@@ -326,7 +319,6 @@ static Workspace carve(void* base, u64 num_keys, u64 n_nodes) {
     return w;
 }
 
-constexpr u64 kMaxKeys = 0xFFFF0000ull;      // the sort counts keys in u32, rounded up to whole 2,048-key segments
 constexpr int32_t kMaxRelations = 65536;
 
 static int check_graph(const rgcn_graph_t* g) {

@@ -2,11 +2,16 @@
 short.  tests/golden/workspace_bytes.json pins them, argument tuple by argument tuple, at the edges where a term of a carve
 switches: no and one edge, one key short of / exactly / one key over a 2,048-key sort segment, node counts that outgrow the
 edge count (the scan length follows the nodes), 1 and 65,536 relations, the three summary directions, fan-out -1 and 256, and
-arguments that must be refused with 0.  CPU only: the size queries touch no device.
+arguments that must be refused with 0.  The per-relation hop's tuples hold its fan-out vector as a list (all -1, a 0 and a 256
+entry, the unit bound set by the runs and by num_dst * R, the edge bound set by E and by num_dst * sum(k)); the relation index
+adds edge counts above both other scan lengths, the term its carve has beyond the in-edge index's.  CPU only: the size queries
+touch no device.
 
-The file was recorded from the library as it stood before the carves moved onto rgcn_sort_scan.h's Arena; run this module as a
+The file was recorded from the library as it stood before the carves moved onto rgcn_sort_scan.h's Arena, the relation index,
+the per-relation hop and the row-wise Adam from the library before their carves came to share take_sort_bufs; run this module as a
 script (python tests/test_workspace_bytes.py) to re-record the byte counts of the tuples in it from the library in the tree --
 only when a size is meant to change."""
+import ctypes as C
 import json
 import os
 
@@ -16,12 +21,18 @@ from scaling_rgcn_training_amd import _lib
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "workspace_bytes.json")
 FUNCTIONS = ["rgcn_plan_workspace_bytes", "rgcn_summary_workspace_bytes", "rgcn_sample_index_workspace_bytes",
-             "rgcn_sample_hop_workspace_bytes", "rgcn_mb_index_bytes", "rgcn_mb_index_workspace_bytes"]
+             "rgcn_sample_hop_workspace_bytes", "rgcn_sample_rel_index_workspace_bytes", "rgcn_sample_hop_rel_workspace_bytes",
+             "rgcn_mb_index_bytes", "rgcn_mb_index_workspace_bytes", "rgcn_emb_adam_rows_workspace_bytes"]
 
 
 def _golden():
     with open(GOLDEN) as f:
         return json.load(f)
+
+
+def _size(name, args):
+    """the size function's answer; a list argument (a fan-out vector) goes in as an int32 array"""
+    return int(getattr(_lib.load(), name)(*[(C.c_int32 * len(a))(*a) if isinstance(a, list) else a for a in args]))
 
 
 def test_golden_covers_every_size_function():
@@ -35,8 +46,7 @@ def test_golden_covers_every_size_function():
 
 @pytest.mark.parametrize("name", FUNCTIONS)
 def test_sizes_match_the_recorded_bytes(name):
-    fn = getattr(_lib.load(), name)
-    got = [[args, int(fn(*args))] for args, _ in _golden()[name]]
+    got = [[args, _size(name, args)] for args, _ in _golden()[name]]
     assert got == _golden()[name]
 
 
@@ -46,8 +56,7 @@ def test_sizes_are_whole_256_byte_pieces(name):
 
 
 if __name__ == "__main__":
-    lib = _lib.load()
-    rec = {name: [[args, int(getattr(lib, name)(*args))] for args, _ in cases] for name, cases in _golden().items()}
+    rec = {name: [[args, _size(name, args)] for args, _ in cases] for name, cases in _golden().items()}
     with open(GOLDEN, "w") as f:
         f.write("{\n" + ",\n".join(json.dumps(n) + ": [\n" + ",\n".join("  " + json.dumps(c) for c in rec[n]) + "\n]" for n in FUNCTIONS)
                 + "\n}\n")
