@@ -644,6 +644,69 @@ int rgcn_emb_adam_rows(float* table, float* exp_avg, float* exp_avg_sq, int32_t*
                        int64_t grad_plane_stride, int ldg, float lr, float beta1, float beta2, float eps, float weight_decay,
                        int assume_unique, int32_t* bad_ids, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- link prediction: DistMult decoder, negatives, filtered ranks (csrc/rgcn_linkpred.hip) ------------------------
+ * Additions; RGCN_ABI_VERSION stays.  Conventions of every entry point below:
+ *   z [num_nodes][ldz] and rel [num_relations][ldr] fp32; width 1..128 (RGCN_ERR_WIDTH); strides multiples of 4 and at least the
+ *   width, bases 16-byte aligned (RGCN_ERR_STRIDE); pad columns behind `width` never enter a sum, whatever they hold.  s / r / o
+ *   (anchor / r / target) are contiguous int64 device vectors.  Limits: num_nodes < 2^31, num_relations <= 65536,
+ *   2 n_triples <= 0xFFFF0000, n_queries <= 0xFFFF0000: RGCN_ERR_PLAN beyond.  NULL pointers (RGCN_ERR_NULL), negative counts
+ *   (RGCN_ERR_ARG) and small workspaces (RGCN_ERR_WORKSPACE) are answered before any launch; n_triples == 0 / n_queries == 0
+ *   launches nothing and writes nothing.  Every *_workspace_bytes answers 0 on arguments its call would refuse.
+ *   rgcn_lp_score / _index_build / _backward / _corrupt are asynchronous: no allocation, no read-back, no synchronisation.  A
+ *   triple with an id out of range scores 0, gets and gives no gradient, and sets RGCN_LP_BAD_NODE / RGCN_LP_BAD_REL in the
+ *   caller-owned device word `bad` (may be NULL; the caller zeroes it and reads it when it next synchronises).
+ *   No float atomics: the same inputs give the same bits. */
+#define RGCN_LP_BAD_NODE 1
+#define RGCN_LP_BAD_REL 2
+
+/* score[t] = sum_k z[s_t][k] rel[r_t][k] z[o_t][k].  A triple is ceil(width / 4) lanes, each adds its four products as
+ * (p0 + p1) + (p2 + p3), the lanes are added by a shuffle tree. */
+int rgcn_lp_score(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                  const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, float* score, int32_t* bad, void* stream);
+
+/* The index of one batch of triples, a function of (s, r, o) alone, into caller buffers: node_slot [2 n_triples] holds the slots
+ * 2 t + side (side 0: s_t, 1: o_t) sorted stably by their node, node_ptr [num_nodes + 1] where each node's slots begin;
+ * rel_triple [n_triples] the triples sorted stably by relation, rel_ptr [num_relations + 1].  Triples with an id out of range lie
+ * behind node_ptr[num_nodes] / rel_ptr[num_relations] and set `bad`.  One half may be left out (node_ptr NULL: no node half, which
+ * only dz needs; rel_ptr NULL: no relation half, which only drel needs). */
+size_t rgcn_lp_index_workspace_bytes(int64_t n_triples, int32_t num_nodes, int32_t num_relations);
+int rgcn_lp_index_build(const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, int32_t num_nodes,
+                        int32_t num_relations, uint32_t* node_ptr, uint32_t* node_slot, uint32_t* rel_ptr, uint32_t* rel_triple,
+                        int32_t* bad, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dz [num_nodes][lddz] and / or drel [num_relations][lddrel] (NULL: not wanted) from g [n_triples] = dL/d score and the index of
+ * the same (s, r, o).  dz[v] = sum over v's slots in sorted order of (g_t rel[r_t]) o z[other end]; EVERY row is written (zeros
+ * where a node has no triple; the pad columns of the last 16-byte piece are +0, columns behind it are not touched); s_t == o_t
+ * contributes twice.  drel[r] = sum_t (g_t z[s_t]) o z[o_t]: the relation's triples in sorted order in chunks of 256, a chunk's
+ * triples dealt round robin to the 64 / ceil(width / 4) lane groups of a wave and the groups added in order, then the chunks in
+ * order.  The workspace is needed for drel only. */
+size_t rgcn_lp_backward_workspace_bytes(int64_t n_triples, int32_t num_relations, int width);
+int rgcn_lp_backward(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                     const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, const float* g,
+                     const uint32_t* node_ptr, const uint32_t* node_slot, const uint32_t* rel_ptr, const uint32_t* rel_triple,
+                     float* dz, int lddz, float* drel, int lddrel, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Negatives: position i * num_negatives + j of the outputs holds triple i with ONE end replaced by a node id in [0, num_nodes):
+ *   d = mix(mix(seed + 0x9E3779B97F4A7C15 (i + 1)) + 0xD1B54A32D192ED03 (j + 1));   id = (d * num_nodes) >> 64;
+ *   the object is replaced when the top bit of mix(d + 0x2545F4914F6CDD1D) is set, else the subject
+ * (mix as in the sampler, arithmetic mod 2^64): a pure function of (seed, i, j, num_nodes).  Ids of s / o pass through unchecked.
+ * Negatives are not filtered against true triples.  num_nodes < 1, num_negatives < 1 or seed < 0: RGCN_ERR_ARG;
+ * n_triples * num_negatives > 0xFFFF0000: RGCN_ERR_PLAN. */
+int rgcn_lp_corrupt(const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, int32_t num_nodes, int32_t num_negatives,
+                    int64_t seed, int64_t* s_out, int64_t* r_out, int64_t* o_out, void* stream);
+
+/* Ranks.  For query q the candidate e scores (z[anchor_q] o rel[r_q]) . z[e]; over all e in [0, num_nodes) that are neither in
+ * filter_idx[filter_ptr[q] .. filter_ptr[q + 1]) nor the target, greater[q] counts the scores strictly above the target's and
+ * equal[q] those with exactly the target's bits.  filter_ptr NULL: raw ranks.  A list holds distinct ids (an id listed twice is taken
+ * off twice); entries out of range are ignored.  Every score of the call -- sweep, target, listed -- comes from one device function,
+ * so the counts are exact integers; the scores need not be rgcn_lp_score's bits.  A query with an id out of range gets -1 / -1.
+ * Scores are never written: the workspace is n_queries floats, whatever num_nodes is.  Integer atomics in the counts. */
+size_t rgcn_lp_rank_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width);
+int rgcn_lp_rank(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                 const int64_t* anchor, const int64_t* r, const int64_t* target, int64_t n_queries, const int64_t* filter_ptr,
+                 const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ Sub-modules:
   ``forward_blocks`` / ``Trainer.train_minibatch`` walk; ``block_index`` / ``BlockIndex``: the index ``RGCNConv.forward_block``
   runs a layer from, straight from a block, without graph plans
 * ``sparse_optim`` -- ``RowAdam``: Adam on the embedding rows a mini-batch step gathered, nothing else of the table is touched
+* ``linkpred`` -- link prediction: the ``DistMult`` decoder, ``corrupt`` negatives, filtered ``ranks`` / ``metrics``,
+  ``FilterIndex``, ``with_inverse_edges``; ``Trainer.train_link_prediction`` is the loop around them
 
 There is no CPU compute path: the layer raises if the HIP library or a GPU is missing.
 """
@@ -48,4 +50,7 @@ def __getattr__(name):
     if name == "RowAdam":
         from .sparse_optim import RowAdam
         return RowAdam
+    if name in ("DistMult", "corrupt", "with_inverse_edges", "FilterIndex", "ranks", "metrics"):
+        from . import linkpred
+        return getattr(linkpred, name)
     raise AttributeError(name)

@@ -148,6 +148,14 @@ def _prototypes() -> dict:
         "rgcn_emb_adam_rows_workspace_bytes": (sz, [i64, i32]),
         "rgcn_emb_adam_rows": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, f32, i32, vp, vp,
                                      sz, vp]),
+        "rgcn_lp_score": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]),
+        "rgcn_lp_index_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lp_index_build": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "rgcn_lp_backward_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lp_backward": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, sz, vp]),
+        "rgcn_lp_corrupt": (i32, [vp, vp, vp, i64, i32, i32, i64, vp, vp, vp, vp]),
+        "rgcn_lp_rank_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lp_rank": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
     }
 
 
@@ -687,6 +695,162 @@ def emb_adam_rows(table: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.
                                      grad.data_ptr(), grad.stride(0) if grad.dim() == 3 else 0, grad.stride(-2), lr, beta1, beta2, eps,
                                      weight_decay, int(bool(assume_unique)), _ptr(bad_ids),
                                      None if assume_unique else workspace.data_ptr(), nbytes, _stream(table)), "rgcn_emb_adam_rows")
+
+
+# ---- link prediction (rgcn_linkpred.hip) -----------------------------------------------------------------------------------
+LP_BAD_NODE, LP_BAD_REL = 1, 2      # RGCN_LP_BAD_*: bits of the `bad` word
+LP_MAX_KEYS = 0xFFFF0000
+
+
+def _lp_tables(what: str, z: torch.Tensor, rel: torch.Tensor):
+    """(num_nodes, num_relations, width) of ``z [N, E]`` / ``rel [R, E]`` after the checks every rgcn_lp_* call shares: fp32 on
+    one GPU, last dimension contiguous, row strides multiples of 4, bases 16-byte aligned (linkpred.py pads what is not)"""
+    for name, t in (("z", z), ("rel", rel)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32:
+            raise RgcnLibraryError(f"{what}: {name} must be a [rows, width] float32 tensor")
+        if t.device.type != "cuda":
+            raise RgcnLibraryError(f"{what}: {name} lives on {t.device}; there is no CPU fallback for the link-prediction kernels")
+        if (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) % 4 != 0 or t.stride(0) < t.shape[1] or t.data_ptr() % 16 != 0:
+            raise RgcnLibraryError(f"{what}: {name} needs a contiguous last dimension, a row stride that is a multiple of 4 and a "
+                                   f"16-byte aligned base (strides {t.stride()})")
+    if rel.device != z.device or rel.shape[1] != z.shape[1]:
+        raise RgcnLibraryError(f"{what}: z {tuple(z.shape)} on {z.device} and rel {tuple(rel.shape)} on {rel.device} do not go together")
+    return int(z.shape[0]), int(rel.shape[0]), int(z.shape[1])
+
+
+def _lp_ids(what: str, dev, **vecs) -> int:
+    """the common length of int64 id vectors on ``dev``"""
+    n = None
+    for name, t in vecs.items():
+        if not torch.is_tensor(t) or t.dim() != 1 or t.dtype != torch.int64 or t.device != dev or (t.numel() > 1 and t.stride(0) != 1):
+            raise RgcnLibraryError(f"{what}: {name} must be a contiguous int64 vector on {dev}")
+        if n is not None and int(t.shape[0]) != n:
+            raise RgcnLibraryError(f"{what}: {', '.join(vecs)} must have one length")
+        n = int(t.shape[0])
+    return n
+
+
+def _lp_bad(what: str, bad: Optional[torch.Tensor], dev) -> None:
+    if bad is not None and (bad.dtype != torch.int32 or bad.device != dev or bad.numel() != 1):
+        raise RgcnLibraryError(f"{what}: bad must be one int32 on {dev}")
+
+
+def lp_score(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor,
+             bad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rgcn_lp_score: ``score[t] = sum_k z[s_t, k] rel[r_t, k] z[o_t, k]`` -> float32 [T].  Asynchronous."""
+    n_nodes, n_rel, width = _lp_tables("rgcn_lp_score", z, rel)
+    n = _lp_ids("rgcn_lp_score", z.device, s=s, r=r, o=o)
+    _lp_bad("rgcn_lp_score", bad, z.device)
+    score = torch.empty(n, dtype=torch.float32, device=z.device)
+    if n:
+        with torch.cuda.device(z.device):
+            check(load().rgcn_lp_score(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
+                                       r.data_ptr(), o.data_ptr(), n, score.data_ptr(), _ptr(bad), _stream(z)), "rgcn_lp_score")
+    return score
+
+
+class LpIndex:
+    """the index of one batch of triples (rgcn_lp_index_build): int32 tensors that hold the library's uint32 values"""
+
+    def __init__(self, node_ptr, node_slot, rel_ptr, rel_triple, n_triples: int, num_nodes: int, num_relations: int):
+        self.node_ptr, self.node_slot, self.rel_ptr, self.rel_triple = node_ptr, node_slot, rel_ptr, rel_triple
+        self.n_triples, self.num_nodes, self.num_relations = n_triples, num_nodes, num_relations
+
+
+def lp_index_build(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes: int, num_relations: int,
+                   bad: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, nodes: bool = True,
+                   relations: bool = True) -> LpIndex:
+    """rgcn_lp_index_build on device vectors: a function of (s, r, o) alone.  ``nodes`` / ``relations``: the halves to build (dz
+    needs the first, drel the second); the other half's tensors are None.  Asynchronous; the workspace is allocated here when it is
+    missing."""
+    lib, dev = load(), s.device
+    n = _lp_ids("rgcn_lp_index_build", dev, s=s, r=r, o=o)
+    if dev.type != "cuda":
+        raise RgcnLibraryError(f"rgcn_lp_index_build: the triples live on {dev}; there is no CPU fallback for the link-prediction kernels")
+    _lp_bad("rgcn_lp_index_build", bad, dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    ix = LpIndex(torch.zeros(num_nodes + 1, **i32) if nodes else None, torch.empty(2 * n, **i32) if nodes else None,
+                 torch.zeros(num_relations + 1, **i32) if relations else None, torch.empty(n, **i32) if relations else None,
+                 n, int(num_nodes), int(num_relations))
+    if n and (nodes or relations):
+        with torch.cuda.device(dev):
+            if workspace is None:
+                workspace = torch.empty(lib.rgcn_lp_index_workspace_bytes(n, num_nodes, num_relations), dtype=torch.uint8, device=dev)
+            check(lib.rgcn_lp_index_build(s.data_ptr(), r.data_ptr(), o.data_ptr(), n, num_nodes, num_relations, _ptr(ix.node_ptr),
+                                          _ptr(ix.node_slot), _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(bad),
+                                          workspace.data_ptr(), int(workspace.numel()), _stream(s)), "rgcn_lp_index_build")
+    return ix
+
+
+def lp_backward(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, g: torch.Tensor, ix: LpIndex,
+                need_z: bool = True, need_rel: bool = True, workspace: Optional[torch.Tensor] = None):
+    """rgcn_lp_backward: ``(dz, drel)`` from ``g [T]`` and the index of the same triples; ``None`` for a gradient that is not
+    wanted.  The gradients are [rows, E] views of buffers whose rows are padded to a multiple of 4.  Asynchronous."""
+    lib, dev = load(), z.device
+    n_nodes, n_rel, width = _lp_tables("rgcn_lp_backward", z, rel)
+    n = _lp_ids("rgcn_lp_backward", dev, s=s, r=r, o=o)
+    if g.dtype != torch.float32 or g.device != dev or g.dim() != 1 or int(g.shape[0]) != n or (n > 1 and g.stride(0) != 1):
+        raise RgcnLibraryError(f"rgcn_lp_backward: g must be a contiguous float32 [{n}] on {dev}")
+    if (ix.n_triples, ix.num_nodes, ix.num_relations) != (n, n_nodes, n_rel):
+        raise RgcnLibraryError("rgcn_lp_backward: the index was built for other sizes")
+    ld = (width + 3) // 4 * 4
+    make = torch.empty if n else torch.zeros       # (no triples: nothing is launched, the gradients are zero)
+    dz = make(n_nodes, ld, dtype=torch.float32, device=dev) if need_z else None
+    drel = make(n_rel, ld, dtype=torch.float32, device=dev) if need_rel else None
+    if n and (need_z or need_rel):
+        with torch.cuda.device(dev):
+            nbytes = 0
+            if need_rel:
+                if workspace is None:
+                    workspace = torch.empty(lib.rgcn_lp_backward_workspace_bytes(n, n_rel, width), dtype=torch.uint8, device=dev)
+                nbytes = int(workspace.numel())
+            check(lib.rgcn_lp_backward(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
+                                       r.data_ptr(), o.data_ptr(), n, g.data_ptr(), _ptr(ix.node_ptr), _ptr(ix.node_slot),
+                                       _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(dz), ld, _ptr(drel), ld,
+                                       workspace.data_ptr() if need_rel else None, nbytes, _stream(z)), "rgcn_lp_backward")
+    return (None if dz is None else dz[:, :width]), (None if drel is None else drel[:, :width])
+
+
+def lp_corrupt(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes: int, num_negatives: int, seed: int):
+    """rgcn_lp_corrupt: ``(s', r', o')``, each int64 [T * num_negatives]; position ``i * num_negatives + j`` is negative j of
+    triple i.  Asynchronous."""
+    dev = s.device
+    n = _lp_ids("rgcn_lp_corrupt", dev, s=s, r=r, o=o)
+    if dev.type != "cuda":
+        raise RgcnLibraryError(f"rgcn_lp_corrupt: the triples live on {dev}; there is no CPU fallback for the link-prediction kernels")
+    out = [torch.empty(n * num_negatives, dtype=torch.int64, device=dev) for _ in range(3)]
+    with torch.cuda.device(dev):
+        check(load().rgcn_lp_corrupt(s.data_ptr(), r.data_ptr(), o.data_ptr(), n, num_nodes, num_negatives, seed, out[0].data_ptr(),
+                                     out[1].data_ptr(), out[2].data_ptr(), _stream(s)), "rgcn_lp_corrupt")
+    return tuple(out)
+
+
+def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.Tensor, target: torch.Tensor,
+            filter_ptr: Optional[torch.Tensor] = None, filter_idx: Optional[torch.Tensor] = None,
+            workspace: Optional[torch.Tensor] = None):
+    """rgcn_lp_rank: ``(greater, equal)`` int64 [Q] of the queries (anchor, r, target) over the candidates that are neither the
+    target nor in the query's filter list (CSR ``filter_ptr [Q + 1]`` / ``filter_idx``, int64; None: raw ranks).  Asynchronous."""
+    lib, dev = load(), z.device
+    n_nodes, n_rel, width = _lp_tables("rgcn_lp_rank", z, rel)
+    n = _lp_ids("rgcn_lp_rank", dev, anchor=anchor, r=r, target=target)
+    flen = 0
+    if filter_ptr is not None:
+        _lp_ids("rgcn_lp_rank", dev, filter_ptr=filter_ptr)
+        _lp_ids("rgcn_lp_rank", dev, filter_idx=filter_idx)
+        if int(filter_ptr.shape[0]) != n + 1:
+            raise RgcnLibraryError(f"rgcn_lp_rank: filter_ptr holds {int(filter_ptr.shape[0])} entries for {n} queries")
+        flen = int(filter_idx.shape[0])
+    greater = torch.empty(n, dtype=torch.int64, device=dev)
+    equal = torch.empty(n, dtype=torch.int64, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            if workspace is None:
+                workspace = torch.empty(lib.rgcn_lp_rank_workspace_bytes(n, n_nodes, width), dtype=torch.uint8, device=dev)
+            check(lib.rgcn_lp_rank(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, anchor.data_ptr(),
+                                   r.data_ptr(), target.data_ptr(), n, _ptr(filter_ptr), _ptr(filter_idx) if flen else None, flen,
+                                   greater.data_ptr(), equal.data_ptr(), workspace.data_ptr(), int(workspace.numel()), _stream(z)),
+                  "rgcn_lp_rank")
+    return greater, equal
 
 
 # ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------

@@ -68,15 +68,6 @@ struct Results {        // device-resident scalars of one call: what the host re
 
 constexpr u64 kRelMul = 0xD1B54A32D192ED03ull;      // the per-relation term of the generator's key
 
-__host__ __device__ inline u64 mix(u64 z) {      // splitmix64's finaliser
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
 // ------------------------------------------------------------------------------------------------
 // index
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // rgcn_sort_scan.h -- the integer building blocks the device-side builders share (rgcn_plan.hip: graph plans; rgcn_summary.hip:
-// node partitions and quotient graphs; rgcn_sample.hip: in-edge index and fan-out hops; rgcn_minibatch.hip: block indices): a stable
+// node partitions and quotient graphs; rgcn_sample.hip: in-edge index and fan-out hops; rgcn_minibatch.hip: block indices; rgcn_linkpred.hip: triple indices): a stable
 // LSD radix sort of (u64 key, u32 value) pairs, an exclusive scan of u32, head flags / run ids over sorted keys, and the host
 // plumbing of a builder: carving a workspace (Arena, take_sort_bufs), the other pair of the sort buffers (from_pair), the one read-back of a
 // build's scalars (read_back).  gfx950 only.  Everything has internal linkage: every including source gets its own copy of the kernels.
@@ -30,6 +30,17 @@ __host__ __device__ inline int bits_for(u64 max_value) {   // bits needed to hol
     int b = 1;
     while ((max_value >> b) != 0 && b < 64) ++b;
     return b;
+}
+
+// splitmix64's finaliser: the one mixing step of the counter-based generators (rgcn_sample.hip: fan-out draws; rgcn_linkpred.hip:
+// negatives).  A draw is a pure function of its key, never of launch geometry.
+__host__ __device__ inline u64 mix(u64 z) {
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -319,6 +319,98 @@ class Trainer:
                 print(f"Epoch: {epoch}, Loss: {loss_value:.4f}")
         return accuracies, losses, f1_ws, f1_ms
 
+    # ---- link prediction (linkpred.py) --------------------------------------------------------------------
+    def _lp_negatives(self, s: Tensor, r: Tensor, o: Tensor, num_nodes: int, num_negatives: int, step_seed: int):
+        """the negatives of one step (a hook: a CPU twin replays recorded ones)"""
+        from .linkpred import corrupt
+        return corrupt(s, r, o, num_nodes, num_negatives, step_seed)
+
+    def _lp_ranks(self, z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor, side: str, filt):
+        """(greater, equal) of one side (a hook, as above)"""
+        from .linkpred import ranks
+        return ranks(z, decoder, s, r, o, side, filt)
+
+    def train_link_prediction(self, model: nn.Module, decoder: nn.Module, training_data, train_triples: Tensor,
+                              valid_triples: Tensor = None, num_negatives: int = 1, batch_size: int = None, reg: float = 0.01,
+                              seed: int = 0) -> Tuple[List[float], List[float]]:
+        """Link prediction as PyG's ``rgcn_link_pred.py`` trains it.  ``training_data``: the encoder's graph (``edge_index`` /
+        ``edge_type``, usually ``with_inverse_edges`` of the training triples); ``train_triples`` / ``valid_triples``: int64 [P, 3]
+        rows (s, r, o).  Per step: a full-graph encode ``z = model(training_data, do_nothing)`` (the edge tensors are moved to the
+        device once, so the plan cache serves every step), a batch of positives (all of them, in order, when ``batch_size`` is
+        None; else a seeded permutation cut into batches) plus ``num_negatives`` ``corrupt`` negatives each, the loss
+        ``BCEWithLogits(scores, labels) + reg (mean z^2 + mean rel^2)`` and one Adam step (``lr``, ``weight_d``) over model and
+        decoder.  The step seed combines ``seed``, epoch and batch as ``train_minibatch`` does.  Eager only.  Returns
+        ``(losses, mrrs)``: the mean step loss per epoch, and with ``valid_triples`` the filtered MRR (both sides, ties at their
+        mean rank, filtered by train + valid triples) after every epoch, else an empty list.  ``decoder.check()`` (ids out of range)
+        runs once per epoch, beside the loss read-back."""
+        from .linkpred import FilterIndex, metrics
+        from .sampling import check_sample_seed
+        for name, t in (("train_triples", train_triples), ("valid_triples", valid_triples)):
+            if t is None and name == "valid_triples":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.int64:
+                raise ValueError(f"{name} must be an int64 [P, 3] tensor of (s, r, o) rows")
+        if train_triples.shape[0] == 0:
+            raise ValueError("train_triples is empty")
+        if isinstance(num_negatives, bool) or not isinstance(num_negatives, int) or num_negatives < 1:
+            raise ValueError(f"num_negatives must be an int >= 1 (got {num_negatives!r})")
+        if batch_size is not None and (isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1):
+            raise ValueError(f"batch_size must be None or an int >= 1 (got {batch_size!r})")
+        if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not reg >= 0:
+            raise ValueError(f"reg must be a number >= 0 (got {reg!r})")
+        seed = check_sample_seed(seed)
+        dev = self.device
+        model, decoder = model.to(dev), decoder.to(dev)
+        data = type(training_data)()
+        for k, v in training_data.__dict__.items():
+            setattr(data, k, v.to(dev) if torch.is_tensor(v) else v)
+        pos = train_triples.to(dev)
+        n_pos = int(pos.shape[0])
+        self.last_train_mode = "eager"
+        optimizer = torch.optim.Adam(list(model.parameters()) + list(decoder.parameters()), lr=self.lr, weight_decay=self.weight_d)
+        perm_gen = torch.Generator().manual_seed(seed)
+        valid = filt = None
+        losses: List[float] = []
+        mrrs: List[float] = []
+        for epoch in range(self.epochs):
+            model.train()
+            if batch_size is None:
+                batches = [pos]
+            else:
+                perm = torch.randperm(n_pos, generator=perm_gen).to(dev)
+                batches = [pos[perm[start:start + batch_size]] for start in range(0, n_pos, batch_size)]
+            step_losses = []
+            for b, batch in enumerate(batches):
+                s, r, o = (batch[:, c].contiguous() for c in range(3))
+                step_seed = (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
+                optimizer.zero_grad()
+                z = model(data, do_nothing)
+                sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, step_seed)
+                scores = decoder(z, torch.cat([s, sn]), torch.cat([r, rn]), torch.cat([o, on]))
+                labels = torch.cat([torch.ones(s.shape[0], device=dev), torch.zeros(sn.shape[0], device=dev)])
+                output = nn.functional.binary_cross_entropy_with_logits(scores, labels)
+                output = output + reg * (z.pow(2).mean() + decoder.rel.pow(2).mean())
+                output.backward()
+                optimizer.step()
+                step_losses.append(output.detach())
+            loss_value = float(torch.stack(step_losses).mean().item())
+            if hasattr(decoder, "check"):
+                decoder.check()
+            losses.append(loss_value)
+            if valid_triples is not None:
+                if valid is None:
+                    valid = valid_triples.to(dev)
+                    filt = FilterIndex(torch.cat([pos, valid]), int(z.shape[0]), int(decoder.rel.shape[0]))
+                model.eval()
+                with torch.no_grad():
+                    z = model(data, do_nothing)
+                vs, vr, vo = (valid[:, c].contiguous() for c in range(3))
+                counts = [self._lp_ranks(z, decoder, vs, vr, vo, side, filt) for side in ("object", "subject")]
+                mrrs.append(metrics(torch.cat([c[0] for c in counts]), torch.cat([c[1] for c in counts]))["mrr"])
+            if self.verbose and epoch % 10 == 0:
+                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}" + (f", filtered MRR: {mrrs[-1]:.4f}" if mrrs else ""))
+        return losses, mrrs
+
     def _train_hipgraph(self, model, training_data, targets, loss_f, activation, sum_graph):
         """The same epoch loop with its GPU work replayed from two hipGraphs: ``g_eval`` (validation forward in eval mode,
         no autograd) and ``g_train`` (zero_grad + forward + loss + backward + Adam step, ``capturable=True``: the step
