@@ -20,6 +20,13 @@ from .conv import RGCNConv
 from .data import Data
 
 
+def _check_blocks(method: str, blocks, block_kernels) -> None:
+    if not isinstance(block_kernels, bool):
+        raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
+    if len(blocks) != 2:
+        raise ValueError(f"the models have two RGCN layers: {method} takes 2 blocks, got {len(blocks)}")
+
+
 class _RGCNStack(nn.Module):
     """x -> rgcn1 -> relu -> rgcn2 -> activation, the tail all three reference models share
     (model/layers.py:21-25, 62-66, 108-112), plus the parameter re-binding contract."""
@@ -67,10 +74,7 @@ class _RGCNStack(nn.Module):
         rows ``[blocks[1].n_dst, num_labels]``.  Eager torch activations; ``forward`` is untouched.  ``block_kernels=True`` (off by
         default): both layers run straight from their blocks on the kernels of csrc/rgcn_minibatch.hip (``RGCNConv.forward_block``,
         DESIGN.md 15) instead of the bipartite layer on freshly built graph plans."""
-        if not isinstance(block_kernels, bool):
-            raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
-        if len(blocks) != 2:
-            raise ValueError(f"the models have two RGCN layers: forward_blocks takes 2 blocks, got {len(blocks)}")
+        _check_blocks("forward_blocks", blocks, block_kernels)
         return self._tail_blocks(self._block_input(blocks[0].src_nodes), blocks, activation, block_kernels)
 
     def forward_blocks_from_rows(self, blocks, activation: Callable, embedding_rows: Tensor, block_kernels: bool = False) -> Tensor:
@@ -78,10 +82,7 @@ class _RGCNStack(nn.Module):
         is the leaf ``self.embedding_rows(blocks[0].src_nodes)`` returned; the pre-transform starts from it and its ``.grad`` is
         the gradient of exactly those rows.  The same output as ``forward_blocks``, bit for bit.  (A method of its
         own: ``forward_blocks`` keeps its signature.)"""
-        if not isinstance(block_kernels, bool):
-            raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
-        if len(blocks) != 2:
-            raise ValueError(f"the models have two RGCN layers: forward_blocks_from_rows takes 2 blocks, got {len(blocks)}")
+        _check_blocks("forward_blocks_from_rows", blocks, block_kernels)
         if not torch.is_tensor(embedding_rows) or embedding_rows.dim() < 2 or embedding_rows.shape[-2] != blocks[0].n_src:
             raise ValueError(f"embedding_rows must hold one row per source node of blocks[0] ({blocks[0].n_src})")
         return self._tail_blocks(self._pre_transform(embedding_rows), blocks, activation, block_kernels)

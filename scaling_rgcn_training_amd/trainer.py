@@ -92,6 +92,31 @@ class _CaptureFailed(RuntimeError):
     pass
 
 
+def _check_number(name: str, value, types, low: int, words: str) -> None:
+    if isinstance(value, bool) or not isinstance(value, types) or not value >= low:
+        raise ValueError(f"{name} must be {words} >= {low} (got {value!r})")
+
+
+def _step_seed(seed: int, epoch: int, b: int) -> int:
+    """the sampler / negatives seed of batch ``b`` of ``epoch``: runs repeat, steps differ"""
+    return (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
+
+
+def _cut_batches(n: int, batch_size: int, perm_gen: torch.Generator, device) -> List[Tensor]:
+    """one permutation of ``range(n)`` from ``perm_gen``, on ``device``, cut into consecutive batches (the last may be short)"""
+    perm = torch.randperm(n, generator=perm_gen).to(device)
+    return [perm[start:start + batch_size] for start in range(0, n, batch_size)]
+
+
+def _data_to(data, device, **overrides):
+    """a new bag of ``data``'s type with every tensor attribute on ``device``; ``overrides`` replace attributes by name"""
+    out = type(data)()
+    for k, v in data.__dict__.items():
+        v = overrides.get(k, v)
+        setattr(out, k, v.to(device) if torch.is_tensor(v) else v)
+    return out
+
+
 class Trainer:
     """``Trainer(data, hidden_l, epochs, emb_dim, lr, weight_d)`` with ``train_summaries``,
     ``train_original``, ``train`` and ``transfer_weights`` as in the reference.  ``data`` is any object
@@ -146,16 +171,7 @@ class Trainer:
                 graph._device_edges = cached
             except AttributeError:
                 pass
-        out = type(data)()
-        for k, v in data.__dict__.items():
-            if k == "edge_index":
-                v = cached[1]
-            elif k == "edge_type":
-                v = cached[2]
-            elif torch.is_tensor(v):
-                v = v.to(self.device)
-            setattr(out, k, v)
-        return out
+        return _data_to(data, self.device, edge_index=cached[1], edge_type=cached[2])
 
     def _want_hipgraph(self, training_data, model: nn.Module = None) -> bool:
         if self.device.type != "cuda" or not self.eval_no_grad:
@@ -184,27 +200,40 @@ class Trainer:
                     print(f"hipGraph capture not possible ({err}); training eagerly")
         self.last_train_mode = "eager"
         optimizer = torch.optim.Adam(model.parameters(), lr=self.lr, weight_decay=self.weight_d)
+
+        def train_epoch(epoch):
+            model.train()
+            optimizer.zero_grad()
+            output = loss_f(model(training_data, activation)[training_data.x_train], targets)
+            output.backward()
+            optimizer.step()
+            return output
+
+        return self._run_epochs(sum_graph, lambda: self._validate(model, activation, training_data), train_epoch)
+
+    def _validate(self, model: nn.Module, activation: Callable, training_data) -> Tuple[float, float, float]:
+        """the eager validation: eval mode, one full-graph forward, the metrics of the validation rows"""
+        model.eval()
+        return evaluate(model, activation, training_data, training_data.x_val, training_data.y_val, no_grad=self.eval_no_grad)
+
+    def _run_epochs(self, sum_graph: bool, validate: Callable, train_epoch: Callable, after_epoch: Callable = None):
+        """THE epoch loop of every training path, with both prints.  Per epoch: unless ``sum_graph``, ``validate() -> (accuracy,
+        weighted F1, macro F1)``; ``train_epoch(epoch) -> loss``, all of the epoch's training, its 0-d loss read back ONCE here;
+        ``after_epoch() -> str`` where a path has work after its epoch: what it returns ends the loss line."""
         accuracies, losses, f1_ws, f1_ms = [], [], [], []
         for epoch in range(self.epochs):
             if not sum_graph:
-                model.eval()
-                acc, f1_w, f1_m = evaluate(model, activation, training_data, training_data.x_val,
-                                           training_data.y_val, no_grad=self.eval_no_grad)
+                acc, f1_w, f1_m = validate()
                 if self.verbose:
                     print(f"Accuracy on validation set = {acc}")
                 accuracies.append(acc)
                 f1_ws.append(f1_w)
                 f1_ms.append(f1_m)
-            model.train()
-            optimizer.zero_grad()
-            out = model(training_data, activation)
-            output = loss_f(out[training_data.x_train], targets)
-            output.backward()
-            optimizer.step()
-            loss_value = output.item()
+            loss_value = train_epoch(epoch).item()
             losses.append(loss_value)
+            suffix = after_epoch() if after_epoch is not None else ""
             if self.verbose and epoch % 10 == 0:
-                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}")
+                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}{suffix}")
         return accuracies, losses, f1_ws, f1_ms
 
     def _sampler(self, graph, training_data, model: nn.Module):
@@ -248,11 +277,9 @@ class Trainer:
         from .sampling import check_fanouts, check_sample_seed
         if not isinstance(block_kernels, bool):
             raise ValueError(f"block_kernels must be a bool (got {block_kernels!r})")
-        sparse_embedding = getattr(self, "sparse_embedding", False)
-        if not isinstance(sparse_embedding, bool):
-            raise ValueError(f"Trainer.sparse_embedding must be a bool (got {sparse_embedding!r})")
-        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
-            raise ValueError(f"batch_size must be an int >= 1 (got {batch_size!r})")
+        if not isinstance(self.sparse_embedding, bool):        # an attribute: it may have been assigned since the constructor
+            raise ValueError(f"Trainer.sparse_embedding must be a bool (got {self.sparse_embedding!r})")
+        _check_number("batch_size", batch_size, int, 1, "an int")
         fanouts = check_fanouts(fanouts)
         if len(fanouts) != 2:
             raise ValueError(f"the models have two RGCN layers: fanouts takes 2 entries, got {len(fanouts)}")
@@ -266,11 +293,9 @@ class Trainer:
         sampler = self._sampler(graph, training_data, model)
         targets = training_data.y_train.to(torch.float32)
         x_train = training_data.x_train.to(self.device)
-        n_train = int(x_train.shape[0])
-        self.last_train_mode = "eager"
-        self.last_batches = []
+        self.last_train_mode, self.last_batches = "eager", []
         row_adam = None
-        table = model.embedding_table() if sparse_embedding else None
+        table = model.embedding_table() if self.sparse_embedding else None
         if table is not None and table.requires_grad:
             from .sparse_optim import RowAdam
             row_adam = RowAdam(table, lr=self.lr, weight_decay=self.weight_d)
@@ -278,31 +303,20 @@ class Trainer:
         else:
             optimizer = torch.optim.Adam(model.parameters(), lr=self.lr, weight_decay=self.weight_d)
         perm_gen = torch.Generator().manual_seed(seed)
-        accuracies, losses, f1_ws, f1_ms = [], [], [], []
-        for epoch in range(self.epochs):
-            if not sum_graph:
-                model.eval()
-                acc, f1_w, f1_m = evaluate(model, activation, training_data, training_data.x_val,
-                                           training_data.y_val, no_grad=self.eval_no_grad)
-                if self.verbose:
-                    print(f"Accuracy on validation set = {acc}")
-                accuracies.append(acc)
-                f1_ws.append(f1_w)
-                f1_ms.append(f1_m)
+        block_args = (block_kernels,) if block_kernels else ()       # a model with the two-argument ``forward_blocks`` keeps working
+
+        def train_epoch(epoch):
             model.train()
-            perm = torch.randperm(n_train, generator=perm_gen).to(self.device)
             batch_losses, batches = [], []
-            for b, start in enumerate(range(0, n_train, batch_size)):
-                rows = perm[start:start + batch_size]
+            for b, rows in enumerate(_cut_batches(int(x_train.shape[0]), batch_size, perm_gen, self.device)):
                 batch = x_train[rows]
-                step_seed = (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
-                blocks = sampler.sample(batch, fanouts, step_seed)
+                blocks = sampler.sample(batch, fanouts, _step_seed(seed, epoch, b))
                 optimizer.zero_grad()
                 if row_adam is not None:
                     emb_rows = model.embedding_rows(blocks[0].src_nodes)
                     out = model.forward_blocks_from_rows(blocks, activation, emb_rows, block_kernels)
                 else:
-                    out = model.forward_blocks(blocks, activation, block_kernels) if block_kernels else model.forward_blocks(blocks, activation)
+                    out = model.forward_blocks(blocks, activation, *block_args)
                 output = loss_f(out, targets[rows])
                 output.backward()
                 optimizer.step()
@@ -310,14 +324,12 @@ class Trainer:
                     row_adam.step(blocks[0].src_nodes, emb_rows.grad, assume_unique=True)
                 batch_losses.append(output.detach())
                 batches.append(batch)
-            loss_value = float(torch.stack(batch_losses).mean().item()) if batch_losses else float("nan")
+            self.last_batches = batches
             if row_adam is not None:
                 row_adam.check()
-            losses.append(loss_value)
-            self.last_batches = batches
-            if self.verbose and epoch % 10 == 0:
-                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}")
-        return accuracies, losses, f1_ws, f1_ms
+            return torch.stack(batch_losses).mean() if batch_losses else torch.tensor(float("nan"))
+
+        return self._run_epochs(sum_graph, lambda: self._validate(model, activation, training_data), train_epoch)
 
     # ---- link prediction (linkpred.py) --------------------------------------------------------------------
     def _lp_negatives(self, s: Tensor, r: Tensor, o: Tensor, num_nodes: int, num_negatives: int, step_seed: int):
@@ -352,40 +364,30 @@ class Trainer:
                 raise ValueError(f"{name} must be an int64 [P, 3] tensor of (s, r, o) rows")
         if train_triples.shape[0] == 0:
             raise ValueError("train_triples is empty")
-        if isinstance(num_negatives, bool) or not isinstance(num_negatives, int) or num_negatives < 1:
-            raise ValueError(f"num_negatives must be an int >= 1 (got {num_negatives!r})")
-        if batch_size is not None and (isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1):
-            raise ValueError(f"batch_size must be None or an int >= 1 (got {batch_size!r})")
-        if isinstance(reg, bool) or not isinstance(reg, (int, float)) or not reg >= 0:
-            raise ValueError(f"reg must be a number >= 0 (got {reg!r})")
+        _check_number("num_negatives", num_negatives, int, 1, "an int")
+        if batch_size is not None:
+            _check_number("batch_size", batch_size, int, 1, "None or an int")
+        _check_number("reg", reg, (int, float), 0, "a number")
         seed = check_sample_seed(seed)
         dev = self.device
         model, decoder = model.to(dev), decoder.to(dev)
-        data = type(training_data)()
-        for k, v in training_data.__dict__.items():
-            setattr(data, k, v.to(dev) if torch.is_tensor(v) else v)
+        data = _data_to(training_data, dev)
         pos = train_triples.to(dev)
-        n_pos = int(pos.shape[0])
+        valid = valid_triples.to(dev) if valid_triples is not None else None
         self.last_train_mode = "eager"
         optimizer = torch.optim.Adam(list(model.parameters()) + list(decoder.parameters()), lr=self.lr, weight_decay=self.weight_d)
         perm_gen = torch.Generator().manual_seed(seed)
-        valid = filt = None
-        losses: List[float] = []
-        mrrs: List[float] = []
-        for epoch in range(self.epochs):
+        filt, mrrs = None, []
+
+        def train_epoch(epoch):
             model.train()
-            if batch_size is None:
-                batches = [pos]
-            else:
-                perm = torch.randperm(n_pos, generator=perm_gen).to(dev)
-                batches = [pos[perm[start:start + batch_size]] for start in range(0, n_pos, batch_size)]
+            batches = [pos] if batch_size is None else [pos[rows] for rows in _cut_batches(int(pos.shape[0]), batch_size, perm_gen, dev)]
             step_losses = []
             for b, batch in enumerate(batches):
                 s, r, o = (batch[:, c].contiguous() for c in range(3))
-                step_seed = (seed * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03 + b * 0x2545F4914F6CDD1D) % (2 ** 63)
                 optimizer.zero_grad()
                 z = model(data, do_nothing)
-                sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, step_seed)
+                sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, _step_seed(seed, epoch, b))
                 scores = decoder(z, torch.cat([s, sn]), torch.cat([r, rn]), torch.cat([o, on]))
                 labels = torch.cat([torch.ones(s.shape[0], device=dev), torch.zeros(sn.shape[0], device=dev)])
                 output = nn.functional.binary_cross_entropy_with_logits(scores, labels)
@@ -393,22 +395,25 @@ class Trainer:
                 output.backward()
                 optimizer.step()
                 step_losses.append(output.detach())
-            loss_value = float(torch.stack(step_losses).mean().item())
+            return torch.stack(step_losses).mean()
+
+        def after_epoch():
+            nonlocal filt
             if hasattr(decoder, "check"):
                 decoder.check()
-            losses.append(loss_value)
-            if valid_triples is not None:
-                if valid is None:
-                    valid = valid_triples.to(dev)
-                    filt = FilterIndex(torch.cat([pos, valid]), int(z.shape[0]), int(decoder.rel.shape[0]))
-                model.eval()
-                with torch.no_grad():
-                    z = model(data, do_nothing)
-                vs, vr, vo = (valid[:, c].contiguous() for c in range(3))
-                counts = [self._lp_ranks(z, decoder, vs, vr, vo, side, filt) for side in ("object", "subject")]
-                mrrs.append(metrics(torch.cat([c[0] for c in counts]), torch.cat([c[1] for c in counts]))["mrr"])
-            if self.verbose and epoch % 10 == 0:
-                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}" + (f", filtered MRR: {mrrs[-1]:.4f}" if mrrs else ""))
+            if valid is None:
+                return ""
+            model.eval()
+            with torch.no_grad():
+                z = model(data, do_nothing)
+            if filt is None:
+                filt = FilterIndex(torch.cat([pos, valid]), int(z.shape[0]), int(decoder.rel.shape[0]))
+            vs, vr, vo = (valid[:, c].contiguous() for c in range(3))
+            counts = [self._lp_ranks(z, decoder, vs, vr, vo, side, filt) for side in ("object", "subject")]
+            mrrs.append(metrics(torch.cat([c[0] for c in counts]), torch.cat([c[1] for c in counts]))["mrr"])
+            return f", filtered MRR: {mrrs[-1]:.4f}"
+
+        _, losses, _, _ = self._run_epochs(True, None, train_epoch, after_epoch)       # nothing before the epoch: the ranking follows it
         return losses, mrrs
 
     def _train_hipgraph(self, model, training_data, targets, loss_f, activation, sum_graph):
@@ -420,14 +425,13 @@ class Trainer:
         Per epoch the host does two replays, one host copy of the validation rows and the ``.item()`` of the loss
         (both part of the reference's API: modelTrainer.py:55,68)."""
         dev = self.device
-        params = [q for q in model.parameters()]
-        saved = [q.detach().clone() for q in params]
+        params = list(model.parameters())
         # the warm-up epoch also advances what is not a parameter: module buffers and the device's RNG stream (the attention
         # model's dropout) -- both are put back, so that the captured loop starts where an eager ``train`` starts.  (Inside
         # the replayed graphs the dropout masks come from torch's graph-safe Philox offsets: same distribution as the eager
         # loop's, not the same stream -- loss curves of Emb_ATT_Layers with dropout agree statistically, not bit for bit.)
-        buffers = [b for b in model.buffers()]
-        saved_buffers = [b.detach().clone() for b in buffers]
+        moved = params + list(model.buffers())
+        saved = [t.detach().clone() for t in moved]
         rng_state = torch.cuda.get_rng_state(dev)
         optimizer = torch.optim.Adam(params, lr=self.lr, weight_decay=self.weight_d, capturable=True)
         idx_train = training_data.x_train.to(dev)
@@ -444,6 +448,11 @@ class Trainer:
             with torch.no_grad():
                 return model(training_data, activation)
 
+        def restore():
+            with torch.no_grad():
+                for t, t0 in zip(moved, saved):
+                    t.copy_(t0)
+
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         try:
@@ -455,15 +464,11 @@ class Trainer:
                 train_step()
                 # undo the warm-up epoch: parameters back, Adam moments and step count zeroed IN PLACE (their tensors are
                 # what the captured optimizer step reads and writes)
-                with torch.no_grad():
-                    for q, q0 in zip(params, saved):
-                        q.copy_(q0)
-                    for b, b0 in zip(buffers, saved_buffers):
-                        b.copy_(b0)
-                    for st in optimizer.state.values():
-                        for v in st.values():
-                            if torch.is_tensor(v):
-                                v.zero_()
+                restore()
+                for st in optimizer.state.values():
+                    for v in st.values():
+                        if torch.is_tensor(v):
+                            v.zero_()
                 torch.cuda.set_rng_state(rng_state, dev)
                 optimizer.zero_grad(set_to_none=True)
                 g_eval = g_train = pred = loss = None
@@ -478,34 +483,27 @@ class Trainer:
                     loss = train_step()
         except RuntimeError as err:
             torch.cuda.synchronize(dev)
-            with torch.no_grad():
-                for q, q0 in zip(params, saved):
-                    q.copy_(q0)
+            restore()
             for q in params:
                 q.grad = None
             raise _CaptureFailed(str(err).splitlines()[0] if str(err) else type(err).__name__) from err
         torch.cuda.current_stream(dev).wait_stream(side)
-        accuracies, losses, f1_ws, f1_ms = [], [], [], []
-        for epoch in range(self.epochs):
-            if not sum_graph:
-                g_eval.replay()
-                acc, f1_w, f1_m = _metrics(pred, activation, training_data.x_val, training_data.y_val)
-                if self.verbose:
-                    print(f"Accuracy on validation set = {acc}")
-                accuracies.append(acc)
-                f1_ws.append(f1_w)
-                f1_ms.append(f1_m)
+
+        def validate():
+            g_eval.replay()
+            return _metrics(pred, activation, training_data.x_val, training_data.y_val)
+
+        def train_epoch(epoch):
             g_train.replay()
-            loss_value = loss.item()
-            losses.append(loss_value)
-            if self.verbose and epoch % 10 == 0:
-                print(f"Epoch: {epoch}, Loss: {loss_value:.4f}")
+            return loss
+
+        out = self._run_epochs(sum_graph, validate, train_epoch)
         model.train()
         # the gradients live in the graph's private pool: hand the caller ordinary tensors
         for q in params:
             if q.grad is not None:
                 q.grad = q.grad.detach().clone()
-        return accuracies, losses, f1_ws, f1_ms
+        return out
 
     def train_summaries(self, configs: Dict[str, Union[bool, str, int, float]]) -> None:
         loss_f, activation = get_losst(configs["dataset"], sumModel=True)
