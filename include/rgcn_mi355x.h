@@ -707,6 +707,54 @@ int rgcn_lp_rank(const float* z, int ldz, const float* rel, int ldr, int width, 
                  const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- summaries -> original graph on tensors: block labels, transferred embeddings (csrc/rgcn_transfer.hip) ----------
+ * Additions; RGCN_ABI_VERSION stays.  Both calls are asynchronous: no allocation, no read-back, no synchronisation, everything on
+ * `stream`.  Argument checks come before the device is looked at.  An id out of range is never used as an address: it sets one of
+ * the bits below in the caller-owned device word `bad` (may be NULL; the caller zeroes it and reads it when it next synchronises).
+ * Integer atomics only: the same inputs give the same bits. */
+#define RGCN_TR_BAD_BLOCK 1 /* a block id outside [0, num_blocks) */
+#define RGCN_TR_BAD_NODE 2  /* a train_idx / nodes entry outside [0, num_nodes) */
+#define RGCN_TR_BAD_MAP 4   /* a map value < -1 or >= the table's rows */
+#define RGCN_TR_MAX_TABLES 16
+#define RGCN_TR_STACK 0  /* out [S][n_out][width]: one plane per table (plane_stride floats apart) */
+#define RGCN_TR_CONCAT 1 /* out [n_out][S width]: the tables side by side */
+#define RGCN_TR_SUM 2    /* out [n_out][width]: ((0 + t_0) + t_1) + ... in fp32, in table order */
+
+/* The fractional labels of a node partition.  block [num_nodes] holds ids in [0, num_blocks); train_idx [n_train] distinct node
+ * ids; y [n_train][ldy] int64 counts (the multi-hot rows of the training nodes).  Out: size [num_blocks] = nodes per block;
+ * y_sum[b][c] = (float)((double)(sum of y[i][c] over the rows i with block[train_idx[i]] == b) / (double)max(1, size[b])) in rows
+ * of ld floats (columns behind `classes` are not touched); nonzero[b] = 1 where the integer sum of the row is not 0.  The sums are
+ * int32.  Equal block ids of a wave are combined before they reach memory, so the one-block partition is one atomic per wave.
+ * A node whose block id is out of range counts nowhere (RGCN_TR_BAD_BLOCK), a training row whose node is out of range adds
+ * nothing (RGCN_TR_BAD_NODE).  workspace: num_blocks x classes int32.
+ * Refusals: NULL size / y_sum / nonzero / workspace (block with num_nodes > 0, train_idx / y with n_train > 0): RGCN_ERR_NULL;
+ * num_blocks < 1, classes < 1, a negative count, ld < classes, ldy < classes: RGCN_ERR_ARG; num_nodes, num_blocks or n_train
+ * >= 2^31, classes > 65536, n_train x classes or num_blocks x classes > 2^38: RGCN_ERR_PLAN; a small workspace:
+ * RGCN_ERR_WORKSPACE.  The query answers 0 on arguments the call refuses. */
+size_t rgcn_tr_block_labels_workspace_bytes(int64_t num_nodes, int64_t num_blocks, int64_t n_train, int classes);
+int rgcn_tr_block_labels(const int64_t* block, int64_t num_nodes, int64_t num_blocks, const int64_t* train_idx, const int64_t* y,
+                         int64_t ldy, int64_t n_train, int classes, int32_t* size, float* y_sum, int64_t ld, int32_t* nonzero,
+                         int32_t* bad, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The transferred embedding of the nodes `nodes` [n_out] (repeats allowed; NULL: all num_nodes nodes in order, n_out ==
+ * num_nodes) from S = num_tables summary tables.  tables / lds / rows / maps are HOST arrays of S entries: table s is fp32
+ * [rows[s]][lds[s]] on the device, maps[s] int64 [num_nodes] on the device with the row of every node in table s, or -1 where the
+ * node is not mapped.  A mapped node's piece is the table row; an unmapped node's piece is uniform in [0, 1):
+ *   bits = mix(mix(seed + 0x9E3779B97F4A7C15 (s + 1)) + node * width + column);   value = (bits >> 40) * 2^-24
+ * (mix as in the sampler, arithmetic mod 2^64): a pure function of (seed, s, node, column), never of the launch, n_out, the node's
+ * position or the mode.  A nodes entry outside [0, num_nodes) gives a row of zeros (RGCN_TR_BAD_NODE), a map value < -1 or >=
+ * rows[s] a piece of zeros (RGCN_TR_BAD_MAP).  ld_out: floats between output rows; plane_stride: floats between the planes of
+ * RGCN_TR_STACK (ignored otherwise).  Whole 16-byte pieces move as such when every lds[s], ld_out (and plane_stride, and width for
+ * RGCN_TR_CONCAT) is a multiple of 4 and every base is 16-byte aligned; anything else goes element by element.  Rows are addressed
+ * by 64-bit element offsets.  No workspace.
+ * Refusals: NULL arrays, a NULL table with rows, a NULL map with nodes, NULL out with n_out > 0: RGCN_ERR_NULL; num_tables outside
+ * 1 .. 16, width < 1, an unknown mode, a negative count or seed, nodes == NULL with n_out != num_nodes: RGCN_ERR_ARG; lds[s] <
+ * width, ld_out smaller than an output row, overlapping planes: RGCN_ERR_STRIDE; num_nodes or n_out >= 2^31: RGCN_ERR_PLAN.
+ * n_out == 0 launches nothing. */
+int rgcn_tr_gather(const float* const* tables, const int32_t* lds, const int64_t* rows, const int64_t* const* maps, int num_tables,
+                   int width, int64_t num_nodes, const int64_t* nodes, int64_t n_out, int mode, int64_t seed, float* out,
+                   int64_t ld_out, int64_t plane_stride, int32_t* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

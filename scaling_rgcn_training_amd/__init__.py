@@ -19,6 +19,9 @@ Sub-modules:
 * ``sparse_optim`` -- ``RowAdam``: Adam on the embedding rows a mini-batch step gathered, nothing else of the table is touched
 * ``linkpred`` -- link prediction: the ``DistMult`` decoder, ``corrupt`` negatives, filtered ``ranks`` / ``metrics``,
   ``FilterIndex``, ``with_inverse_edges``; ``Trainer.train_link_prediction`` is the loop around them
+* ``transfer`` -- summaries -> original graph on tensors: ``summary_labels`` (the fractional labels of a partition's blocks),
+  ``TransferredEmbedding`` and the ``stack`` / ``concat`` / ``sum_embeddings`` tricks ``Trainer.train_original`` takes
+* ``tensor_data`` -- ``TensorDataset`` / ``TensorGraph``: the dataset ``Trainer`` reads, for a graph that has no node names
 
 There is no CPU compute path: the layer raises if the HIP library or a GPU is missing.
 """
@@ -53,4 +56,10 @@ def __getattr__(name):
     if name in ("DistMult", "corrupt", "with_inverse_edges", "FilterIndex", "ranks", "metrics"):
         from . import linkpred
         return getattr(linkpred, name)
+    if name in ("TensorDataset", "TensorGraph"):
+        from . import tensor_data
+        return getattr(tensor_data, name)
+    if name in ("TransferredEmbedding", "summary_labels"):
+        from . import transfer
+        return getattr(transfer, name)
     raise AttributeError(name)

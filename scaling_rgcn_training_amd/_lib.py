@@ -156,6 +156,9 @@ def _prototypes() -> dict:
         "rgcn_lp_corrupt": (i32, [vp, vp, vp, i64, i32, i32, i64, vp, vp, vp, vp]),
         "rgcn_lp_rank_workspace_bytes": (sz, [i64, i32, i32]),
         "rgcn_lp_rank": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
+        "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
+        "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
+        "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
     }
 
 
@@ -851,6 +854,50 @@ def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.T
                                    greater.data_ptr(), equal.data_ptr(), workspace.data_ptr(), int(workspace.numel()), _stream(z)),
                   "rgcn_lp_rank")
     return greater, equal
+
+
+# ---- summaries -> original graph (rgcn_transfer.hip; transfer.py validates and drives them) ---------------------------------
+TR_BAD_BLOCK, TR_BAD_NODE, TR_BAD_MAP = 1, 2, 4      # RGCN_TR_BAD_*: bits of the `bad` word
+TR_MAX_TABLES = 16
+TR_MODES = {"stack": 0, "concat": 1, "sum": 2}       # RGCN_TR_STACK / _CONCAT / _SUM
+
+
+def tr_block_labels(block: torch.Tensor, num_blocks: int, train_idx: torch.Tensor, y: torch.Tensor, bad: Optional[torch.Tensor] = None):
+    """rgcn_tr_block_labels on contiguous int64 device tensors ``block [N]``, ``train_idx [L]``, ``y [L, C]`` ->
+    ``(size int32 [B], y_sum float32 [B, C], nonzero int32 [B])``.  Asynchronous on the current stream of ``block``'s device."""
+    lib, dev = load(), block.device
+    n, l, c = int(block.shape[0]), int(train_idx.shape[0]), int(y.shape[1])
+    nbytes = lib.rgcn_tr_block_labels_workspace_bytes(n, int(num_blocks), l, c)
+    if nbytes == 0:
+        raise RgcnLibraryError("rgcn_tr_block_labels_workspace_bytes: bad arguments")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        size = torch.empty(num_blocks, dtype=torch.int32, device=dev)
+        nonzero = torch.empty(num_blocks, dtype=torch.int32, device=dev)
+        y_sum = torch.empty(num_blocks, c, dtype=torch.float32, device=dev)
+        check(lib.rgcn_tr_block_labels(block.data_ptr() if n else None, n, int(num_blocks), train_idx.data_ptr() if l else None,
+                                       y.data_ptr() if l else None, c, l, c, size.data_ptr(), y_sum.data_ptr(), c, nonzero.data_ptr(),
+                                       _ptr(bad), ws.data_ptr(), nbytes, _stream(block)), "rgcn_tr_block_labels")
+    return size, y_sum, nonzero
+
+
+def tr_gather(tables, maps, num_nodes: int, width: int, nodes: Optional[torch.Tensor], mode: int, seed: int, out: torch.Tensor,
+              bad: Optional[torch.Tensor] = None) -> None:
+    """rgcn_tr_gather into ``out`` (contiguous: [S, M, E], [M, S E] or [M, E] by ``mode``); ``tables``: fp32 [B_s, E] device
+    tensors with a contiguous last dimension (any row stride), ``maps``: contiguous int64 [N], ``nodes``: contiguous int64 [M] or
+    None.  Asynchronous on the current stream of ``out``'s device."""
+    s = len(tables)
+    m = int(num_nodes) if nodes is None else int(nodes.shape[0])
+    if m == 0:      # (nothing to write; an empty tensor has no address to pass)
+        return
+    tabs = (C.c_void_p * s)(*[t.data_ptr() if t.shape[0] else None for t in tables])
+    lds = (C.c_int32 * s)(*[int(t.stride(0)) if t.shape[0] > 1 else int(width) for t in tables])
+    rows = (C.c_int64 * s)(*[int(t.shape[0]) for t in tables])
+    mps = (C.c_void_p * s)(*[mp.data_ptr() for mp in maps])
+    with torch.cuda.device(out.device):
+        check(load().rgcn_tr_gather(tabs, lds, rows, mps, s, int(width), int(num_nodes), _ptr(nodes), m, int(mode), int(seed),
+                                    out.data_ptr(), int(out.stride(-2)), int(out.stride(0)) if out.dim() == 3 else 0, _ptr(bad),
+                                    _stream(out)), "rgcn_tr_gather")
 
 
 # ---- bipartite layers: the root term (rgcn_rows.hip) ------------------------------------------------------------------
