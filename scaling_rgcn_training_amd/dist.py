@@ -23,8 +23,10 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
+from . import _lib
 from .conv import DistContext, RGCNConv
-from .plan import GraphPlans, build_plan, cached_graph_plans, edge_weights
+from .eplan import HEAVY, build_edge_plan, build_shared_heavy, check_ep_ranges
+from .plan import GraphPlans, PlanBuild, build_plan, cached_graph_plans, edge_weights, range_plans
 
 
 PIECES = 4  # gather pipeline depth: the collective of piece s runs under the kernels of piece s + 1
@@ -286,20 +288,28 @@ def rank_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relation
     laid out from the same edge list: on the GPU by the library's plan builder with the piece's node range (it keeps
     the edges that scatter into the range), on the CPU (tests) by the torch form from this rank's share."""
     ranges = [dctx.node_range(s, n_nodes) for s in range(dctx.pieces)]
-    from .eplan import check_ep_ranges
     check_ep_ranges(paths, [(r, r) for r in ranges])
     nf, nb = needed_rows(edge_index, n_nodes, dctx, edge_type, paths) if dctx.exchange == "needed" else (None, None)
     if edge_type.device.type == "cuda":
-        from .plan import build_graph_plans_device
-        from . import _lib
-        # exchange = "needed": x holds the rows this rank's FORWARD blocks read, so d_weight stays on the pieces' own plans
+        t_dw = _lib.dw_tiles_geometry()[0]
+        # one tile-major d_weight plan over ONE contiguous range of the rank (RankPlans.dw_rank) instead of one per piece; under
+        # exchange = "needed" x holds the rows this rank's FORWARD blocks read, so d_weight stays on the pieces' own plans
         rank_dw = dw_tiles and dctx.exchange == "full" and paths[0] != "ep"
-        extras = {}
-        pcs = build_graph_plans_device(edge_index, edge_type, n_nodes, num_relations, tile, aggr, chunk=chunk,
-                                       ranges=[(r, r) for r in ranges], split=split, dw_tiles=dw_tiles and not rank_dw, paths=paths,
-                                       rank_dw_range=dw_range(edge_index, n_nodes, dctx.world, dctx.rank, _lib.dw_tiles_geometry()[0]) if rank_dw else None,
-                                       extras=extras, hub_split=(dctx.world, dctx.rank) if dctx.split_hubs else None)
-        return RankPlans(pcs, nf, nb, extras.get("dw_rank"), extras.get("shared_fwd"), extras.get("shared_bwd"))
+        dwr = dw_range(edge_index, n_nodes, dctx.world, dctx.rank, t_dw) if rank_dw else (0, 0)
+        pb = PlanBuild(edge_index, edge_type, n_nodes, num_relations, aggr, max([1, dwr[1] - dwr[0]] + [e - b for b, e in ranges]),
+                       min(tile, t_dw) if dw_tiles else tile)
+        # hubs split across ranks: the heavy segments of an edge-parallel direction are the WHOLE graph's, their rows dealt over the
+        # ranks (eplan.SharedHeavy); the pieces' plans hold the light rows and the pseudo rows of their own segments
+        shared, builds = [None, None], [pb, pb]
+        for d in (0, 1):
+            if dctx.split_hubs and paths[d] == "ep" and pb.num_edges > 0:
+                shared[d] = build_shared_heavy(edge_index[d], edge_index[1 - d], edge_type, pb.w, n_nodes, HEAVY, dctx.world, dctx.rank)
+                if shared[d] is not None:
+                    builds[d] = pb.without(shared[d].edge_mask)
+        pcs = [range_plans(builds, r, r, tile, chunk, split, paths, dw_tiles and not rank_dw, shared) for r in ranges]
+        for gp in pcs:          # (an edge-parallel piece counts the whole graph's edges)
+            gp.num_edges = gp.fwd.n_edges if gp.fwd is not None else pb.num_edges
+        return RankPlans(pcs, nf, nb, dw_rank=pb.dw_plan(*dwr) if rank_dw else None, shared_fwd=shared[0], shared_bwd=shared[1])
     src, dst = edge_index[0].to(torch.int64), edge_index[1].to(torch.int64)
     rel = edge_type.to(torch.int64)
     w = edge_weights(src, dst, rel, num_relations, aggr)
@@ -315,7 +325,6 @@ def rank_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relation
     bg, bs, br, bw, bpiece = share(src, dst)       # transposed: edges OUT OF my blocks
     # edge-parallel directions (torch twin of the device path; tests): the pieces' eplan.EdgePlan over the whole edge list, the
     # heavy segments shared across the ranks where dctx.split_hubs
-    from .eplan import HEAVY, build_edge_plan, build_shared_heavy
     sh_f = build_shared_heavy(src, dst, rel, w, n_nodes, HEAVY, world, rank) if paths[0] == "ep" and dctx.split_hubs else None
     sh_b = build_shared_heavy(dst, src, rel, w, n_nodes, HEAVY, world, rank) if paths[1] == "ep" and dctx.split_hubs else None
     out = []

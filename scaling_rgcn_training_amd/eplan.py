@@ -23,7 +23,7 @@ The same units are a dense relation-major walk for the weight-gradient kernels (
 nothing but slots and units), where the tile-major plan's units hold a handful of rows each on such graphs.
 
 Cost: Z is written and read once (2 x rows x 4 x out bytes beside the gathers), which is why the headline graph stays on
-the tile kernels (``choose_path``).  On the GPU the arrays come from the library's own plan builder (``build_edge_plan_device``:
+the tile kernels (``choose_path``).  On the GPU the arrays come from the library's own plan builder (``plan.PlanBuild.edge_plan``:
 rgcn_plan_build_* with layout 2 -- one relation-major "tile" -- and rgcn_eplan_segments); ``build_edge_plan`` is its torch twin
 (bit-identical: tests/test_gpu_ep.py) and what the CPU-only tests walk.
 """
@@ -408,47 +408,12 @@ def build_edge_plan(gather: Tensor, scatter: Tensor, rel: Tensor, w: Tensor, n_n
 
 def build_edge_plan_device(graph, w: Tensor, transposed: bool, n_nodes: int, num_relations: int, ws: Tensor,
                            node_begin: int = 0, node_end: Optional[int] = None, piece: int = PIECE, heavy: int = 0,
-                           edge_index: Optional[Tensor] = None, edge_type: Optional[Tensor] = None,
-                           shared: Optional[SharedHeavy] = None, light_graph=None) -> EdgePlan:
-    """The same plan by the library's own builder (csrc/rgcn_plan.hip): rgcn_plan_build_begin / _finish with layout 2 lay the
-    owned range out as one relation-major "tile", rgcn_eplan_segments sorts the slots by destination; only the sum levels of
-    hubs (arithmetic on seg_ptr) and the split-off of the heavy segments (``heavy`` > 0; needs the COO tensors) stay here.
-    graph / w / ws: _lib.graph_struct, _lib.edge_weights, _lib.plan_workspace."""
-    from . import _lib
-    if node_end is None:
-        node_end = n_nodes
-    n_own = node_end - node_begin
-    hp, keep = None, None
-    if shared is not None:
-        # hubs split across ranks: the light graph (the edge list without the whole graph's heavy segments; built once per
-        # direction by the caller: light_graph = (graph struct, its weights)) and the pseudo rows of this range's segments
-        graph, w = light_graph
-        hp = shared_heavy_part(shared, n_nodes, node_begin, node_end, num_relations)
-    elif heavy > 0 and edge_index is not None and int(edge_type.shape[0]) > 0:
-        g_, s_ = (edge_index[1], edge_index[0]) if transposed else (edge_index[0], edge_index[1])
-        own = (s_ >= node_begin) & (s_ < node_end)
-        hm = heavy_mask(torch.where(own, s_, torch.full_like(s_, -1)), edge_type, n_nodes + 1, heavy)      # (-1: not owned, its own keys)
-        if hm is not None:
-            hm = hm & own
-            if bool(hm.any()):
-                hp = build_heavy_part(g_[hm], s_[hm] - node_begin, edge_type[hm], w[hm], n_own, num_relations, piece)
-                lm = ~hm
-                ei_l, et_l, w = edge_index[:, lm].contiguous(), edge_type[lm].contiguous(), w[lm].contiguous()
-                graph, keep = _lib.graph_struct(ei_l, et_l, n_nodes, num_relations)
-    ps, a, n_edges = _lib.plan_build(graph, w, transposed, node_begin, node_end, 16, UNIT, ws, 2)
-    levels, n_all, max_rows = _finish_levels(a["slot_row"], hp, n_own, piece, True)
-    n_rows = n_all - (hp.n_seg if hp is not None else 0)
-    ep = EdgePlan(n_nodes=n_nodes, node_begin=node_begin, node_end=node_end, num_relations=num_relations, n_units=int(ps.n_chunks),
-                  n_rows=n_rows, unit_rel=a["chunk_rel"], unit_cnt=a["chunk_cnt"], slot_src=a["slot_src"], slot_w=a["slot_w"],
-                  slot_row=a["slot_row"], levels=levels, max_rows_per_dst=max_rows, heavy=hp)
-    # the same arrays are the relation-major walk of the weight-gradient kernels: the struct the builder filled
-    from .plan import TilePlan
-    tp = TilePlan(n_nodes=n_nodes, node_begin=node_begin, node_end=node_end, num_relations=num_relations, tile=int(ps.tile),
-                  chunk=UNIT, n_tiles=int(ps.n_tiles), n_chunks=int(ps.n_chunks), n_edges=n_edges, slot_dstl=None, layout=2, **a)
-    tp._cstruct = ps
-    ep._tile_plan = tp
-    del keep
-    return ep
+                           edge_index: Optional[Tensor] = None, edge_type: Optional[Tensor] = None) -> EdgePlan:
+    """plan.PlanBuild.edge_plan for a caller that made ``graph`` / ``w`` / ``ws`` (_lib.graph_struct, _lib.edge_weights,
+    _lib.plan_workspace) itself; the split-off of the heavy segments (``heavy`` > 0) needs the COO tensors."""
+    from .plan import PlanBuild
+    pb = PlanBuild.adopt(graph, w, ws, n_nodes, num_relations, edge_index, edge_type)
+    return pb.edge_plan(transposed, node_begin, n_nodes if node_end is None else node_end, heavy, piece=piece)
 
 
 # ---- max aggregation (RGCNConv(aggr="max"), csrc/rgcn_segmax.hip) ------------------------------------------------------
@@ -509,27 +474,16 @@ def _max_backward(ep: EdgePlan, piece: int, on_device: bool) -> MaxPlan:
 
 
 def build_max_plan(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int, piece: int = PIECE) -> MaxPlan:
-    """The max plan of a graph: on the GPU by the library's builder (build_edge_plan_device with every segment heavy), on the
+    """The max plan of a graph: on the GPU by the library's builder (plan.PlanBuild.edge_plan with every segment heavy), on the
     CPU by its torch twin (build_edge_plan) -- identical arrays.  ValueError past EP_MAX_OWNED nodes, before anything is built."""
     if n_nodes > EP_MAX_OWNED:
         raise ValueError(f"RGCNConv(aggr='max') on {n_nodes} nodes: its edge-parallel plan holds at most EP_MAX_OWNED = 2^24 = "
                          f"{EP_MAX_OWNED} nodes, and a max layer has no other plan")
-    e = int(edge_type.shape[0])
     if edge_type.device.type == "cuda":
-        from . import _lib
-        graph, keep = _lib.graph_struct(edge_index, edge_type, n_nodes, num_relations)
-        ws = _lib.plan_workspace(e, n_nodes, num_relations, 16, edge_type.device)
-        try:
-            w = _lib.edge_weights(graph, "max", ws)
-        except _lib.RgcnLibraryError as err:
-            if "out of range" in str(err):
-                raise ValueError("edge_index / edge_type out of range [0, num_nodes) / [0, num_relations)") from err
-            raise
-        ep = build_edge_plan_device(graph, w, False, n_nodes, num_relations, ws, piece=piece, heavy=1, edge_index=edge_index,
-                                    edge_type=edge_type)
-        del keep
-        return _max_backward(ep, piece, True)
-    w = torch.ones(e, dtype=torch.float32)
+        from .plan import PlanBuild
+        pb = PlanBuild(edge_index, edge_type, n_nodes, num_relations, "max", n_nodes, 16)
+        return _max_backward(pb.edge_plan(False, 0, n_nodes, 1, piece=piece), piece, True)
+    w = torch.ones(int(edge_type.shape[0]), dtype=torch.float32)
     ep = build_edge_plan(edge_index[0], edge_index[1], edge_type, w, n_nodes, num_relations, piece=piece, heavy=1)
     return _max_backward(ep, piece, False)
 

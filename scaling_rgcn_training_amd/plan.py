@@ -41,6 +41,10 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import _lib
+from .eplan import (HEAVY, PIECE, EdgePlan, SharedHeavy, _finish_levels, build_edge_plan, build_heavy_part, check_ep_ranges,
+                    heavy_mask, resolve_paths, shared_heavy_part)
+
 CHUNK = 64  # default edge slots per chunk == rows of one LDS ring slot (csrc/rgcn_common.h kChunk)
 UNIT = 64   # rows the weight-gradient kernels walk at a time: a chunk is chunk // UNIT units
 CHUNKS = (64, 128)   # chunk sizes (slot strides) the kernels are built for
@@ -805,14 +809,12 @@ def build_graph_plans_torch(edge_index: Tensor, edge_type: Tensor, n_nodes: int,
                             split: bool = False, paths: Tuple[str, str] = ("ring", "ring")) -> GraphPlans:
     """The plans as torch tensor ops (any device): the TEST ORACLE of the device-side builder and what the CPU-only
     tests walk with tests/plan_emulator.py.  paths: 'ring' (tile-major plan) or 'ep' (eplan.EdgePlan) per direction."""
-    from .eplan import build_edge_plan, check_ep_ranges
     fb, fe = fwd_range if fwd_range is not None else (0, n_nodes)
     bb, be = bwd_range if bwd_range is not None else (0, n_nodes)
     check_ep_ranges(paths, [((fb, fe), (bb, be))])
     src, dst = edge_index[0], edge_index[1]
     w = edge_weights(src, dst, edge_type, num_relations, aggr)
     gp = GraphPlans(fwd=None, bwd=None, num_edges=int(edge_type.shape[0]))
-    from .eplan import HEAVY
     if paths[0] == "ep":
         gp.ep_fwd = build_edge_plan(src, dst, edge_type, w, n_nodes, num_relations, fb, fe, heavy=HEAVY)
     else:
@@ -835,113 +837,148 @@ def empty_plan(n_nodes: int, node_begin: int, num_relations: int, tile: int, chu
                     slot_w=z(torch.float32), slot_dstl=None, slot_row=z(), slot_acc=z(), layout=layout)
 
 
-def _device_plan(graph, w, transposed: bool, n_nodes: int, num_relations: int, tile: int, chunk: int,
-                 node_begin: int, node_end: int, ws, split: bool = False, aligned: bool = True) -> TilePlan:
-    from . import _lib
-    if node_end <= node_begin:           # nothing to lay out
-        return empty_plan(n_nodes, node_begin, num_relations, tile, chunk, ws.device, int(split))
-    if aligned and node_begin % tile != 0:       # forward / dX plans of a rank: its tiles must be the single-rank tiles
-        raise ValueError("node_begin must be a multiple of the tile size")
-    ps, a, n_edges = _lib.plan_build(graph, w, transposed, node_begin, node_end, tile, chunk, ws, split)
-    if int(split) == 5:          # the pairs left fewer units than _begin sized rel_order for
-        a["rel_order"] = a["rel_order"][:int(ps.n_units)]
-    plan = TilePlan(n_nodes=n_nodes, node_begin=node_begin, node_end=node_end, num_relations=num_relations, tile=tile,
-                    chunk=int(ps.chunk), n_tiles=int(ps.n_tiles), n_chunks=int(ps.n_chunks), n_edges=n_edges, slot_dstl=None,
-                    layout=int(split), chunk_rows=int(ps.chunk_rows), **a)
-    plan._cstruct = ps
-    return plan
+class PlanBuild:
+    """The device build session of one graph: the C struct of its edge list (``_lib.graph_struct``), the tensors that struct points
+    into, the edge weights (rgcn_edge_weights, one pass for both directions and every range) and the builder's workspace -- what
+    every plan of the graph is laid out from (csrc/rgcn_plan.hip) and what lives exactly as long as the session does.
+    ``max_owned``: the longest node range a plan will own; ``ws_tile``: the smallest tile of any plan (it sizes the group arrays)."""
+
+    def __init__(self, edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int, aggr: str, max_owned: int, ws_tile: int):
+        self._graph(edge_index, edge_type, n_nodes, num_relations)
+        self.ws = _lib.plan_workspace(self.num_edges, max_owned, num_relations, ws_tile, edge_type.device)
+        try:
+            self.w = _lib.edge_weights(self.graph, aggr, self.ws)
+        except _lib.RgcnLibraryError as err:
+            if "out of range" in str(err):
+                raise ValueError("edge_index / edge_type out of range [0, num_nodes) / [0, num_relations)") from err
+            raise
+
+    def _graph(self, edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int) -> None:
+        self.edge_index, self.edge_type, self.n_nodes, self.num_relations = edge_index, edge_type, n_nodes, num_relations
+        self.num_edges = int(edge_type.shape[0])
+        self.graph, self._owned = _lib.graph_struct(edge_index, edge_type, n_nodes, num_relations)      # (_owned: what the struct points into)
+
+    @classmethod
+    def adopt(cls, graph, w: Tensor, ws: Tensor, n_nodes: int, num_relations: int, edge_index: Optional[Tensor] = None,
+              edge_type: Optional[Tensor] = None) -> "PlanBuild":
+        """a session over a struct, weights and workspace the caller made -- and keeps alive -- itself (eplan.build_edge_plan_device);
+        without the COO tensors no heavy segment can be cut out"""
+        pb = cls.__new__(cls)
+        pb.edge_index, pb.edge_type, pb.n_nodes, pb.num_relations = edge_index, edge_type, n_nodes, num_relations
+        pb.num_edges, pb.graph, pb._owned, pb.w, pb.ws = int(graph.num_edges), graph, (), w, ws
+        return pb
+
+    def without(self, edge_mask: Tensor) -> "PlanBuild":
+        """the session of the same graph without the masked edges (the LIGHT graph once heavy segments are cut out): contiguous
+        copies of its own, the kept edges' weights, the same workspace"""
+        keep = ~edge_mask
+        pb = PlanBuild.__new__(PlanBuild)
+        pb._graph(self.edge_index[:, keep].contiguous(), self.edge_type[keep].contiguous(), self.n_nodes, self.num_relations)
+        pb.w, pb.ws = self.w[keep].contiguous(), self.ws
+        return pb
+
+    def tile_plan(self, transposed: bool, tile: int, chunk: int, begin: int, end: int, layout: int = 0, aligned: bool = True) -> TilePlan:
+        layout = int(layout)
+        if end <= begin:           # nothing to lay out
+            return empty_plan(self.n_nodes, begin, self.num_relations, tile, chunk, self.ws.device, layout)
+        if aligned and begin % tile != 0:       # forward / dX plans of a rank: its tiles must be the single-rank tiles
+            raise ValueError("node_begin must be a multiple of the tile size")
+        ps, a, n_edges = _lib.plan_build(self.graph, self.w, transposed, begin, end, tile, chunk, self.ws, layout)
+        if layout == 5:          # the pairs left fewer units than _begin sized rel_order for
+            a["rel_order"] = a["rel_order"][:int(ps.n_units)]
+        plan = TilePlan(n_nodes=self.n_nodes, node_begin=begin, node_end=end, num_relations=self.num_relations, tile=tile,
+                        chunk=int(ps.chunk), n_tiles=int(ps.n_tiles), n_chunks=int(ps.n_chunks), n_edges=n_edges, slot_dstl=None,
+                        layout=layout, chunk_rows=int(ps.chunk_rows), **a)
+        plan._cstruct = ps
+        return plan
+
+    def dw_plan(self, begin: int, end: int):
+        """(plan, walk table) of the tile-major weight-gradient kernel over the in-edges of [begin, end): its own layout of the
+        same edges (layout 5: the two rows of a (destination, relation) pair on one slot -- dw_pairs / dw_pairs_kernel; the range
+        need not be a multiple of THAT tile -- the sums of a partitioned d_weight differ in order from the single-rank ones
+        anyway).  (None, None) for an empty range (its owner adds zeros); None past the relations the kernel holds."""
+        t_dw, _, max_rel = _lib.dw_tiles_geometry()
+        if self.num_relations > max_rel:
+            return None
+        if end <= begin:
+            return None, None
+        pl = self.tile_plan(False, t_dw, 64, begin, end, DW_PLAN_LAYOUT, aligned=False)
+        return pl, _lib.dw_tiles_walk(_lib.plan_struct(pl), self.ws.device)
+
+    def edge_plan(self, transposed: bool, begin: int, end: int, heavy: int, shared: Optional[SharedHeavy] = None, piece: int = PIECE) -> EdgePlan:
+        """eplan.build_edge_plan by the library's own builder: rgcn_plan_build_begin / _finish with layout 2 lay the owned range out
+        as one relation-major "tile", rgcn_eplan_segments sorts the slots by destination; only the sum levels of hubs (arithmetic
+        on seg_ptr) and the split-off of the heavy segments stay here.  ``heavy`` > 0: this range's segments of at least that many
+        rows become its HeavyPart and leave the units.  ``shared`` (hubs split across ranks): this is the ``without`` session of
+        the whole graph's heavy segments, and the range gets the pseudo rows of its own."""
+        n_own, light, hp = end - begin, self, None
+        if shared is not None:
+            hp = shared_heavy_part(shared, self.n_nodes, begin, end, self.num_relations)
+        elif heavy > 0 and self.edge_index is not None and self.num_edges > 0:
+            g_, s_ = (self.edge_index[1], self.edge_index[0]) if transposed else (self.edge_index[0], self.edge_index[1])
+            own = (s_ >= begin) & (s_ < end)
+            hm = heavy_mask(torch.where(own, s_, torch.full_like(s_, -1)), self.edge_type, self.n_nodes + 1, heavy)      # (-1: not owned, its own keys)
+            hm = hm & own if hm is not None else None
+            if hm is not None and bool(hm.any()):
+                hp = build_heavy_part(g_[hm], s_[hm] - begin, self.edge_type[hm], self.w[hm], n_own, self.num_relations, piece)
+                light = self.without(hm)
+        ps, a, n_edges = _lib.plan_build(light.graph, light.w, transposed, begin, end, 16, UNIT, self.ws, 2)
+        levels, n_all, max_rows = _finish_levels(a["slot_row"], hp, n_own, piece, True)
+        ep = EdgePlan(n_nodes=self.n_nodes, node_begin=begin, node_end=end, num_relations=self.num_relations, n_units=int(ps.n_chunks),
+                      n_rows=n_all - (hp.n_seg if hp is not None else 0), unit_rel=a["chunk_rel"], unit_cnt=a["chunk_cnt"],
+                      slot_src=a["slot_src"], slot_w=a["slot_w"], slot_row=a["slot_row"], levels=levels, max_rows_per_dst=max_rows, heavy=hp)
+        # the same arrays are the relation-major walk of the weight-gradient kernels: the struct the builder filled
+        ep._tile_plan = TilePlan(n_nodes=self.n_nodes, node_begin=begin, node_end=end, num_relations=self.num_relations, tile=int(ps.tile),
+                                 chunk=UNIT, n_tiles=int(ps.n_tiles), n_chunks=int(ps.n_chunks), n_edges=n_edges, slot_dstl=None, layout=2, **a)
+        ep._tile_plan._cstruct = ps
+        return ep
+
+
+def range_plans(builds, fwd_range: Tuple[int, int], bwd_range: Tuple[int, int], tile: int, chunk: int, split, paths: Tuple[str, str],
+                dw_tiles: bool = False, shared=(None, None)) -> GraphPlans:
+    """The GraphPlans of one (forward range, dX range) pair.  ``builds``: the PlanBuild per direction -- one session twice, or
+    (dist.py, hubs split across ranks) the ``without`` session of a direction whose heavy segments are ``shared[d]``."""
+    if chunk not in CHUNKS and chunk != CHUNK_112:
+        raise ValueError(f"chunk must be one of {CHUNKS} (or {CHUNK_112})")
+    pb, (fb, fe), (bb, be) = builds[0], fwd_range, bwd_range
+    if fe <= fb or be <= bb:       # an empty block of a rank (dist.py)
+        return GraphPlans(fwd=empty_plan(pb.n_nodes, fb, pb.num_relations, tile, chunk, pb.ws.device, int(split)),
+                          bwd=empty_plan(pb.n_nodes, bb, pb.num_relations, tile, chunk, pb.ws.device, int(split)), num_edges=0)
+    gp = GraphPlans(fwd=None, bwd=None, num_edges=pb.num_edges)
+    if paths[0] == "ep":       # edge-parallel direction: relation-major units + destination-major segments (eplan.py)
+        gp.ep_fwd = builds[0].edge_plan(False, fb, fe, HEAVY, shared[0])
+    else:
+        gp.fwd = pb.tile_plan(False, tile, chunk, fb, fe, split)
+    if paths[1] == "ep":
+        gp.ep_bwd = builds[1].edge_plan(True, bb, be, HEAVY, shared[1])
+    else:
+        gp.bwd = builds[1].tile_plan(True, tile, chunk, bb, be, split)
+    dw = pb.dw_plan(fb, fe) if dw_tiles and paths[0] != "ep" else None
+    if dw is not None:
+        gp.dw, gp.dw_walk = dw
+    return gp
 
 
 def build_graph_plans_device(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_relations: int, tile: int,
                              aggr: str = "mean", fwd_range: Optional[Tuple[int, int]] = None,
                              bwd_range: Optional[Tuple[int, int]] = None, chunk: int = CHUNK,
                              ranges=None, split: bool = False, dw_tiles: bool = False,
-                             paths: Tuple[str, str] = ("ring", "ring"), rank_dw_range: Optional[Tuple[int, int]] = None,
-                             extras: Optional[dict] = None, hub_split: Optional[Tuple[int, int]] = None):
+                             paths: Tuple[str, str] = ("ring", "ring")):
     """The plans built by the HIP library itself (csrc/rgcn_plan.hip through rgcn_edge_weights / rgcn_plan_build_*):
-    what every GPU forward uses.  ``ranges``: a list of (begin, end) owned ranges -> a list of GraphPlans that share one
-    edge-weight pass and one workspace (dist.py: one pair of plans per owned block).  ``rank_dw_range`` (dist.py, full exchange):
-    ONE tile-major weight-gradient plan over that contiguous node range besides the pieces' forward / transposed plans, returned
-    in ``extras["dw_rank"] = (plan, walk table)`` -- both operands of d_weight are replicated, so its cut need not be the
-    forward's and one launch per rank replaces one per piece.  ``hub_split = (world, rank)`` (dist.py): the heavy segments of an
-    edge-parallel direction are the WHOLE graph's, their rows dealt over the ranks (eplan.SharedHeavy, returned in
-    ``extras["shared_fwd"]`` / ``["shared_bwd"]``); the pieces' plans hold the light rows and the pseudo rows of their own segments."""
-    from . import _lib
-    from .eplan import check_ep_ranges
-    if chunk not in CHUNKS and chunk != CHUNK_112:
-        raise ValueError(f"chunk must be one of {CHUNKS} (or {CHUNK_112})")
+    what every GPU forward uses.  ``ranges``: a list of (forward range, dX range) pairs -> a list of GraphPlans laid out from one
+    PlanBuild (one edge-weight pass, one workspace), each counting the edges of its own forward plan."""
     rs = ranges if ranges is not None else [(fwd_range or (0, n_nodes), bwd_range or (0, n_nodes))]
     check_ep_ranges(paths, rs)
-    graph, keep = _lib.graph_struct(edge_index, edge_type, n_nodes, num_relations)
-    e = int(edge_type.shape[0])
-    own_max = max([1] + [max(f[1] - f[0], b[1] - b[0]) for f, b in rs] + ([rank_dw_range[1] - rank_dw_range[0]] if rank_dw_range else []))
-    ws_tile = min(tile, _lib.dw_tiles_geometry()[0]) if dw_tiles else tile      # the smallest tile sizes the group arrays
-    ws = _lib.plan_workspace(e, own_max, num_relations, ws_tile, edge_type.device)
-    try:
-        w = _lib.edge_weights(graph, aggr, ws)
-    except _lib.RgcnLibraryError as err:
-        if "out of range" in str(err):
-            raise ValueError("edge_index / edge_type out of range [0, num_nodes) / [0, num_relations)") from err
-        raise
-    from .eplan import HEAVY
-    heavy = HEAVY
-    shared, light, keep_light = [None, None], [None, None], []
-    if hub_split is not None and e > 0:
-        from .eplan import build_shared_heavy
-        for d in (0, 1):
-            if paths[d] != "ep":
-                continue
-            g_, s_ = (edge_index[1], edge_index[0]) if d else (edge_index[0], edge_index[1])
-            sh = build_shared_heavy(g_, s_, edge_type, w, n_nodes, heavy, hub_split[0], hub_split[1])
-            if sh is None:
-                continue
-            lm = ~sh.edge_mask
-            ei_l, et_l, w_l = edge_index[:, lm].contiguous(), edge_type[lm].contiguous(), w[lm].contiguous()
-            g_l, k_l = _lib.graph_struct(ei_l, et_l, n_nodes, num_relations)
-            keep_light.append((k_l, ei_l, et_l))
-            shared[d], light[d] = sh, (g_l, w_l)
-        if extras is not None:
-            extras["shared_fwd"], extras["shared_bwd"] = shared
-    out = []
-    for (fb, fe), (bb, be) in rs:
-        gp = GraphPlans(fwd=None, bwd=None, num_edges=e)
-        if fe <= fb or be <= bb:       # an empty block of a rank (dist.py)
-            out.append(GraphPlans(fwd=empty_plan(n_nodes, fb, num_relations, tile, chunk, ws.device, int(split)),
-                                  bwd=empty_plan(n_nodes, bb, num_relations, tile, chunk, ws.device, int(split)), num_edges=0))
-            continue
-        if paths[0] == "ep":       # edge-parallel direction: relation-major units + destination-major segments (eplan.py)
-            from .eplan import build_edge_plan_device
-            gp.ep_fwd = build_edge_plan_device(graph, w, False, n_nodes, num_relations, ws, fb, fe, heavy=heavy,
-                                               edge_index=edge_index, edge_type=edge_type, shared=shared[0], light_graph=light[0])
-        else:
-            gp.fwd = _device_plan(graph, w, False, n_nodes, num_relations, tile, chunk, fb, fe, ws, split)
-            if ranges is not None:
-                gp.num_edges = gp.fwd.n_edges
-        if paths[1] == "ep":
-            from .eplan import build_edge_plan_device
-            gp.ep_bwd = build_edge_plan_device(graph, w, True, n_nodes, num_relations, ws, bb, be, heavy=heavy,
-                                               edge_index=edge_index, edge_type=edge_type, shared=shared[1], light_graph=light[1])
-        else:
-            gp.bwd = _device_plan(graph, w, True, n_nodes, num_relations, tile, chunk, bb, be, ws, split)
-        if dw_tiles and paths[0] != "ep" and fe > fb:
-            # the tile-major weight-gradient kernel's own layout of the same edges (a rank's piece: its node range need not
-            # be a multiple of THAT tile -- the sums of a partitioned d_weight differ in order from the single-rank ones anyway)
-            t_dw, walkers, max_rel = _lib.dw_tiles_geometry()
-            if num_relations <= max_rel:
-                # (layout 5: the two rows of a (destination, relation) pair on one slot -- dw_pairs / dw_pairs_kernel)
-                gp.dw = _device_plan(graph, w, False, n_nodes, num_relations, t_dw, 64, fb, fe, ws, DW_PLAN_LAYOUT, aligned=False)
-                gp.dw_walk = _lib.dw_tiles_walk(_lib.plan_struct(gp.dw), edge_type.device)
-        out.append(gp)
-    if rank_dw_range is not None and extras is not None and paths[0] != "ep":
-        t_dw, walkers, max_rel = _lib.dw_tiles_geometry()
-        if num_relations <= max_rel:
-            if rank_dw_range[1] > rank_dw_range[0]:
-                pl = _device_plan(graph, w, False, n_nodes, num_relations, t_dw, 64, rank_dw_range[0], rank_dw_range[1], ws, DW_PLAN_LAYOUT, aligned=False)
-                extras["dw_rank"] = (pl, _lib.dw_tiles_walk(_lib.plan_struct(pl), edge_type.device))
-            else:
-                extras["dw_rank"] = (None, None)      # an empty range (fewer tiles than ranks): this rank adds zeros
-    del keep, keep_light
-    return out if ranges is not None else out[0]
+    own_max = max([1] + [max(f[1] - f[0], b[1] - b[0]) for f, b in rs])
+    ws_tile = min(tile, _lib.dw_tiles_geometry()[0]) if dw_tiles else tile
+    pb = PlanBuild(edge_index, edge_type, n_nodes, num_relations, aggr, own_max, ws_tile)
+    out = [range_plans((pb, pb), f, b, tile, chunk, split, paths, dw_tiles) for f, b in rs]
+    if ranges is None:
+        return out[0]
+    for gp in out:
+        if gp.fwd is not None:
+            gp.num_edges = gp.fwd.n_edges
+    return out
 
 
 def dw_walk_table(plan: TilePlan, walkers: int) -> Tensor:
@@ -1007,7 +1044,6 @@ def cached_graph_plans(edge_index: Tensor, edge_type: Tensor, n_nodes: int, num_
     if hit is not None:
         _CACHE[key] = hit           # most recently used last
         return hit[0]
-    from .eplan import resolve_paths
     paths = resolve_paths(paths, edge_index, n_nodes, num_relations, widths, tile, chunk)
     if builder is None:
         plans = build_graph_plans(edge_index, edge_type, n_nodes, num_relations, tile, aggr, chunk=chunk, split=split,
