@@ -69,8 +69,10 @@ enum rgcn_status {
     RGCN_ERR_GRAPH = -9,     /* rgcn_plan_build, rgcn_sample_*, rgcn_mb_index_build: an edge_index / edge_type value is out of range */
     RGCN_ERR_ADDRESS = -10,  /* rgcn_bwd_dw_tiles: a gathered matrix cannot be addressed through a buffer descriptor (2^24 rows or
                               * 4 GiB and more): use rgcn_bwd_dw, whose kernels fall back to 64-bit pointers */
-    RGCN_ERR_ARG = -11       /* rgcn_sample_*: a scalar argument outside its domain (fan-out, seed, hop, number of destinations),
+    RGCN_ERR_ARG = -11,      /* rgcn_sample_*: a scalar argument outside its domain (fan-out, seed, hop, number of destinations),
                               * or a destination listed twice */
+    RGCN_ERR_COLLISION = -12 /* rgcn_nt_build: two different terms share their hash_bits hash bits: nothing was merged; call again
+                              * with more bits or another seed */
 };
 
 /* Graph plan in HBM, built once per graph (scaling_rgcn_training_amd/plan.py documents the layout;
@@ -754,6 +756,51 @@ int rgcn_tr_block_labels(const int64_t* block, int64_t num_nodes, int64_t num_bl
 int rgcn_tr_gather(const float* const* tables, const int32_t* lds, const int64_t* rows, const int64_t* const* maps, int num_tables,
                    int width, int64_t num_nodes, const int64_t* nodes, int64_t n_out, int mode, int64_t seed, float* out,
                    int64_t ld_out, int64_t plane_stride, int32_t* bad, void* stream);
+
+/* ---- N-Triples ingest: file bytes -> COO tensors and term tables (csrc/rgcn_ingest.hip) -------------------------
+ * Additions; RGCN_ABI_VERSION stays.  The contract is graphs.py's: lines end at '\n' (one '\r' before it is dropped, the last line
+ * need not end in '\n'); a line of at most 2 bytes is skipped; every other line loses its last 2 bytes and splits at its first two
+ * spaces into subject, predicate, object (the object keeps further spaces; a term may be empty); 'A'..'Z' are folded to lower case
+ * wherever bytes are compared.  Terms are ordered bytewise.  Node ids are the ranks among the terms that occur as subject or
+ * object, relation ids the ranks among the predicates other than "<http://www.w3.org/1999/02/22-rdf-syntax-ns#type>" and "<type>",
+ * class ids the ranks among the objects of the rdf-syntax type triples whose subject's bytes up to its first '#' are not
+ * "http://swrc.ontoware.org/ontology".  The i-th other triple, in file order, is edge 2 i = (s, o, 2 rel) and edge 2 i + 1 =
+ * (o, s, 2 rel + 1).  The subjects of the class triples are the labelled nodes; labels[j][c] = 1 iff labelled_idx[j] has class c.
+ *
+ * `text` is a device pointer to num_bytes <= 0xFFFF0000 bytes (RGCN_ERR_PLAN beyond; offsets are 32-bit); at most 0x55550000
+ * triples.  Four calls, each on `stream`, each with a caller-owned workspace; the library allocates nothing.  A call SYNCHRONISES
+ * the stream only for the read-backs named below, into the host pointers given.  Argument errors (RGCN_ERR_NULL, _ARG, _PLAN,
+ * _WORKSPACE, in this order of checks) are answered before any launch; the size queries answer 0 on arguments the call refuses and
+ * multiples of 256 otherwise.
+ *
+ *   rgcn_nt_lines      *num_lines = lines of the text (one read-back).
+ *   rgcn_nt_tokenize   num_lines as rgcn_nt_lines answered (another count: RGCN_ERR_ARG).  Occurrence 3 t + role (role 0 / 1 / 2:
+ *                      subject / predicate / object of the t-th triple, in file order) -> occ_off / occ_len [3 num_lines entries
+ *                      each, the first 3 T written].  One read-back into info[4] (host): T, the 1-based number of the first line
+ *                      with fewer than two spaces after the cut (0: none), that of the first line with a NUL byte (0: none), the
+ *                      longest term.  RGCN_ERR_GRAPH when either line number is set; occ_off / occ_len are then unspecified.
+ *   rgcn_nt_build      distinct terms by a hash_bits-bit hash (1 .. 64, else RGCN_ERR_ARG; seed >= 0) and a stable sort; EVERY
+ *                      occurrence is then compared, length and bytes, with the first of its run: a difference answers
+ *                      RGCN_ERR_COLLISION, and no id ever depends on the hash.  Bytewise ranks by refinement rounds over 4 bytes a
+ *                      round (one read-back per round), roles, ids.  counts[8] (host): U distinct terms, N nodes, R relations (the
+ *                      COO has 2 R edge types), C classes, E edges, L labelled nodes, the device status word, rounds.
+ *                      max_term_len as rgcn_nt_tokenize answered; occ pairs that leave the text: RGCN_ERR_GRAPH.
+ *   rgcn_nt_emit       the same workspace, untouched since rgcn_nt_build answered RGCN_OK, and that call's counts: edge_index
+ *                      int64 [2][E], edge_type [E], labelled_idx [L] ascending, labels [L][C], and (offset, length) into the text of
+ *                      one occurrence of every node / relation / class, in id order.  Asynchronous, no read-back.  Counts that
+ *                      do not fit num_triples: RGCN_ERR_ARG; nothing is ever written outside the sizes the counts give. */
+size_t rgcn_nt_lines_workspace_bytes(int64_t num_bytes);
+int rgcn_nt_lines(const uint8_t* text, int64_t num_bytes, void* workspace, size_t workspace_bytes, int64_t* num_lines, void* stream);
+size_t rgcn_nt_tokenize_workspace_bytes(int64_t num_bytes, int64_t num_lines);
+int rgcn_nt_tokenize(const uint8_t* text, int64_t num_bytes, int64_t num_lines, uint32_t* occ_off, uint32_t* occ_len, void* workspace,
+                     size_t workspace_bytes, int64_t* info, void* stream);
+size_t rgcn_nt_workspace_bytes(int64_t num_triples);
+int rgcn_nt_build(const uint8_t* text, int64_t num_bytes, const uint32_t* occ_off, const uint32_t* occ_len, int64_t num_triples,
+                  int64_t max_term_len, int hash_bits, int64_t seed, void* workspace, size_t workspace_bytes, int64_t* counts,
+                  void* stream);
+int rgcn_nt_emit(int64_t num_triples, const int64_t* counts, int64_t* edge_index, int64_t* edge_type, int64_t* labelled_idx,
+                 int64_t* labels, uint32_t* node_off, uint32_t* node_len, uint32_t* rel_off, uint32_t* rel_len, uint32_t* cls_off,
+                 uint32_t* cls_len, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,8 @@ Sub-modules:
 * ``transfer`` -- summaries -> original graph on tensors: ``summary_labels`` (the fractional labels of a partition's blocks),
   ``TransferredEmbedding`` and the ``stack`` / ``concat`` / ``sum_embeddings`` tricks ``Trainer.train_original`` takes
 * ``tensor_data`` -- ``TensorDataset`` / ``TensorGraph``: the dataset ``Trainer`` reads, for a graph that has no node names
+* ``ingest`` -- ``load_nt``: an N-Triples file -> COO tensors, labels and ``TermTable`` name tables on the GPU (``NTGraph``), with
+  ``graphs.py``'s contract and no per-line Python
 
 There is no CPU compute path: the layer raises if the HIP library or a GPU is missing.
 """
@@ -59,6 +61,9 @@ def __getattr__(name):
     if name in ("TensorDataset", "TensorGraph"):
         from . import tensor_data
         return getattr(tensor_data, name)
+    if name in ("load_nt", "NTGraph", "TermTable"):
+        from . import ingest
+        return getattr(ingest, name)
     if name in ("TransferredEmbedding", "summary_labels"):
         from . import transfer
         return getattr(transfer, name)

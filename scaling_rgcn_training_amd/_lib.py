@@ -159,6 +159,13 @@ def _prototypes() -> dict:
         "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
+        "rgcn_nt_lines_workspace_bytes": (sz, [i64]),
+        "rgcn_nt_lines": (i32, [vp, i64, vp, sz, C.POINTER(C.c_int64), vp]),
+        "rgcn_nt_tokenize_workspace_bytes": (sz, [i64, i64]),
+        "rgcn_nt_tokenize": (i32, [vp, i64, i64, vp, vp, vp, sz, C.POINTER(C.c_int64), vp]),
+        "rgcn_nt_workspace_bytes": (sz, [i64]),
+        "rgcn_nt_build": (i32, [vp, i64, vp, vp, i64, i64, i32, i64, vp, sz, C.POINTER(C.c_int64), vp]),
+        "rgcn_nt_emit": (i32, [i64, C.POINTER(C.c_int64), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     }
 
 

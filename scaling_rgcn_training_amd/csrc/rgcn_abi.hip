@@ -197,6 +197,7 @@ extern "C" const char* rgcn_status_string(int status) {
         case RGCN_ERR_GRAPH: return "edge_index / edge_type value out of range";
         case RGCN_ERR_ADDRESS: return "matrix not addressable through a buffer descriptor (2^24 rows or 4 GiB and more)";
         case RGCN_ERR_ARG: return "argument outside its domain (fan-out, seed, hop, number of destinations, or a destination listed twice)";
+        case RGCN_ERR_COLLISION: return "two different terms share their hash bits: retry with more bits or another seed";
     }
     if (status > 0) return hipGetErrorString((hipError_t)status);
     return "unknown status";
