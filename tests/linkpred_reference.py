@@ -39,6 +39,37 @@ def corrupt(s, r, o, num_nodes: int, num_negatives: int, seed: int):
     return so, ro, oo
 
 
+def corrupt_at(s, r, o, num_nodes: int, num_negatives: int, seed: int, positions):
+    """(s', r', o') of ``corrupt`` at the given output positions only: a batch too long for the Python-integer loop is checked at
+    chosen places"""
+    s, r, o = (np.asarray(a, dtype=np.int64) for a in (s, r, o))
+    positions = np.asarray(positions, dtype=np.int64)
+    so, ro, oo = (np.empty(len(positions), np.int64) for _ in range(3))
+    for n, p in enumerate(positions.tolist()):
+        i, j = divmod(p, num_negatives)
+        node, obj = draw(seed, i, j, num_nodes)
+        so[n], ro[n], oo[n] = (s[i], r[i], node) if obj else (node, r[i], o[i])
+    return so, ro, oo
+
+
+def triple_index(s, r, o, num_nodes: int, num_relations: int):
+    """What rgcn_lp_index_build must give, by stable argsorts: a dict of ``node_ptr [N + 1]``, ``node_slot`` (the slots 2 t + side of
+    the valid triples in (node, slot) order), ``bad_slots`` (the sorted slots of the other triples: the tail of the device's
+    node_slot, in any order), ``rel_ptr [R + 1]``, ``rel_triple``, ``bad_triples`` and the ``bad`` word"""
+    s, r, o = (np.asarray(a, dtype=np.int64) for a in (s, r, o))
+    ok, bad = valid_triples(s, r, o, num_nodes, num_relations)
+    slot_node = np.stack([s, o], 1).reshape(-1)                     # slot 2 t + side
+    slot_ok = np.repeat(ok, 2)
+    slots = np.flatnonzero(slot_ok)
+    order = np.argsort(slot_node[slots], kind="stable")
+    triples = np.flatnonzero(ok)
+    t_order = np.argsort(r[triples], kind="stable")
+    return {"node_ptr": np.searchsorted(slot_node[slots][order], np.arange(num_nodes + 1)).astype(np.int64),
+            "node_slot": slots[order].astype(np.int64), "bad_slots": np.flatnonzero(~slot_ok).astype(np.int64),
+            "rel_ptr": np.searchsorted(r[triples][t_order], np.arange(num_relations + 1)).astype(np.int64),
+            "rel_triple": triples[t_order].astype(np.int64), "bad_triples": np.flatnonzero(~ok).astype(np.int64), "bad": bad}
+
+
 def valid_triples(s, r, o, num_nodes: int, num_relations: int):
     """(mask of the triples whose ids are all in range, the `bad` word the others set)"""
     s, r, o = (np.asarray(a, dtype=np.int64) for a in (s, r, o))

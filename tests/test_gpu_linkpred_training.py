@@ -43,7 +43,7 @@ def _setup(seed=0):
     return data, train, held, model, decoder
 
 
-def _gpu_run(data, train, held, model, decoder):
+def _gpu_run(data, train, held, model, decoder, epochs=EPOCHS, neg=NEG, batch_size=None):
     from scaling_rgcn_training_amd.trainer import Trainer
 
     class Recording(Trainer):
@@ -57,23 +57,16 @@ def _gpu_run(data, train, held, model, decoder):
             self.counts.append(tuple(t.cpu().numpy() for t in out))
             return out
 
-    t = Recording(None, DIM, EPOCHS, DIM, 0.01, 0.0, verbose=False, hipgraph=False)
+    t = Recording(None, DIM, epochs, DIM, 0.01, 0.0, verbose=False, hipgraph=False)
     t.negatives, t.counts = [], []
-    losses, mrrs = t.train_link_prediction(copy.deepcopy(model), copy.deepcopy(decoder), data, train, held, num_negatives=NEG, seed=3)
+    losses, mrrs = t.train_link_prediction(copy.deepcopy(model), copy.deepcopy(decoder), data, train, held, num_negatives=neg,
+                                           batch_size=batch_size, seed=3)
     return losses, mrrs, t.negatives, t.counts
 
 
-def test_loss_curve_and_filtered_mrr_match_the_cpu_twin():
+def _twin_run(data, train, held, model, decoder, negatives, epochs=EPOCHS, neg=NEG, batch_size=None):
+    """(losses, mrrs, bands) of the CPU twin fed the negatives the GPU run drew"""
     from scaling_rgcn_training_amd.trainer import Trainer
-    data, train, held, model, decoder = _setup()
-    losses, mrrs, negatives, counts = _gpu_run(data, train, held, model, decoder)
-    assert len(losses) == EPOCHS and len(mrrs) == EPOCHS and len(negatives) == EPOCHS and len(counts) == 2 * EPOCHS
-    # the negatives are the restatement's, step by step
-    s, r, o = (train[:, c].numpy() for c in range(3))
-    for epoch in (0, EPOCHS - 1):
-        step_seed = (3 * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03) % (2 ** 63)
-        for got, ref in zip(negatives[epoch], R.corrupt(s, r, o, N, NEG, step_seed)):
-            assert np.array_equal(got.numpy(), ref)
 
     class Twin(Trainer):
         device = torch.device("cpu")
@@ -92,15 +85,32 @@ def test_loss_curve_and_filtered_mrr_match_the_cpu_twin():
             self.bands.append(R.rank_band(zn, rn, anchor.numpy(), r.numpy(), target.numpy(), lists))
             return torch.as_tensor(g), torch.as_tensor(e)
 
-    twin = Twin(None, DIM, EPOCHS, DIM, 0.01, 0.0, verbose=False, hipgraph=False)
+    twin = Twin(None, DIM, epochs, DIM, 0.01, 0.0, verbose=False, hipgraph=False)
     twin.replay, twin.bands = list(negatives), []
-    t_losses, t_mrrs = twin.train_link_prediction(cpu_twin(model), TorchDistMult(decoder.rel), data, train, held, num_negatives=NEG, seed=3)
+    t_losses, t_mrrs = twin.train_link_prediction(cpu_twin(model), TorchDistMult(decoder.rel), data, train, held, num_negatives=neg,
+                                                  batch_size=batch_size, seed=3)
+    assert not twin.replay
+    return t_losses, t_mrrs, twin.bands
+
+
+def test_loss_curve_and_filtered_mrr_match_the_cpu_twin():
+    data, train, held, model, decoder = _setup()
+    losses, mrrs, negatives, counts = _gpu_run(data, train, held, model, decoder)
+    assert len(losses) == EPOCHS and len(mrrs) == EPOCHS and len(negatives) == EPOCHS and len(counts) == 2 * EPOCHS
+    # the negatives are the restatement's, step by step
+    s, r, o = (train[:, c].numpy() for c in range(3))
+    for epoch in (0, EPOCHS - 1):
+        step_seed = (3 * 0x9E3779B97F4A7C15 + epoch * 0xD1B54A32D192ED03) % (2 ** 63)
+        for got, ref in zip(negatives[epoch], R.corrupt(s, r, o, N, NEG, step_seed)):
+            assert np.array_equal(got.numpy(), ref)
+
+    t_losses, t_mrrs, bands = _twin_run(data, train, held, model, decoder, negatives)
     print("link prediction losses  gpu", [f"{v:.6f}" for v in losses])
     print("link prediction losses twin", [f"{v:.6f}" for v in t_losses])
     print("filtered MRR  gpu", [f"{v:.6f}" for v in mrrs])
     print("filtered MRR twin", [f"{v:.6f}" for v in t_mrrs])
-    outside = sum(int(((g < lo) | (g > hi)).sum()) for (g, _), (lo, hi) in zip(counts, twin.bands))
-    open_ = sum(int((lo != hi).sum()) for lo, hi in twin.bands)
+    outside = sum(int(((g < lo) | (g > hi)).sum()) for (g, _), (lo, hi) in zip(counts, bands))
+    open_ = sum(int((lo != hi).sum()) for lo, hi in bands)
     print(f"rank counts outside the twin's float64 band: {outside} of {2 * EPOCHS * HELD}; open bands: {open_}")
     assert losses[-1] < losses[0]
     np.testing.assert_allclose(losses, t_losses, rtol=2e-4, atol=2e-5)
@@ -108,8 +118,8 @@ def test_loss_curve_and_filtered_mrr_match_the_cpu_twin():
     for epoch in range(EPOCHS):
         g = np.concatenate([counts[2 * epoch][0], counts[2 * epoch + 1][0]])
         e = np.concatenate([counts[2 * epoch][1], counts[2 * epoch + 1][1]])
-        lo = np.concatenate([twin.bands[2 * epoch][0], twin.bands[2 * epoch + 1][0]])
-        hi = np.concatenate([twin.bands[2 * epoch][1], twin.bands[2 * epoch + 1][1]])
+        lo = np.concatenate([bands[2 * epoch][0], bands[2 * epoch + 1][0]])
+        hi = np.concatenate([bands[2 * epoch][1], bands[2 * epoch + 1][1]])
         assert ((g >= lo) & (g <= hi)).all(), f"epoch {epoch}: a rank count outside the float64 band"
         assert mrrs[epoch] == pytest.approx(R.metrics(g, e)["mrr"], abs=1e-12)
         if (lo == hi).all() and not e.any():
@@ -123,3 +133,51 @@ def test_a_second_run_reproduces_the_losses_bit_for_bit():
     assert a[0] == b[0] and a[1] == b[1]
     for x, y in zip(a[2], b[2]):
         assert all(torch.equal(p, q) for p, q in zip(x, y))
+
+
+def test_mini_batches_match_the_cpu_twin_and_repeat():
+    """``batch_size=300``: 7 batches per epoch from one seeded permutation, the last of 200 triples; 5 epochs, 3 negatives each, on
+    the graph of the full-batch test.  The bands are the twin's: they bound the rounding of a fp32 ranking pass over the TWIN's
+    parameters, so they hold only while the two runs' parameters agree to fp32 rounding (max |z - z_twin| stays near 7e-7 here).
+    That is a property of the graph and the initial weights, not of the kernels: Adam's first step is lr g / (|g| + 1e-8), and
+    where an element's first gradient lies within the rounding of the two gradient computations (|g| < 1e-7 against a largest
+    |g_gpu - g_twin| of 9e-8) the two runs step apart.  On another initialisation (``_setup(seed=2)``) one element of
+    ``rgcn2.weight`` did: 6e-5 apart after step 0, z 2e-4 apart after step 1, and 5 of 400 counts one off a closed band of the
+    twin while every count lay inside the band of the GPU run's own parameters."""
+    from scaling_rgcn_training_amd.trainer import _step_seed
+    epochs, neg, batch, seed = 5, 3, 300, 3
+    data, train, held, model, decoder = _setup()
+    run = lambda: _gpu_run(data, train, held, model, decoder, epochs=epochs, neg=neg, batch_size=batch)
+    losses, mrrs, negatives, counts = run()
+    assert len(losses) == epochs and len(mrrs) == epochs and len(negatives) == 7 * epochs and len(counts) == 2 * epochs
+    # the negatives of (epoch, batch): the restatement's at that step's seed, on the batch rows of the seeded permutation
+    perm_gen = torch.Generator().manual_seed(seed)
+    for epoch in range(epochs):
+        perm = torch.randperm(E, generator=perm_gen)
+        for b in range(7):
+            rows = perm[b * batch:(b + 1) * batch]
+            assert len(rows) == (200 if b == 6 else batch)
+            s, r, o = (train[rows, c].numpy() for c in range(3))
+            for got, ref in zip(negatives[7 * epoch + b], R.corrupt(s, r, o, N, neg, _step_seed(seed, epoch, b))):
+                assert np.array_equal(got.numpy(), ref), (epoch, b)
+    t_losses, t_mrrs, bands = _twin_run(data, train, held, model, decoder, negatives, epochs=epochs, neg=neg, batch_size=batch)
+    print("mini-batch link prediction losses  gpu", [f"{v:.6f}" for v in losses])
+    print("mini-batch link prediction losses twin", [f"{v:.6f}" for v in t_losses])
+    outside = sum(int(((g < lo) | (g > hi)).sum()) for (g, _), (lo, hi) in zip(counts, bands))
+    print(f"mini-batch rank counts outside the twin's float64 band: {outside} of {2 * epochs * HELD}; open bands: "
+          f"{sum(int((lo != hi).sum()) for lo, hi in bands)}")
+    assert losses[-1] < losses[0]
+    np.testing.assert_allclose(losses, t_losses, rtol=2e-4, atol=2e-5)
+    for (g, e), (lo, hi) in zip(counts, bands):
+        assert ((g >= lo) & (g <= hi)).all(), "a rank count outside the float64 band"
+    for epoch in range(epochs):
+        g = np.concatenate([counts[2 * epoch][0], counts[2 * epoch + 1][0]])
+        e = np.concatenate([counts[2 * epoch][1], counts[2 * epoch + 1][1]])
+        assert mrrs[epoch] == pytest.approx(R.metrics(g, e)["mrr"], abs=1e-12)
+    # a second run: the same bits
+    again = run()
+    assert again[0] == losses and again[1] == mrrs
+    for x, y in zip(again[2], negatives):
+        assert all(torch.equal(p, q) for p, q in zip(x, y))
+    for x, y in zip(again[3], counts):
+        assert all(np.array_equal(p, q) for p, q in zip(x, y))

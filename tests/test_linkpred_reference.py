@@ -72,6 +72,46 @@ def test_corrupt_properties():
     assert all(R.draw(5, i, 0, 2)[0] == (R.draw(5, i, 0, 2 ** 31 - 1)[0] >> 30) for i in range(50))
 
 
+def test_corrupt_at_is_corrupt_at_those_positions():
+    g = torch.Generator().manual_seed(4)
+    n, k, n_nodes = 60, 7, 1000
+    s, o = (torch.randint(0, n_nodes, (n,), generator=g).numpy() for _ in range(2))
+    r = torch.randint(0, 5, (n,), generator=g).numpy()
+    full = R.corrupt(s, r, o, n_nodes, k, seed=2 ** 63 - 1)
+    pos = np.array([0, 1, 6, 7, 8, 13, 14, 200, n * k - 1, 200])       # both ends, around multiples of k, one position twice
+    for a, b in zip(R.corrupt_at(s, r, o, n_nodes, k, 2 ** 63 - 1, pos), full):
+        assert np.array_equal(a, b[pos])
+    every = R.corrupt_at(s, r, o, n_nodes, k, 2 ** 63 - 1, np.arange(n * k))
+    assert all(np.array_equal(a, b) for a, b in zip(every, full))
+
+
+def test_triple_index_against_buckets():
+    """the argsort formulation against plain buckets filled in position order"""
+    g = torch.Generator().manual_seed(6)
+    n_nodes, n_rel, n = 300, 270, 500
+    s, o = (torch.randint(0, n_nodes, (n,), generator=g).numpy() for _ in range(2))
+    r = torch.randint(0, n_rel, (n,), generator=g).numpy()
+    s[3], o[4], r[5], s[6], r[7] = n_nodes, 2 ** 40, n_rel, -1, -7
+    s[8], r[8] = n_nodes + 1, n_rel + 1
+    s[9], o[9] = 0, n_nodes - 1
+    ix = R.triple_index(s, r, o, n_nodes, n_rel)
+    node, rel, bad_slots, bad_triples = [[] for _ in range(n_nodes)], [[] for _ in range(n_rel)], [], []
+    for t in range(n):
+        if 0 <= s[t] < n_nodes and 0 <= o[t] < n_nodes and 0 <= r[t] < n_rel:
+            node[s[t]].append(2 * t)
+            node[o[t]].append(2 * t + 1)
+            rel[r[t]].append(t)
+        else:
+            bad_slots += [2 * t, 2 * t + 1]
+            bad_triples.append(t)
+    assert bad_triples == [3, 4, 5, 6, 7, 8] and ix["bad"] == R.BAD_NODE | R.BAD_REL
+    assert ix["node_slot"].tolist() == [x for b in node for x in b] and ix["rel_triple"].tolist() == [x for b in rel for x in b]
+    assert ix["node_ptr"].tolist() == np.concatenate([[0], np.cumsum([len(b) for b in node])]).tolist()
+    assert ix["rel_ptr"].tolist() == np.concatenate([[0], np.cumsum([len(b) for b in rel])]).tolist()
+    assert ix["bad_slots"].tolist() == bad_slots and ix["bad_triples"].tolist() == bad_triples
+    assert ix["node_ptr"][-1] == 2 * (n - 6) and ix["rel_ptr"][-1] == n - 6
+
+
 def test_rank_counts_and_band():
     z = np.array([[1., 0.], [2., 0.], [2., 0.], [3., 0.], [0., 5.]])
     rel = np.array([[1., 1.]])
