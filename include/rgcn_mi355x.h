@@ -709,6 +709,35 @@ int rgcn_lp_rank(const float* z, int ldz, const float* rel, int ldr, int width, 
                  const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- link prediction on rows wider than 128 (csrc/rgcn_linkpred_wide.hip) ------------------------------------------
+ * Additions; RGCN_ABI_VERSION stays.  The calls above with width 1..RGCN_XWIDE_MAX_WIDTH and their own work split: every convention,
+ * limit, status and the `bad` word are those of rgcn_lp_*; the index of rgcn_lp_index_build and the negatives of rgcn_lp_corrupt
+ * depend on the ids alone and serve both families.  No float atomics: the same inputs give the same bits.
+ *
+ * A row is up to 128 16-byte pieces; lane l of a wave owns pieces l and l + 64.  Score: one wave per triple, a lane adds its pieces
+ * in ascending order (each as (p0 + p1) + (p2 + p3)), the 64 lanes by one fixed shuffle tree. */
+int rgcn_lpw_score(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                   const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, float* score, int32_t* bad, void* stream);
+
+/* dz: one wave per node over its slots in sorted order; every row is written, the pad columns of the last piece +0.  drel: a
+ * relation's triples in sorted order in chunks of 256; a chunk's triples dealt round robin to the 4 waves of a workgroup, the waves'
+ * rows added in wave order, then the chunks in order.  The workspace (chunk pointers and one row per chunk, at most
+ * n_triples / 256 + num_relations chunks) is needed for drel only. */
+size_t rgcn_lpw_backward_workspace_bytes(int64_t n_triples, int32_t num_relations, int width);
+int rgcn_lpw_backward(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                      const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, const float* g,
+                      const uint32_t* node_ptr, const uint32_t* node_slot, const uint32_t* rel_ptr, const uint32_t* rel_triple,
+                      float* dz, int lddz, float* drel, int lddrel, void* workspace, size_t workspace_bytes, void* stream);
+
+/* rgcn_lp_rank's contract (counts, filter, -1 / -1, a workspace of n_queries floats whatever num_nodes is); greater / equal are
+ * cleared by the call's first kernel.  wg_queries: the query rows a workgroup keeps in LDS, 64 or 32; 0 takes the library's choice
+ * by width (what every caller but a timing run passes); anything else is RGCN_ERR_ARG.  The counts do not depend on it. */
+size_t rgcn_lpw_rank_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width);
+int rgcn_lpw_rank(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                  const int64_t* anchor, const int64_t* r, const int64_t* target, int64_t n_queries, const int64_t* filter_ptr,
+                  const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal, int wg_queries, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---- summaries -> original graph on tensors: block labels, transferred embeddings (csrc/rgcn_transfer.hip) ----------
  * Additions; RGCN_ABI_VERSION stays.  Both calls are asynchronous: no allocation, no read-back, no synchronisation, everything on
  * `stream`.  Argument checks come before the device is looked at.  An id out of range is never used as an address: it sets one of

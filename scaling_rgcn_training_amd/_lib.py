@@ -156,6 +156,11 @@ def _prototypes() -> dict:
         "rgcn_lp_corrupt": (i32, [vp, vp, vp, i64, i32, i32, i64, vp, vp, vp, vp]),
         "rgcn_lp_rank_workspace_bytes": (sz, [i64, i32, i32]),
         "rgcn_lp_rank": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
+        "rgcn_lpw_score": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]),
+        "rgcn_lpw_backward_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lpw_backward": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, sz, vp]),
+        "rgcn_lpw_rank_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lpw_rank": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, i32, vp, sz, vp]),
         "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
@@ -746,16 +751,18 @@ def _lp_bad(what: str, bad: Optional[torch.Tensor], dev) -> None:
 
 
 def lp_score(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor,
-             bad: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """rgcn_lp_score: ``score[t] = sum_k z[s_t, k] rel[r_t, k] z[o_t, k]`` -> float32 [T].  Asynchronous."""
-    n_nodes, n_rel, width = _lp_tables("rgcn_lp_score", z, rel)
-    n = _lp_ids("rgcn_lp_score", z.device, s=s, r=r, o=o)
-    _lp_bad("rgcn_lp_score", bad, z.device)
+             bad: Optional[torch.Tensor] = None, family: str = "lp") -> torch.Tensor:
+    """rgcn_lp_score: ``score[t] = sum_k z[s_t, k] rel[r_t, k] z[o_t, k]`` -> float32 [T].  Asynchronous.  ``family``: "lp"
+    (widths 1..128) or "lpw" (rgcn_lpw_*, widths 1..512, csrc/rgcn_linkpred_wide.hip), here and in lp_backward / lp_rank."""
+    what = f"rgcn_{family}_score"
+    n_nodes, n_rel, width = _lp_tables(what, z, rel)
+    n = _lp_ids(what, z.device, s=s, r=r, o=o)
+    _lp_bad(what, bad, z.device)
     score = torch.empty(n, dtype=torch.float32, device=z.device)
     if n:
         with torch.cuda.device(z.device):
-            check(load().rgcn_lp_score(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
-                                       r.data_ptr(), o.data_ptr(), n, score.data_ptr(), _ptr(bad), _stream(z)), "rgcn_lp_score")
+            check(getattr(load(), what)(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
+                                        r.data_ptr(), o.data_ptr(), n, score.data_ptr(), _ptr(bad), _stream(z)), what)
     return score
 
 
@@ -793,16 +800,16 @@ def lp_index_build(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes:
 
 
 def lp_backward(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, g: torch.Tensor, ix: LpIndex,
-                need_z: bool = True, need_rel: bool = True, workspace: Optional[torch.Tensor] = None):
+                need_z: bool = True, need_rel: bool = True, workspace: Optional[torch.Tensor] = None, family: str = "lp"):
     """rgcn_lp_backward: ``(dz, drel)`` from ``g [T]`` and the index of the same triples; ``None`` for a gradient that is not
     wanted.  The gradients are [rows, E] views of buffers whose rows are padded to a multiple of 4.  Asynchronous."""
-    lib, dev = load(), z.device
-    n_nodes, n_rel, width = _lp_tables("rgcn_lp_backward", z, rel)
-    n = _lp_ids("rgcn_lp_backward", dev, s=s, r=r, o=o)
+    lib, dev, what = load(), z.device, f"rgcn_{family}_backward"
+    n_nodes, n_rel, width = _lp_tables(what, z, rel)
+    n = _lp_ids(what, dev, s=s, r=r, o=o)
     if g.dtype != torch.float32 or g.device != dev or g.dim() != 1 or int(g.shape[0]) != n or (n > 1 and g.stride(0) != 1):
-        raise RgcnLibraryError(f"rgcn_lp_backward: g must be a contiguous float32 [{n}] on {dev}")
+        raise RgcnLibraryError(f"{what}: g must be a contiguous float32 [{n}] on {dev}")
     if (ix.n_triples, ix.num_nodes, ix.num_relations) != (n, n_nodes, n_rel):
-        raise RgcnLibraryError("rgcn_lp_backward: the index was built for other sizes")
+        raise RgcnLibraryError(f"{what}: the index was built for other sizes")
     ld = (width + 3) // 4 * 4
     make = torch.empty if n else torch.zeros       # (no triples: nothing is launched, the gradients are zero)
     dz = make(n_nodes, ld, dtype=torch.float32, device=dev) if need_z else None
@@ -812,13 +819,28 @@ def lp_backward(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Te
             nbytes = 0
             if need_rel:
                 if workspace is None:
-                    workspace = torch.empty(lib.rgcn_lp_backward_workspace_bytes(n, n_rel, width), dtype=torch.uint8, device=dev)
+                    workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(n, n_rel, width), dtype=torch.uint8, device=dev)
                 nbytes = int(workspace.numel())
-            check(lib.rgcn_lp_backward(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
+            check(getattr(lib, what)(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
                                        r.data_ptr(), o.data_ptr(), n, g.data_ptr(), _ptr(ix.node_ptr), _ptr(ix.node_slot),
                                        _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(dz), ld, _ptr(drel), ld,
-                                       workspace.data_ptr() if need_rel else None, nbytes, _stream(z)), "rgcn_lp_backward")
+                                       workspace.data_ptr() if need_rel else None, nbytes, _stream(z)), what)
     return (None if dz is None else dz[:, :width]), (None if drel is None else drel[:, :width])
+
+
+def lpw_score(*args, **kw):
+    """lp_score on rgcn_lpw_score (widths 1..512)"""
+    return lp_score(*args, family="lpw", **kw)
+
+
+def lpw_backward(*args, **kw):
+    """lp_backward on rgcn_lpw_backward (widths 1..512), from the same index"""
+    return lp_backward(*args, family="lpw", **kw)
+
+
+def lpw_rank(*args, **kw):
+    """lp_rank on rgcn_lpw_rank (widths 1..512)"""
+    return lp_rank(*args, family="lpw", **kw)
 
 
 def lp_corrupt(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes: int, num_negatives: int, seed: int):
@@ -837,29 +859,32 @@ def lp_corrupt(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes: int
 
 def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.Tensor, target: torch.Tensor,
             filter_ptr: Optional[torch.Tensor] = None, filter_idx: Optional[torch.Tensor] = None,
-            workspace: Optional[torch.Tensor] = None):
+            workspace: Optional[torch.Tensor] = None, family: str = "lp", wg_queries: int = 0):
     """rgcn_lp_rank: ``(greater, equal)`` int64 [Q] of the queries (anchor, r, target) over the candidates that are neither the
-    target nor in the query's filter list (CSR ``filter_ptr [Q + 1]`` / ``filter_idx``, int64; None: raw ranks).  Asynchronous."""
-    lib, dev = load(), z.device
-    n_nodes, n_rel, width = _lp_tables("rgcn_lp_rank", z, rel)
-    n = _lp_ids("rgcn_lp_rank", dev, anchor=anchor, r=r, target=target)
+    target nor in the query's filter list (CSR ``filter_ptr [Q + 1]`` / ``filter_idx``, int64; None: raw ranks).  Asynchronous.
+    ``wg_queries`` ("lpw" only): the query rows per workgroup, 64 or 32; 0 is the library's choice (tools/linkpred_timing.py
+    times both)."""
+    lib, dev, what = load(), z.device, f"rgcn_{family}_rank"
+    n_nodes, n_rel, width = _lp_tables(what, z, rel)
+    n = _lp_ids(what, dev, anchor=anchor, r=r, target=target)
+    shape = (int(wg_queries),) if family == "lpw" else ()
     flen = 0
     if filter_ptr is not None:
-        _lp_ids("rgcn_lp_rank", dev, filter_ptr=filter_ptr)
-        _lp_ids("rgcn_lp_rank", dev, filter_idx=filter_idx)
+        _lp_ids(what, dev, filter_ptr=filter_ptr)
+        _lp_ids(what, dev, filter_idx=filter_idx)
         if int(filter_ptr.shape[0]) != n + 1:
-            raise RgcnLibraryError(f"rgcn_lp_rank: filter_ptr holds {int(filter_ptr.shape[0])} entries for {n} queries")
+            raise RgcnLibraryError(f"{what}: filter_ptr holds {int(filter_ptr.shape[0])} entries for {n} queries")
         flen = int(filter_idx.shape[0])
     greater = torch.empty(n, dtype=torch.int64, device=dev)
     equal = torch.empty(n, dtype=torch.int64, device=dev)
     if n:
         with torch.cuda.device(dev):
             if workspace is None:
-                workspace = torch.empty(lib.rgcn_lp_rank_workspace_bytes(n, n_nodes, width), dtype=torch.uint8, device=dev)
-            check(lib.rgcn_lp_rank(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, anchor.data_ptr(),
+                workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(n, n_nodes, width), dtype=torch.uint8, device=dev)
+            check(getattr(lib, what)(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, anchor.data_ptr(),
                                    r.data_ptr(), target.data_ptr(), n, _ptr(filter_ptr), _ptr(filter_idx) if flen else None, flen,
-                                   greater.data_ptr(), equal.data_ptr(), workspace.data_ptr(), int(workspace.numel()), _stream(z)),
-                  "rgcn_lp_rank")
+                                   greater.data_ptr(), equal.data_ptr(), *shape, workspace.data_ptr(), int(workspace.numel()), _stream(z)),
+                  what)
     return greater, equal
 
 

@@ -13,15 +13,16 @@ from torch import Tensor, nn
 from . import _lib
 
 MAX_WIDTH = 128
+WIDE_MAX_WIDTH = _lib.XWIDE_MAX_WIDTH      # DistMult(..., wide=True): the rgcn_lpw_* kernels
 
 
-def _padded(t: Tensor) -> Tensor:
+def _padded(t: Tensor, max_width: int = MAX_WIDTH) -> Tensor:
     """``t [rows, E]`` as the kernels read it: fp32, last dimension contiguous, row stride a multiple of 4, base 16-byte aligned.
     Returned as it is when it already lies that way (every width that is a multiple of 4), else copied into padded rows."""
     if t.dtype != torch.float32 or t.dim() != 2:
         raise ValueError(f"expected a [rows, width] float32 tensor (got {tuple(t.shape)}, {t.dtype})")
-    if not 1 <= t.shape[1] <= MAX_WIDTH:
-        raise ValueError(f"widths 1..{MAX_WIDTH} only (got {t.shape[1]}); DESIGN.md 18")
+    if not 1 <= t.shape[1] <= max_width:
+        raise ValueError(f"widths 1..{max_width} only (got {t.shape[1]}); DESIGN.md 18, 21")
     if (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
         return t
     buf = torch.zeros(t.shape[0], (t.shape[1] + 3) // 4 * 4, dtype=torch.float32, device=t.device)
@@ -46,14 +47,16 @@ def _triples(s: Tensor, r: Tensor, o: Tensor, dev=None) -> Tuple[Tensor, Tensor,
 
 class _DistMultFunction(torch.autograd.Function):
     """rgcn_lp_score forward; rgcn_lp_index_build + rgcn_lp_backward backward.  The index is built in the backward, so at most once per
-    forward / backward pair and only when a gradient is wanted, and only the halves the wanted gradients need."""
+    forward / backward pair and only when a gradient is wanted, and only the halves the wanted gradients need.  ``family``: "lp", or
+    "lpw" for a wide decoder's rows of more than 128 columns (the index is the same)."""
 
     @staticmethod
-    def forward(ctx, z, rel, s, r, o, bad, builds):
-        zp, rp = _padded(z.detach()), _padded(rel.detach())
+    def forward(ctx, z, rel, s, r, o, bad, builds, family):
+        limit = WIDE_MAX_WIDTH if family == "lpw" else MAX_WIDTH
+        zp, rp = _padded(z.detach(), limit), _padded(rel.detach(), limit)
         ctx.save_for_backward(zp, rp, s, r, o)
-        ctx.bad, ctx.builds = bad, builds
-        return _lib.lp_score(zp, rp, s, r, o, bad)
+        ctx.bad, ctx.builds, ctx.family = bad, builds, family
+        return _lib.lp_score(zp, rp, s, r, o, bad, family=family)
 
     @staticmethod
     def backward(ctx, g):
@@ -64,21 +67,31 @@ class _DistMultFunction(torch.autograd.Function):
             ix = _lib.lp_index_build(s, r, o, int(zp.shape[0]), int(rp.shape[0]), ctx.bad, nodes=need_z, relations=need_rel)
             ctx.builds["node"] += int(need_z)
             ctx.builds["relation"] += int(need_rel)
-            dz, drel = _lib.lp_backward(zp, rp, s, r, o, g.contiguous(), ix, need_z, need_rel)
-        return dz, drel, None, None, None, None, None
+            dz, drel = _lib.lp_backward(zp, rp, s, r, o, g.contiguous(), ix, need_z, need_rel, family=ctx.family)
+        return dz, drel, None, None, None, None, None, None
 
 
 class DistMult(nn.Module):
     """``score(s, r, o) = sum_k z[s, k] rel[r, k] z[o, k]`` with one trainable row per relation.  ``rel`` is initialised with
-    ``xavier_uniform_``, as PyG's example decoder is.  Ids out of range score 0, get no gradient and are reported by ``check()``."""
+    ``xavier_uniform_``, as PyG's example decoder is.  Ids out of range score 0, get no gradient and are reported by ``check()``.
+    ``wide=True`` allows ``dim`` up to 512 (``None``: ``conv``'s import-time ``RGCN_WIDE`` default, as ``RGCNConv`` takes it): a
+    ``dim`` above 128 runs on csrc/rgcn_linkpred_wide.hip, a wide decoder of at most 128 on the kernels of a narrow
+    one, bit for bit."""
 
-    def __init__(self, num_relations: int, dim: int):
+    def __init__(self, num_relations: int, dim: int, wide: Optional[bool] = None):
         super().__init__()
         if isinstance(num_relations, bool) or not isinstance(num_relations, int) or not 1 <= num_relations <= 65536:
             raise ValueError(f"num_relations must be an int in 1..65536 (got {num_relations!r})")
-        if isinstance(dim, bool) or not isinstance(dim, int) or not 1 <= dim <= MAX_WIDTH:
-            raise ValueError(f"dim must be an int in 1..{MAX_WIDTH} (got {dim!r}); wider decoders are not built (DESIGN.md 18)")
-        self.num_relations, self.dim = num_relations, dim
+        if wide is None:
+            from .conv import _WIDE_DEFAULT
+            wide = _WIDE_DEFAULT
+        if not isinstance(wide, bool):
+            raise ValueError(f"wide must be a bool or None (got {wide!r})")
+        limit = WIDE_MAX_WIDTH if wide else MAX_WIDTH
+        if isinstance(dim, bool) or not isinstance(dim, int) or not 1 <= dim <= limit:
+            raise ValueError(f"dim must be an int in 1..{limit} (got {dim!r}); wide=True allows 1..{WIDE_MAX_WIDTH} (DESIGN.md 21)")
+        self.num_relations, self.dim, self.wide = num_relations, dim, wide
+        self.family = "lpw" if dim > MAX_WIDTH else "lp"      # the kernels that serve this width
         self.rel = nn.Parameter(torch.empty(num_relations, dim))
         nn.init.xavier_uniform_(self.rel)
         self._bad: Optional[Tensor] = None
@@ -95,7 +108,7 @@ class DistMult(nn.Module):
         if z.device != self.rel.device:
             raise ValueError(f"z lives on {z.device}, the decoder on {self.rel.device}")
         s, r, o = _triples(s, r, o, z.device)
-        return _DistMultFunction.apply(z, self.rel, s, r, o, self._bad_word(z.device), self.index_builds)
+        return _DistMultFunction.apply(z, self.rel, s, r, o, self._bad_word(z.device), self.index_builds, self.family)
 
     def check(self) -> None:
         """Raise if a call since the last ``check()`` met an id out of range.  Reads one word back: SYNCHRONISES."""
@@ -208,7 +221,9 @@ def ranks(z: Tensor, decoder: DistMult, s: Tensor, r: Tensor, o: Tensor, side: s
             raise ValueError("the filter was built for another number of nodes or relations")
         fptr, fidx = filter.lists(s, r, o, side)
     anchor, target = (s, o) if side == "object" else (o, s)
-    return _lib.lp_rank(_padded(z.detach()), _padded(decoder.rel.detach()), anchor, r, target, fptr, fidx)
+    limit = WIDE_MAX_WIDTH if decoder.family == "lpw" else MAX_WIDTH
+    return _lib.lp_rank(_padded(z.detach(), limit), _padded(decoder.rel.detach(), limit), anchor, r, target, fptr, fidx,
+                        family=decoder.family)
 
 
 def metrics(greater: Tensor, equal: Tensor, ks: Sequence[int] = (1, 3, 10), ties: str = "mean") -> Dict[str, float]:

@@ -6,7 +6,8 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 if [[ "${1:-}" == "--temps" ]]; then
   mkdir -p "$2"; cd "$2"
   for f in $(python3 -c "import sys; sys.path.insert(0, '$ROOT'); import os, __graft_entry__ as g; print(*[os.path.basename(s)[:-4] for s in g.SRCS])"); do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -save-temps -Rpass-analysis=kernel-resource-usage \
+    extra="$(python3 -c "import sys; sys.path.insert(0, '$ROOT'); import __graft_entry__ as g; print(*g.SRC_FLAGS.get('$f.hip', []))")"
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $extra -c -save-temps -Rpass-analysis=kernel-resource-usage \
         "$ROOT/scaling_rgcn_training_amd/csrc/$f.hip" -o "$f.o" 2> "$f.resources.txt"
   done
 fi

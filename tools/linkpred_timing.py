@@ -10,6 +10,10 @@ calls that end in a synchronise (tools/minibatch_timing.py's method).
   * ``train_step``: one step of ``Trainer.train_link_prediction``'s loop (full-graph encode, 1M positives + 1M negatives, loss,
     backward, Adam) with the HIP decoder and negatives, against the same step with the torch decoder and negatives.
     python tools/linkpred_timing.py [--steps 10] [--out profiles/linkpred_timing.txt]
+``--dim D`` with D > 128 times the wide decoder (``DistMult(..., wide=True)``, csrc/rgcn_linkpred_wide.hip) on the same
+graph: ``score_backward`` and ``ranks`` as above, and ``rank_shapes``, the raw ranking pass with 64 and with 32 query rows per
+workgroup, alternating; ``corrupt`` and ``train_step`` do not depend on the decoder's kernels and are left out.  Its default output is
+profiles/linkpred_wide_timing.txt.
 Writes one JSON line per measurement."""
 import argparse
 import json
@@ -69,8 +73,11 @@ def torch_ranks(z, rel, s, r, o, filt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linkpred_timing.txt"))
+    ap.add_argument("--dim", type=int, default=DIM)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    dim, wide = args.dim, args.dim > 128
+    args.out = args.out or os.path.join(ROOT, "profiles", "linkpred_wide_timing.txt" if wide else "linkpred_timing.txt")
     import __graft_entry__ as g
     g.build()
     from oracle import rgcn_oracle as O
@@ -83,7 +90,7 @@ def main():
     dev = torch.device("cuda:0")
     steps = args.steps
     gen = torch.Generator(device=dev).manual_seed(0)
-    shape = {"nodes": NODES, "edges": EDGES, "relations": RELATIONS, "dim": DIM}
+    shape = {"nodes": NODES, "edges": EDGES, "relations": RELATIONS, "dim": dim}
     lines = [json.dumps({"steps": steps, "method": "host clock around calls that end in a synchronise, median after two warm-ups",
                          "device": torch.cuda.get_device_name(0), **shape})]
 
@@ -91,8 +98,9 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
-    z = torch.randn(NODES, DIM, device=dev, generator=gen)
-    dec = DistMult(RELATIONS, DIM).to(dev)
+    z = torch.randn(NODES, dim, device=dev, generator=gen)
+    dec = DistMult(RELATIONS, dim, wide=True).to(dev) if wide else DistMult(RELATIONS, dim).to(dev)
+    fam = dict(family=dec.family)
     s, o = (torch.randint(0, NODES, (TRIPLES,), device=dev, generator=gen) for _ in range(2))
     r = torch.randint(0, RELATIONS, (TRIPLES,), device=dev, generator=gen)
     gout = torch.randn(TRIPLES, device=dev, generator=gen)
@@ -115,20 +123,21 @@ def main():
     rec["max_abs_diff_dz"] = float((zg.grad - ours_grads[0]).abs().max())
     rec["max_abs_diff_drel_over_max"] = float((dec.rel.grad - ours_grads[1]).abs().max() / dec.rel.grad.abs().max())
     rel = dec.rel.detach()
-    rec["hip_score_ms"] = wall_ms(lambda: _lib.lp_score(z, rel, s, r, o), steps)
+    rec["hip_score_ms"] = wall_ms(lambda: _lib.lp_score(z, rel, s, r, o, **fam), steps)
     rec["hip_index_build_ms"] = wall_ms(lambda: _lib.lp_index_build(s, r, o, NODES, RELATIONS), steps)
     ix = _lib.lp_index_build(s, r, o, NODES, RELATIONS)
-    rec["hip_backward_ms"] = wall_ms(lambda: _lib.lp_backward(z, rel, s, r, o, gout, ix), steps)
+    rec["hip_backward_ms"] = wall_ms(lambda: _lib.lp_backward(z, rel, s, r, o, gout, ix, **fam), steps)
     rec["torch_score_ms"] = wall_ms(lambda: torch_score(z, rel, s, r, o), steps)
     emit(rec)
     del zg, ours_grads, ix
 
     # ---- (ii) negatives
-    rec = {"case": "corrupt", "triples": TRIPLES, "negatives_per_triple": 1,
-           "hip_ms": wall_ms(lambda: corrupt(s, r, o, NODES, 1, 7), steps),
-           "torch_ms": wall_ms(lambda: torch_corrupt(s, r, o, NODES, gen), steps)}
-    rec["torch_over_hip"] = round(rec["torch_ms"] / rec["hip_ms"], 2)
-    emit(rec)
+    if not wide:
+        rec = {"case": "corrupt", "triples": TRIPLES, "negatives_per_triple": 1,
+               "hip_ms": wall_ms(lambda: corrupt(s, r, o, NODES, 1, 7), steps),
+               "torch_ms": wall_ms(lambda: torch_corrupt(s, r, o, NODES, gen), steps)}
+        rec["torch_over_hip"] = round(rec["torch_ms"] / rec["hip_ms"], 2)
+        emit(rec)
 
     # ---- (iii) filtered ranks
     known = torch.stack([s, r, o], 1)
@@ -148,10 +157,31 @@ def main():
     g_t, e_t = torch_ranks(z, rel, qs, qr, qo, filt)
     rec["queries_with_another_greater_count_than_torch"] = int((g_h != g_t).sum())
     rec["max_abs_diff_greater"] = int((g_h - g_t).abs().max())
-    rec["pair_gflop"] = round(2 * QUERIES * NODES * DIM / 1e9, 1)
-    rec["hip_raw_tflops_fp32"] = round(2 * QUERIES * NODES * DIM / (rec["hip_raw_ms"] * 1e-3) / 1e12, 2)
+    rec["pair_gflop"] = round(2 * QUERIES * NODES * dim / 1e9, 1)
+    rec["hip_raw_tflops_fp32"] = round(2 * QUERIES * NODES * dim / (rec["hip_raw_ms"] * 1e-3) / 1e12, 2)
     emit(rec)
     del filt, known, g_h, g_t, e_h, e_t
+    if wide:
+        # the two workgroup shapes of the sweep, raw ranks (no lists), one call of each in turn so that both see the same machine
+        rec = {"case": "rank_shapes", "queries": QUERIES, "entities": NODES, "dim": dim, "calls_each": rank_steps}
+        for wg in (64, 32):
+            _lib.lpw_rank(z, rel, qs, qr, qo, wg_queries=wg)
+        ts = {64: [], 32: []}
+        for _ in range(rank_steps):
+            for wg in (64, 32):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                _lib.lpw_rank(z, rel, qs, qr, qo, wg_queries=wg)
+                torch.cuda.synchronize()
+                ts[wg].append(round((time.perf_counter() - t0) * 1e3, 3))
+        for wg in (64, 32):
+            rec[f"wg{wg}_ms_each"], rec[f"wg{wg}_ms"] = ts[wg], sorted(ts[wg])[rank_steps // 2]
+        g64, g32 = _lib.lpw_rank(z, rel, qs, qr, qo, wg_queries=64), _lib.lpw_rank(z, rel, qs, qr, qo, wg_queries=32)
+        rec["counts_equal"] = bool(torch.equal(g64[0], g32[0]) and torch.equal(g64[1], g32[1]))
+        emit(rec)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return 0
 
     # ---- (iv) one training step
     ei, et = O.synthetic_graph(NODES, EDGES, RELATIONS, seed=0)
