@@ -738,6 +738,44 @@ int rgcn_lpw_rank(const float* z, int ldz, const float* rel, int ldr, int width,
                   const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal, int wg_queries, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- link prediction with asymmetric decoders: ComplEx and TransE (csrc/rgcn_kge.hip) ------------------------------
+ * Additions; RGCN_ABI_VERSION stays.  Every convention, limit, status and the `bad` word are those of rgcn_lp_* (widths 1..128); the
+ * index of rgcn_lp_index_build and the negatives of rgcn_lp_corrupt depend on the ids alone and serve every decoder.  `decoder` is
+ * one of the two constants below (anything else: RGCN_ERR_ARG).  No float atomics: the same inputs give the same bits.
+ *   RGCN_KGE_COMPLEX     columns 2k, 2k + 1 of a row are the real and imaginary part of component k (an odd width: RGCN_ERR_WIDTH);
+ *                        score = Re sum_k s_k r_k conj(o_k); d/ds = conj(r) o o, d/do = s o r, d/dr = conj(s) o o.
+ *   RGCN_KGE_TRANSE_L1   score = -sum_k |d_k|, d = (s + r) - o in that order; d/ds = d/dr = -sign(d), d/do = +sign(d), sign(0) = 0. */
+#define RGCN_KGE_COMPLEX 0
+#define RGCN_KGE_TRANSE_L1 1
+
+/* One float per triple.  A triple is ceil(width / 4) lanes with one 16-byte piece of each of the three rows; ComplEx adds the piece's
+ * two components as p0 + p1, TransE its four columns as (|d0| + |d1|) + (|d2| + |d3|); the lanes are added by rgcn_lp_score's shuffle
+ * tree (TransE negates the sum). */
+int rgcn_kge_score(int decoder, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                   const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, float* score, int32_t* bad, void* stream);
+
+/* rgcn_lp_backward's contract on the index of rgcn_lp_index_build.  dz[v]: v's slots in sorted order, the slot's parity choosing the
+ * formula (even: v is the subject of the triple, odd: its object); s_t == o_t contributes both.  drel[r]: chunks of 256 triples, lane
+ * groups dealt round robin and added in order, then the chunks in order.  Every row is written, the pad columns of the last piece +0;
+ * either output may be NULL.  The workspace is needed for drel only. */
+size_t rgcn_kge_backward_workspace_bytes(int decoder, int64_t n_triples, int32_t num_relations, int width);
+int rgcn_kge_backward(int decoder, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes,
+                      int32_t num_relations, const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples, const float* g,
+                      const uint32_t* node_ptr, const uint32_t* node_slot, const uint32_t* rel_ptr, const uint32_t* rel_triple,
+                      float* dz, int lddz, float* drel, int lddrel, void* workspace, size_t workspace_bytes, void* stream);
+
+/* rgcn_lp_rank's contract (counts, filter and its clamping, -1 / -1, a workspace of n_queries floats whatever num_nodes is); greater /
+ * equal are cleared by the call's first kernel.  side 0: the anchor is the subject and the candidates are objects, (s, r, ?); side 1:
+ * the anchor is the object, (?, r, o); anything else is RGCN_ERR_ARG.  ComplEx: the query row s o r (side 0) or conj(r) o o (side 1),
+ * then rgcn_lp_rank's fp32-MFMA sweep.  TransE: the query row s + r (side 0) or o - r (side 1), a candidate c scores -|query - c|_1 on
+ * the vector ALU; a pair's columns are added in four chains (chain k: columns 16 c + 4 k + j in ascending (c, j)), the chains as
+ * (k0 + k1) + (k2 + k3).  One device function per decoder makes every score of the call. */
+size_t rgcn_kge_rank_workspace_bytes(int decoder, int64_t n_queries, int32_t num_nodes, int width);
+int rgcn_kge_rank(int decoder, int side, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes,
+                  int32_t num_relations, const int64_t* anchor, const int64_t* r, const int64_t* target, int64_t n_queries,
+                  const int64_t* filter_ptr, const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- summaries -> original graph on tensors: block labels, transferred embeddings (csrc/rgcn_transfer.hip) ----------
  * Additions; RGCN_ABI_VERSION stays.  Both calls are asynchronous: no allocation, no read-back, no synchronisation, everything on
  * `stream`.  Argument checks come before the device is looked at.  An id out of range is never used as an address: it sets one of

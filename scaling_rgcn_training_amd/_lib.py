@@ -161,6 +161,12 @@ def _prototypes() -> dict:
         "rgcn_lpw_backward": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, sz, vp]),
         "rgcn_lpw_rank_workspace_bytes": (sz, [i64, i32, i32]),
         "rgcn_lpw_rank": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, i32, vp, sz, vp]),
+        "rgcn_kge_score": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]),
+        "rgcn_kge_backward_workspace_bytes": (sz, [i32, i64, i32, i32]),
+        "rgcn_kge_backward": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, sz,
+                                    vp]),
+        "rgcn_kge_rank_workspace_bytes": (sz, [i32, i64, i32, i32]),
+        "rgcn_kge_rank": (i32, [i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
@@ -715,6 +721,7 @@ def emb_adam_rows(table: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.
 # ---- link prediction (rgcn_linkpred.hip) -----------------------------------------------------------------------------------
 LP_BAD_NODE, LP_BAD_REL = 1, 2      # RGCN_LP_BAD_*: bits of the `bad` word
 LP_MAX_KEYS = 0xFFFF0000
+KGE_COMPLEX, KGE_TRANSE_L1 = 0, 1      # RGCN_KGE_*: the `decoder` of the rgcn_kge_* calls (csrc/rgcn_kge.hip)
 
 
 def _lp_tables(what: str, z: torch.Tensor, rel: torch.Tensor):
@@ -751,18 +758,19 @@ def _lp_bad(what: str, bad: Optional[torch.Tensor], dev) -> None:
 
 
 def lp_score(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor,
-             bad: Optional[torch.Tensor] = None, family: str = "lp") -> torch.Tensor:
+             bad: Optional[torch.Tensor] = None, family: str = "lp", decoder: int = 0) -> torch.Tensor:
     """rgcn_lp_score: ``score[t] = sum_k z[s_t, k] rel[r_t, k] z[o_t, k]`` -> float32 [T].  Asynchronous.  ``family``: "lp"
-    (widths 1..128) or "lpw" (rgcn_lpw_*, widths 1..512, csrc/rgcn_linkpred_wide.hip), here and in lp_backward / lp_rank."""
-    what = f"rgcn_{family}_score"
+    (widths 1..128), "lpw" (rgcn_lpw_*, widths 1..512, csrc/rgcn_linkpred_wide.hip) or "kge" (rgcn_kge_*, csrc/rgcn_kge.hip, whose
+    calls begin with ``decoder``: KGE_COMPLEX or KGE_TRANSE_L1), here and in lp_backward / lp_rank."""
+    what, head = f"rgcn_{family}_score", _kge_head(family, decoder)
     n_nodes, n_rel, width = _lp_tables(what, z, rel)
     n = _lp_ids(what, z.device, s=s, r=r, o=o)
     _lp_bad(what, bad, z.device)
     score = torch.empty(n, dtype=torch.float32, device=z.device)
     if n:
         with torch.cuda.device(z.device):
-            check(getattr(load(), what)(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
-                                        r.data_ptr(), o.data_ptr(), n, score.data_ptr(), _ptr(bad), _stream(z)), what)
+            check(getattr(load(), what)(*head, z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel,
+                                        s.data_ptr(), r.data_ptr(), o.data_ptr(), n, score.data_ptr(), _ptr(bad), _stream(z)), what)
     return score
 
 
@@ -800,10 +808,11 @@ def lp_index_build(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes:
 
 
 def lp_backward(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, g: torch.Tensor, ix: LpIndex,
-                need_z: bool = True, need_rel: bool = True, workspace: Optional[torch.Tensor] = None, family: str = "lp"):
+                need_z: bool = True, need_rel: bool = True, workspace: Optional[torch.Tensor] = None, family: str = "lp",
+                decoder: int = 0):
     """rgcn_lp_backward: ``(dz, drel)`` from ``g [T]`` and the index of the same triples; ``None`` for a gradient that is not
     wanted.  The gradients are [rows, E] views of buffers whose rows are padded to a multiple of 4.  Asynchronous."""
-    lib, dev, what = load(), z.device, f"rgcn_{family}_backward"
+    lib, dev, what, head = load(), z.device, f"rgcn_{family}_backward", _kge_head(family, decoder)
     n_nodes, n_rel, width = _lp_tables(what, z, rel)
     n = _lp_ids(what, dev, s=s, r=r, o=o)
     if g.dtype != torch.float32 or g.device != dev or g.dim() != 1 or int(g.shape[0]) != n or (n > 1 and g.stride(0) != 1):
@@ -819,13 +828,34 @@ def lp_backward(z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Te
             nbytes = 0
             if need_rel:
                 if workspace is None:
-                    workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(n, n_rel, width), dtype=torch.uint8, device=dev)
+                    workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(*head, n, n_rel, width), dtype=torch.uint8, device=dev)
                 nbytes = int(workspace.numel())
-            check(getattr(lib, what)(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
+            check(getattr(lib, what)(*head, z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, s.data_ptr(),
                                        r.data_ptr(), o.data_ptr(), n, g.data_ptr(), _ptr(ix.node_ptr), _ptr(ix.node_slot),
                                        _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(dz), ld, _ptr(drel), ld,
                                        workspace.data_ptr() if need_rel else None, nbytes, _stream(z)), what)
     return (None if dz is None else dz[:, :width]), (None if drel is None else drel[:, :width])
+
+
+def _kge_head(family: str, decoder: int) -> tuple:
+    """the leading ``decoder`` argument of the rgcn_kge_* calls; nothing for the other families"""
+    return (int(decoder),) if family == "kge" else ()
+
+
+def kge_score(decoder: int, *args, **kw):
+    """lp_score on rgcn_kge_score: ComplEx (``Re sum_k s_k r_k conj(o_k)``, interleaved real / imaginary columns) or TransE
+    (``-sum_k |s_k + r_k - o_k|``)"""
+    return lp_score(*args, family="kge", decoder=decoder, **kw)
+
+
+def kge_backward(decoder: int, *args, **kw):
+    """lp_backward on rgcn_kge_backward, from the same index"""
+    return lp_backward(*args, family="kge", decoder=decoder, **kw)
+
+
+def kge_rank(decoder: int, side: int, *args, **kw):
+    """lp_rank on rgcn_kge_rank; ``side`` 0: (s, r, ?), 1: (?, r, o)"""
+    return lp_rank(*args, family="kge", decoder=decoder, side=side, **kw)
 
 
 def lpw_score(*args, **kw):
@@ -859,12 +889,12 @@ def lp_corrupt(s: torch.Tensor, r: torch.Tensor, o: torch.Tensor, num_nodes: int
 
 def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.Tensor, target: torch.Tensor,
             filter_ptr: Optional[torch.Tensor] = None, filter_idx: Optional[torch.Tensor] = None,
-            workspace: Optional[torch.Tensor] = None, family: str = "lp", wg_queries: int = 0):
+            workspace: Optional[torch.Tensor] = None, family: str = "lp", wg_queries: int = 0, decoder: int = 0, side: int = 0):
     """rgcn_lp_rank: ``(greater, equal)`` int64 [Q] of the queries (anchor, r, target) over the candidates that are neither the
     target nor in the query's filter list (CSR ``filter_ptr [Q + 1]`` / ``filter_idx``, int64; None: raw ranks).  Asynchronous.
     ``wg_queries`` ("lpw" only): the query rows per workgroup, 64 or 32; 0 is the library's choice (tools/linkpred_timing.py
-    times both)."""
-    lib, dev, what = load(), z.device, f"rgcn_{family}_rank"
+    times both).  ``side`` ("kge" only): 0, the anchor is the subject and the candidates are objects; 1, the anchor is the object."""
+    lib, dev, what, head = load(), z.device, f"rgcn_{family}_rank", _kge_head(family, decoder)
     n_nodes, n_rel, width = _lp_tables(what, z, rel)
     n = _lp_ids(what, dev, anchor=anchor, r=r, target=target)
     shape = (int(wg_queries),) if family == "lpw" else ()
@@ -880,8 +910,9 @@ def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.T
     if n:
         with torch.cuda.device(dev):
             if workspace is None:
-                workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(n, n_nodes, width), dtype=torch.uint8, device=dev)
-            check(getattr(lib, what)(z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes, n_rel, anchor.data_ptr(),
+                workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(*head, n, n_nodes, width), dtype=torch.uint8, device=dev)
+            check(getattr(lib, what)(*head, *((int(side),) if head else ()), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width,
+                                   n_nodes, n_rel, anchor.data_ptr(),
                                    r.data_ptr(), target.data_ptr(), n, _ptr(filter_ptr), _ptr(filter_idx) if flen else None, flen,
                                    greater.data_ptr(), equal.data_ptr(), *shape, workspace.data_ptr(), int(workspace.numel()), _stream(z)),
                   what)

@@ -2,7 +2,8 @@
 the kernels of csrc/rgcn_linkpred.hip, with the plumbing both frameworks' examples have around them (PyG ``rgcn_link_pred.py``,
 DGL ``link.py``): ``with_inverse_edges`` for the encoder's graph, ``FilterIndex`` for the known triples, ``metrics`` for MRR and
 Hits@k.  The encoder is any model that returns ``z [N, dim]``, e.g. ``Emb_Layers(2 R, hidden, dim, N, emb)`` with
-``activation=do_nothing``.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
+``activation=do_nothing``.  ``ComplEx`` and ``TransE`` are the asymmetric decoders, on the kernels of csrc/rgcn_kge.hip:
+the same index, negatives, filter and metrics serve them.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -122,6 +123,83 @@ class DistMult(nn.Module):
             raise ValueError("DistMult: " + " and ".join(what) + " (such triples scored 0 and got no gradient)")
 
 
+class _KgeFunction(torch.autograd.Function):
+    """rgcn_kge_score forward; rgcn_lp_index_build + rgcn_kge_backward backward, as ``_DistMultFunction`` does it: the index is a
+    function of the ids alone, so it is the same one, built in the backward and only the halves the wanted gradients need."""
+
+    @staticmethod
+    def forward(ctx, z, rel, s, r, o, bad, builds, code):
+        zp, rp = _padded(z.detach()), _padded(rel.detach())
+        ctx.save_for_backward(zp, rp, s, r, o)
+        ctx.bad, ctx.builds, ctx.code = bad, builds, code
+        return _lib.kge_score(code, zp, rp, s, r, o, bad)
+
+    @staticmethod
+    def backward(ctx, g):
+        zp, rp, s, r, o = ctx.saved_tensors
+        need_z, need_rel = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dz = drel = None
+        if need_z or need_rel:
+            ix = _lib.lp_index_build(s, r, o, int(zp.shape[0]), int(rp.shape[0]), ctx.bad, nodes=need_z, relations=need_rel)
+            ctx.builds["node"] += int(need_z)
+            ctx.builds["relation"] += int(need_rel)
+            dz, drel = _lib.kge_backward(ctx.code, zp, rp, s, r, o, g.contiguous(), ix, need_z, need_rel)
+        return dz, drel, None, None, None, None, None, None
+
+
+class _KgeDecoder(nn.Module):
+    """What ``ComplEx`` and ``TransE`` share: one trainable row per relation (``xavier_uniform_``), the ``bad`` word and
+    ``check()``, ``index_builds``, and a forward on the kernels of csrc/rgcn_kge.hip.  ``dim`` is 1..128."""
+    code: int
+
+    def __init__(self, num_relations: int, dim: int):
+        super().__init__()
+        if isinstance(num_relations, bool) or not isinstance(num_relations, int) or not 1 <= num_relations <= 65536:
+            raise ValueError(f"num_relations must be an int in 1..65536 (got {num_relations!r})")
+        if isinstance(dim, bool) or not isinstance(dim, int) or not 1 <= dim <= MAX_WIDTH:
+            raise ValueError(f"dim must be an int in 1..{MAX_WIDTH} (got {dim!r}); DESIGN.md 22")
+        self.num_relations, self.dim = num_relations, dim
+        self.rel = nn.Parameter(torch.empty(num_relations, dim))
+        nn.init.xavier_uniform_(self.rel)
+        self._bad: Optional[Tensor] = None
+        self.index_builds = {"node": 0, "relation": 0}      # halves of the index built so far (tests, profiling)
+
+    _bad_word = DistMult._bad_word
+
+    def forward(self, z: Tensor, s: Tensor, r: Tensor, o: Tensor) -> Tensor:
+        if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] != self.dim or z.dtype != torch.float32:
+            raise ValueError(f"z must be float32 [N, {self.dim}] (got {tuple(z.shape) if torch.is_tensor(z) else type(z)})")
+        if z.device != self.rel.device:
+            raise ValueError(f"z lives on {z.device}, the decoder on {self.rel.device}")
+        s, r, o = _triples(s, r, o, z.device)
+        return _KgeFunction.apply(z, self.rel, s, r, o, self._bad_word(z.device), self.index_builds, self.code)
+
+    def check(self) -> None:
+        """Raise if a call since the last ``check()`` met an id out of range.  Reads one word back: SYNCHRONISES."""
+        try:
+            DistMult.check(self)
+        except ValueError as err:
+            raise ValueError(str(err).replace("DistMult", type(self).__name__)) from None
+
+
+class ComplEx(_KgeDecoder):
+    """``score(s, r, o) = Re sum_k s_k r_k conj(o_k)`` on ``dim / 2`` complex components: columns ``2k, 2k + 1`` of a row of ``z`` /
+    ``rel`` are the real and imaginary part of component k, the layout ``torch.view_as_complex(z.view(N, dim // 2, 2))`` reads.
+    Not symmetric in subject and object.  ``dim`` must be even."""
+    code = _lib.KGE_COMPLEX
+
+    def __init__(self, num_relations: int, dim: int):
+        super().__init__(num_relations, dim)
+        if dim % 2:
+            raise ValueError(f"ComplEx needs an even dim: two columns per complex component (got {dim})")
+
+
+class TransE(_KgeDecoder):
+    """``score(s, r, o) = -sum_k |z[s, k] + rel[r, k] - z[o, k]|``: the L1 norm, PyG's default ``p_norm``.  The gradient uses
+    ``sign(0) = 0``, torch's convention.  Scores are never positive: train it with ``loss="margin"``."""
+    code = _lib.KGE_TRANSE_L1
+
+
 def corrupt(s: Tensor, r: Tensor, o: Tensor, num_nodes: int, num_negatives: int, seed: int) -> Tuple[Tensor, Tensor, Tensor]:
     """``num_negatives`` negatives per triple: ``(s', r', o')``, each ``[T * num_negatives]``, position ``i * num_negatives + j``
     being triple i with its subject or its object replaced by a node drawn from the generator at ``(seed, i, j)``.  A pure function
@@ -200,16 +278,17 @@ class FilterIndex:
         return out_ptr, idx[src].contiguous()
 
 
-def ranks(z: Tensor, decoder: DistMult, s: Tensor, r: Tensor, o: Tensor, side: str = "object",
+def ranks(z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor, side: str = "object",
           filter: Optional[FilterIndex] = None) -> Tuple[Tensor, Tensor]:
     """``(greater, equal)`` int64 [Q]: for every test triple the candidates that score strictly above, and exactly like, its true
     object (``side="object"``: (s, r, ?)) or subject (``"subject"``: (?, r, o); DistMult is symmetric, the same kernel with the
     object as anchor), over all N entities but the true one and, with ``filter``, but every entity that completes the query to a
-    known triple.  No [Q, N] scores exist anywhere.  A query with an id out of range gets (-1, -1)."""
+    known triple.  No [Q, N] scores exist anywhere.  A query with an id out of range gets (-1, -1).  ``ComplEx`` and ``TransE``
+    decoders are ranked by rgcn_kge_rank, which is told the side."""
     if side not in ("object", "subject"):
         raise ValueError(f"side must be 'object' or 'subject' (got {side!r})")
-    if not isinstance(decoder, DistMult):
-        raise ValueError("ranks scores with a DistMult decoder")
+    if not isinstance(decoder, (DistMult, _KgeDecoder)):
+        raise ValueError("ranks scores with a DistMult, ComplEx or TransE decoder")
     if filter is not None and not isinstance(filter, FilterIndex):
         raise ValueError("filter must be a FilterIndex or None")
     if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] != decoder.dim:
@@ -221,6 +300,9 @@ def ranks(z: Tensor, decoder: DistMult, s: Tensor, r: Tensor, o: Tensor, side: s
             raise ValueError("the filter was built for another number of nodes or relations")
         fptr, fidx = filter.lists(s, r, o, side)
     anchor, target = (s, o) if side == "object" else (o, s)
+    if isinstance(decoder, _KgeDecoder):       # not symmetric: the kernel is told which end the anchor is
+        return _lib.kge_rank(decoder.code, 0 if side == "object" else 1, _padded(z.detach()), _padded(decoder.rel.detach()), anchor, r,
+                             target, fptr, fidx)
     limit = WIDE_MAX_WIDTH if decoder.family == "lpw" else MAX_WIDTH
     return _lib.lp_rank(_padded(z.detach(), limit), _padded(decoder.rel.detach(), limit), anchor, r, target, fptr, fidx,
                         family=decoder.family)

@@ -344,7 +344,7 @@ class Trainer:
 
     def train_link_prediction(self, model: nn.Module, decoder: nn.Module, training_data, train_triples: Tensor,
                               valid_triples: Tensor = None, num_negatives: int = 1, batch_size: int = None, reg: float = 0.01,
-                              seed: int = 0) -> Tuple[List[float], List[float]]:
+                              seed: int = 0, loss: str = "bce", margin: float = 1.0) -> Tuple[List[float], List[float]]:
         """Link prediction as PyG's ``rgcn_link_pred.py`` trains it.  ``training_data``: the encoder's graph (``edge_index`` /
         ``edge_type``, usually ``with_inverse_edges`` of the training triples); ``train_triples`` / ``valid_triples``: int64 [P, 3]
         rows (s, r, o).  Per step: a full-graph encode ``z = model(training_data, do_nothing)`` (the edge tensors are moved to the
@@ -354,7 +354,10 @@ class Trainer:
         decoder.  The step seed combines ``seed``, epoch and batch as ``train_minibatch`` does.  Eager only.  Returns
         ``(losses, mrrs)``: the mean step loss per epoch, and with ``valid_triples`` the filtered MRR (both sides, ties at their
         mean rank, filtered by train + valid triples) after every epoch, else an empty list.  ``decoder.check()`` (ids out of range)
-        runs once per epoch, beside the loss read-back."""
+        runs once per epoch, beside the loss read-back.  ``loss="margin"`` replaces the BCE term by PyG's TransE loss,
+        ``relu(margin + neg - pos).mean()`` with every positive paired with its ``num_negatives`` negatives (torch ops on the two
+        score vectors).  ``TransE`` scores are never positive, so BCE on them as logits can only push towards 0 and is a poor fit:
+        train ``TransE`` with ``loss="margin"``; ``DistMult`` and ``ComplEx`` take either."""
         from .linkpred import FilterIndex, metrics
         from .sampling import check_sample_seed
         for name, t in (("train_triples", train_triples), ("valid_triples", valid_triples)):
@@ -368,6 +371,9 @@ class Trainer:
         if batch_size is not None:
             _check_number("batch_size", batch_size, int, 1, "None or an int")
         _check_number("reg", reg, (int, float), 0, "a number")
+        if loss not in ("bce", "margin"):
+            raise ValueError(f"loss must be 'bce' or 'margin' (got {loss!r})")
+        _check_number("margin", margin, (int, float), 0, "a number")
         seed = check_sample_seed(seed)
         dev = self.device
         model, decoder = model.to(dev), decoder.to(dev)
@@ -389,8 +395,12 @@ class Trainer:
                 z = model(data, do_nothing)
                 sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, _step_seed(seed, epoch, b))
                 scores = decoder(z, torch.cat([s, sn]), torch.cat([r, rn]), torch.cat([o, on]))
-                labels = torch.cat([torch.ones(s.shape[0], device=dev), torch.zeros(sn.shape[0], device=dev)])
-                output = nn.functional.binary_cross_entropy_with_logits(scores, labels)
+                if loss == "bce":
+                    labels = torch.cat([torch.ones(s.shape[0], device=dev), torch.zeros(sn.shape[0], device=dev)])
+                    output = nn.functional.binary_cross_entropy_with_logits(scores, labels)
+                else:       # negative i * num_negatives + j belongs to positive i
+                    p, n = scores[:s.shape[0]], scores[s.shape[0]:].view(s.shape[0], num_negatives)
+                    output = torch.relu(margin + n - p[:, None]).mean()
                 output = output + reg * (z.pow(2).mean() + decoder.rel.pow(2).mean())
                 output.backward()
                 optimizer.step()
