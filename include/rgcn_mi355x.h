@@ -776,6 +776,58 @@ int rgcn_kge_rank(int decoder, int side, const float* z, int ldz, const float* r
                   const int64_t* filter_ptr, const int64_t* filter_idx, int64_t filter_len, int64_t* greater, int64_t* equal,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- link prediction: the softmax loss over all entities (csrc/rgcn_lp_softmax.hip) ---------------------------------
+ * Additions; RGCN_ABI_VERSION stays.  For query i with query row q_i and true entity target_i
+ *     loss_i = logsumexp_n <q_i, z_n> - <q_i, z_target_i>,    n over ALL num_nodes entities (unfiltered, the true one included),
+ * and its gradient, without a [n_queries x num_nodes] matrix anywhere.  Every convention, limit, status and the `bad` word are those of
+ * rgcn_lp_* (widths 1..128, strides multiples of 4, 16-byte bases, pad columns never read as data; asynchronous, no allocation, no
+ * read-back); n_queries < 2^31 (RGCN_ERR_PLAN beyond).  `decoder` is RGCN_KGE_COMPLEX or RGCN_LPSM_DISTMULT; RGCN_KGE_TRANSE_L1 (its
+ * score is no dot product with a query row) and anything else: RGCN_ERR_ARG.  `side` as in rgcn_kge_rank.
+ * NO FLOAT ATOMICS: every sum has a fixed order (below), so the same inputs give the same bits on every call. */
+#define RGCN_LPSM_DISTMULT 2
+
+/* qrows [n_queries][ldq]: the decoder's query row of (anchor_i, r_i), the row the rank kernels build on the fly -- DistMult
+ * z[a] o rel[r]; ComplEx s o r (side 0) or conj(r) o o (side 1) -- materialised because the backward reads it three times; the pad
+ * columns of the last 16-byte piece are +0.  qtarget [n_queries] is target_i, or -1 for a query with any id out of range, which also
+ * gets a zero row and sets `bad`.  The calls below take qtarget as `target`: a target outside [0, num_nodes) makes the query VOID
+ * (loss 0, tlogit 0, no gradient from it or into it). */
+int rgcn_lpsm_query(int decoder, int side, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes,
+                    int32_t num_relations, const int64_t* anchor, const int64_t* r, const int64_t* target, int64_t n_queries,
+                    float* qrows, int ldq, int64_t* qtarget, int32_t* bad, void* stream);
+
+/* lse, tlogit, loss [n_queries].  rgcn_lp_rank's sweep (64 query rows in LDS, grid (query blocks, entity slices), one device function
+ * for every logit) with an online (max, sum of exp(. - max)) pair where that sweep counts; a row past num_nodes is no logit.  Pairs
+ * are merged in fixed order: a lane's rows in sweep order, the sixteen lanes of a row group by a butterfly, the eight waves in order,
+ * the slices in order.  The workspace holds one pair per (query rounded up to 64, slice):
+ *   slices = min(ceil(1024 / ceil(Q / 64)), ceil(ceil(N / 16) / 8)), at least 1;   bytes = 8 * slices * 64 ceil(Q / 64), in 256s. */
+size_t rgcn_lpsm_forward_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width);
+int rgcn_lpsm_forward(const float* qrows, int ldq, const float* z, int ldz, int width, int32_t num_nodes, const int64_t* target,
+                      int64_t n_queries, float* lse, float* tlogit, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+
+/* With w_in = g_i (exp(<q_i, z_n> - lse_i) - [n == target_i]):  dq [n_queries][lddq], dq_i = sum_n w_in z_n, and, when dz is not
+ * NULL, dz [num_nodes][lddz], dz_n = sum_i w_in q_i -- the ENTITY side of d loss / d z only, written and not accumulated; every row
+ * is written, the pad columns of the last piece +0.  lse is rgcn_lpsm_forward's.  Both come from one sweep body: 64 rows of one table
+ * stay in LDS, the other table streams past in 16-row tiles, each wave adds into its own registers; then the waves are added in
+ * order, then the slices of the streamed table in order (slices as above with the roles of the tables; the workspace holds
+ * slices x rows x 4 ceil(width / 4) floats per sliced sweep, nothing for a sweep of one slice; want_dz != 0: dz is asked for). */
+size_t rgcn_lpsm_backward_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width, int want_dz);
+int rgcn_lpsm_backward(const float* qrows, int ldq, const float* z, int ldz, int width, int32_t num_nodes, const int64_t* target,
+                       int64_t n_queries, const float* lse, const float* g, float* dq, int lddq, float* dz, int lddz, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* From dq to the rows the query rows were built from, on the index of rgcn_lp_index_build of the same (s, r, o); the anchor is s
+ * (side 0) or o (side 1).  dz (may be NULL) is ACCUMULATED INTO: dz[v] += the sum over v's slots in sorted order whose parity is the
+ * anchor end -- DistMult dq o rel[r]; ComplEx conj(r) o dq (side 0), dq o r (side 1); rows without such a slot are not touched.  drel
+ * (may be NULL) is WRITTEN, every row: DistMult dq o z[a]; ComplEx conj(s) o dq (side 0), conj(dq) o o (side 1); chunks of 256
+ * triples, lane groups dealt round robin and added in order, then the chunks in order (rgcn_lp_backward's scheme and workspace,
+ * needed for drel only). */
+size_t rgcn_lpsm_query_backward_workspace_bytes(int decoder, int64_t n_triples, int32_t num_relations, int width);
+int rgcn_lpsm_query_backward(int decoder, int side, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes,
+                             int32_t num_relations, const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples,
+                             const float* dq, int lddq, const uint32_t* node_ptr, const uint32_t* node_slot, const uint32_t* rel_ptr,
+                             const uint32_t* rel_triple, float* dz, int lddz, float* drel, int lddrel, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- summaries -> original graph on tensors: block labels, transferred embeddings (csrc/rgcn_transfer.hip) ----------
  * Additions; RGCN_ABI_VERSION stays.  Both calls are asynchronous: no allocation, no read-back, no synchronisation, everything on
  * `stream`.  Argument checks come before the device is looked at.  An id out of range is never used as an address: it sets one of

@@ -167,6 +167,14 @@ def _prototypes() -> dict:
                                     vp]),
         "rgcn_kge_rank_workspace_bytes": (sz, [i32, i64, i32, i32]),
         "rgcn_kge_rank": (i32, [i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
+        "rgcn_lpsm_query": (i32, [i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp]),
+        "rgcn_lpsm_forward_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lpsm_forward": (i32, [vp, i32, vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, sz, vp]),
+        "rgcn_lpsm_backward_workspace_bytes": (sz, [i64, i32, i32, i32]),
+        "rgcn_lpsm_backward": (i32, [vp, i32, vp, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, i32, vp, sz, vp]),
+        "rgcn_lpsm_query_backward_workspace_bytes": (sz, [i32, i64, i32, i32]),
+        "rgcn_lpsm_query_backward": (i32, [i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, i32,
+                                           vp, i32, vp, sz, vp]),
         "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
@@ -917,6 +925,103 @@ def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.T
                                    greater.data_ptr(), equal.data_ptr(), *shape, workspace.data_ptr(), int(workspace.numel()), _stream(z)),
                   what)
     return greater, equal
+
+
+# ---- the softmax loss over all entities (rgcn_lp_softmax.hip) ------------------------------------------------
+LPSM_DISTMULT = 2      # RGCN_LPSM_DISTMULT: the `decoder` of the rgcn_lpsm_* calls beside KGE_COMPLEX
+
+
+def _lpsm_rows(rows: int, width: int, dev, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a ``[rows, width]`` float32 view of rows padded to a multiple of 4 (``out``: the caller's own view, taken as it is)"""
+    if out is not None:
+        return out
+    return torch.empty(rows, (width + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :width]
+
+
+def _lpsm_workspace(what: str, nbytes: int, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
+    return workspace if workspace is not None else torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def lpsm_query(decoder: int, side: int, z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.Tensor, target: torch.Tensor,
+               bad: Optional[torch.Tensor] = None, qrows: Optional[torch.Tensor] = None):
+    """rgcn_lpsm_query: ``(qrows [Q, E], qtarget int64 [Q])``, the decoder's query rows of (anchor, r) and the targets with -1 where
+    a query has an id out of range.  Asynchronous, as every call of this family."""
+    what = "rgcn_lpsm_query"
+    n_nodes, n_rel, width = _lp_tables(what, z, rel)
+    n = _lp_ids(what, z.device, anchor=anchor, r=r, target=target)
+    _lp_bad(what, bad, z.device)
+    qrows = _lpsm_rows(n, width, z.device, qrows)
+    qtarget = torch.empty(n, dtype=torch.int64, device=z.device)
+    if n:
+        with torch.cuda.device(z.device):
+            check(load().rgcn_lpsm_query(int(decoder), int(side), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes,
+                                         n_rel, anchor.data_ptr(), r.data_ptr(), target.data_ptr(), n, qrows.data_ptr(), qrows.stride(0),
+                                         qtarget.data_ptr(), _ptr(bad), _stream(z)), what)
+    return qrows, qtarget
+
+
+def lpsm_forward(qrows: torch.Tensor, z: torch.Tensor, target: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+    """rgcn_lpsm_forward: ``(lse, tlogit, loss)`` float32 [Q]; ``target`` is lpsm_query's ``qtarget``"""
+    lib, dev, what = load(), z.device, "rgcn_lpsm_forward"
+    n_nodes, n, width = _lp_tables(what, z, qrows)
+    _lp_ids(what, dev, target=target)
+    if int(target.shape[0]) != n:
+        raise RgcnLibraryError(f"{what}: {int(target.shape[0])} targets for {n} query rows")
+    lse, tlogit, loss = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(3))
+    if n:
+        with torch.cuda.device(dev):
+            ws = _lpsm_workspace(what, lib.rgcn_lpsm_forward_workspace_bytes(n, n_nodes, width), workspace, dev)
+            check(lib.rgcn_lpsm_forward(qrows.data_ptr(), qrows.stride(0), z.data_ptr(), z.stride(0), width, n_nodes, target.data_ptr(), n,
+                                        lse.data_ptr(), tlogit.data_ptr(), loss.data_ptr(), ws.data_ptr(), int(ws.numel()), _stream(z)), what)
+    return lse, tlogit, loss
+
+
+def lpsm_backward(qrows: torch.Tensor, z: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, g: torch.Tensor, need_z: bool = True,
+                  workspace: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None, dz: Optional[torch.Tensor] = None):
+    """rgcn_lpsm_backward: ``(dq [Q, E], dz [N, E] or None)``, dz being the entity side of the gradient only"""
+    lib, dev, what = load(), z.device, "rgcn_lpsm_backward"
+    n_nodes, n, width = _lp_tables(what, z, qrows)
+    _lp_ids(what, dev, target=target)
+    for name, t in (("lse", lse), ("g", g)):
+        if t.dtype != torch.float32 or t.device != dev or t.dim() != 1 or int(t.shape[0]) != n or (n > 1 and t.stride(0) != 1):
+            raise RgcnLibraryError(f"{what}: {name} must be a contiguous float32 [{n}] on {dev}")
+    if int(target.shape[0]) != n:
+        raise RgcnLibraryError(f"{what}: {int(target.shape[0])} targets for {n} query rows")
+    dq = _lpsm_rows(n, width, dev, dq)
+    if need_z:
+        dz = _lpsm_rows(n_nodes, width, dev, dz) if n else torch.zeros(n_nodes, width, dtype=torch.float32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            ws = _lpsm_workspace(what, lib.rgcn_lpsm_backward_workspace_bytes(n, n_nodes, width, int(need_z)), workspace, dev)
+            check(lib.rgcn_lpsm_backward(qrows.data_ptr(), qrows.stride(0), z.data_ptr(), z.stride(0), width, n_nodes, target.data_ptr(),
+                                         n, lse.data_ptr(), g.data_ptr(), dq.data_ptr(), dq.stride(0), _ptr(dz) if need_z else None,
+                                         dz.stride(0) if need_z else 0, ws.data_ptr(), int(ws.numel()), _stream(z)), what)
+    return dq, (dz if need_z else None)
+
+
+def lpsm_query_backward(decoder: int, side: int, z: torch.Tensor, rel: torch.Tensor, s: torch.Tensor, r: torch.Tensor, o: torch.Tensor,
+                        dq: torch.Tensor, ix: LpIndex, dz: Optional[torch.Tensor] = None, need_rel: bool = True,
+                        workspace: Optional[torch.Tensor] = None, drel: Optional[torch.Tensor] = None):
+    """rgcn_lpsm_query_backward: the anchor side of the gradient is added INTO ``dz`` (None: not wanted); returns ``drel [R, E]`` or
+    None.  ``ix``: the index of the same (s, r, o), the halves that are wanted."""
+    lib, dev, what = load(), z.device, "rgcn_lpsm_query_backward"
+    n_nodes, n_rel, width = _lp_tables(what, z, rel)
+    n = _lp_ids(what, dev, s=s, r=r, o=o)
+    _lp_tables(what, z, dq)
+    if int(dq.shape[0]) != n or (ix.n_triples, ix.num_nodes, ix.num_relations) != (n, n_nodes, n_rel):
+        raise RgcnLibraryError(f"{what}: dq or the index was built for other sizes")
+    if need_rel:
+        drel = _lpsm_rows(n_rel, width, dev, drel) if n else torch.zeros(n_rel, width, dtype=torch.float32, device=dev)
+    if n and (dz is not None or need_rel):
+        with torch.cuda.device(dev):
+            nbytes = lib.rgcn_lpsm_query_backward_workspace_bytes(int(decoder), n, n_rel, width) if need_rel else 0
+            ws = _lpsm_workspace(what, nbytes, workspace, dev)
+            check(lib.rgcn_lpsm_query_backward(int(decoder), int(side), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width,
+                                               n_nodes, n_rel, s.data_ptr(), r.data_ptr(), o.data_ptr(), n, dq.data_ptr(), dq.stride(0),
+                                               _ptr(ix.node_ptr), _ptr(ix.node_slot), _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(dz),
+                                               0 if dz is None else dz.stride(0), _ptr(drel) if need_rel else None,
+                                               drel.stride(0) if need_rel else 0, ws.data_ptr(), int(ws.numel()), _stream(z)), what)
+    return drel if need_rel else None
 
 
 # ---- summaries -> original graph (rgcn_transfer.hip; transfer.py validates and drives them) ---------------------------------

@@ -3,7 +3,8 @@ the kernels of csrc/rgcn_linkpred.hip, with the plumbing both frameworks' exampl
 DGL ``link.py``): ``with_inverse_edges`` for the encoder's graph, ``FilterIndex`` for the known triples, ``metrics`` for MRR and
 Hits@k.  The encoder is any model that returns ``z [N, dim]``, e.g. ``Emb_Layers(2 R, hidden, dim, N, emb)`` with
 ``activation=do_nothing``.  ``ComplEx`` and ``TransE`` are the asymmetric decoders, on the kernels of csrc/rgcn_kge.hip:
-the same index, negatives, filter and metrics serve them.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
+the same index, negatives, filter and metrics serve them.  ``softmax_loss`` is the 1-N training loss over all entities, on the kernels of
+csrc/rgcn_lp_softmax.hip.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -198,6 +199,62 @@ class TransE(_KgeDecoder):
     """``score(s, r, o) = -sum_k |z[s, k] + rel[r, k] - z[o, k]|``: the L1 norm, PyG's default ``p_norm``.  The gradient uses
     ``sign(0) = 0``, torch's convention.  Scores are never positive: train it with ``loss="margin"``."""
     code = _lib.KGE_TRANSE_L1
+
+
+class _SoftmaxLossFunction(torch.autograd.Function):
+    """rgcn_lpsm_query + rgcn_lpsm_forward forward; rgcn_lpsm_backward, then rgcn_lp_index_build + rgcn_lpsm_query_backward
+    backward.  The index is the decoders' own, built in the backward and only the halves the wanted gradients need."""
+
+    @staticmethod
+    def forward(ctx, z, rel, s, r, o, bad, builds, code, side):
+        zp, rp = _padded(z.detach()), _padded(rel.detach())
+        anchor, target = (s, o) if side == 0 else (o, s)
+        qrows, qtarget = _lib.lpsm_query(code, side, zp, rp, anchor, r, target, bad)
+        lse, _, loss = _lib.lpsm_forward(qrows, zp, qtarget)
+        ctx.save_for_backward(zp, rp, s, r, o, qrows, qtarget, lse)
+        ctx.bad, ctx.builds, ctx.code, ctx.side = bad, builds, code, side
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        zp, rp, s, r, o, qrows, qtarget, lse = ctx.saved_tensors
+        need_z, need_rel = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dz = drel = None
+        if need_z or need_rel:
+            dq, dz = _lib.lpsm_backward(qrows, zp, qtarget, lse, g.contiguous(), need_z)
+            ix = _lib.lp_index_build(s, r, o, int(zp.shape[0]), int(rp.shape[0]), ctx.bad, nodes=need_z, relations=need_rel)
+            ctx.builds["node"] += int(need_z)
+            ctx.builds["relation"] += int(need_rel)
+            drel = _lib.lpsm_query_backward(ctx.code, ctx.side, zp, rp, s, r, o, dq, ix, dz, need_rel)
+        return dz, drel, None, None, None, None, None, None, None
+
+
+def softmax_loss(z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor, side: str = "object") -> Tensor:
+    """The 1-N ("1vsAll") loss, float32 [Q]: ``loss_i = logsumexp_n <q_i, z_n> - <q_i, z_target_i>`` over ALL N entities, unfiltered
+    and with the true one included; ``q_i`` is the decoder's query row of (s_i, r_i, ?) (``side="object"``, the target is o_i) or
+    (?, r_i, o_i) (``"subject"``, the target is s_i), the row ``ranks`` scores with.  No [Q, N] logits exist, forward or backward
+    (csrc/rgcn_lp_softmax.hip).  Differentiable in ``z`` and ``decoder.rel`` under any upstream [Q] gradient.
+    ``DistMult`` of at most 128 columns and ``ComplEx``; ``TransE`` scores are no dot product with a query row, and the wide
+    ``DistMult`` is not served.  A triple with an id out of range gets loss 0 and no gradient and is reported by ``check()``."""
+    if side not in ("object", "subject"):
+        raise ValueError(f"side must be 'object' or 'subject' (got {side!r})")
+    if isinstance(decoder, DistMult):
+        if decoder.family != "lp":
+            raise ValueError(f"softmax_loss serves DistMult up to {MAX_WIDTH} columns (got {decoder.dim}); DESIGN.md 23")
+        code = _lib.LPSM_DISTMULT
+    elif isinstance(decoder, ComplEx):
+        code = decoder.code
+    else:
+        raise ValueError("softmax_loss needs a DistMult or ComplEx decoder: the score must be a dot product with a query row")
+    if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] != decoder.dim or z.dtype != torch.float32:
+        raise ValueError(f"z must be float32 [N, {decoder.dim}] (got {tuple(z.shape) if torch.is_tensor(z) else type(z)})")
+    if z.device != decoder.rel.device:
+        raise ValueError(f"z lives on {z.device}, the decoder on {decoder.rel.device}")
+    if z.device.type != "cuda":
+        raise ValueError(f"softmax_loss runs on the GPU only: z lives on {z.device} and there is no torch fallback")
+    s, r, o = _triples(s, r, o, z.device)
+    return _SoftmaxLossFunction.apply(z, decoder.rel, s, r, o, decoder._bad_word(z.device), decoder.index_builds, code,
+                                      0 if side == "object" else 1)
 
 
 def corrupt(s: Tensor, r: Tensor, o: Tensor, num_nodes: int, num_negatives: int, seed: int) -> Tuple[Tensor, Tensor, Tensor]:

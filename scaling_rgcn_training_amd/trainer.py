@@ -357,8 +357,11 @@ class Trainer:
         runs once per epoch, beside the loss read-back.  ``loss="margin"`` replaces the BCE term by PyG's TransE loss,
         ``relu(margin + neg - pos).mean()`` with every positive paired with its ``num_negatives`` negatives (torch ops on the two
         score vectors).  ``TransE`` scores are never positive, so BCE on them as logits can only push towards 0 and is a poor fit:
-        train ``TransE`` with ``loss="margin"``; ``DistMult`` and ``ComplEx`` take either."""
-        from .linkpred import FilterIndex, metrics
+        train ``TransE`` with ``loss="margin"``; ``DistMult`` and ``ComplEx`` take either.  ``loss="softmax"`` is the 1-N regime
+        (DESIGN.md 23): per batch ``linkpred.softmax_loss`` on both sides, every positive against ALL entities, the step loss the mean
+        of the ``2 B`` values plus the ``reg`` term; ``num_negatives`` is ignored and no negative is drawn.  ``DistMult`` up to 128
+        columns and ``ComplEx`` only."""
+        from .linkpred import FilterIndex, metrics, softmax_loss
         from .sampling import check_sample_seed
         for name, t in (("train_triples", train_triples), ("valid_triples", valid_triples)):
             if t is None and name == "valid_triples":
@@ -371,8 +374,8 @@ class Trainer:
         if batch_size is not None:
             _check_number("batch_size", batch_size, int, 1, "None or an int")
         _check_number("reg", reg, (int, float), 0, "a number")
-        if loss not in ("bce", "margin"):
-            raise ValueError(f"loss must be 'bce' or 'margin' (got {loss!r})")
+        if loss not in ("bce", "margin", "softmax"):
+            raise ValueError(f"loss must be 'bce', 'margin' or 'softmax' (got {loss!r})")
         _check_number("margin", margin, (int, float), 0, "a number")
         seed = check_sample_seed(seed)
         dev = self.device
@@ -393,14 +396,17 @@ class Trainer:
                 s, r, o = (batch[:, c].contiguous() for c in range(3))
                 optimizer.zero_grad()
                 z = model(data, do_nothing)
-                sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, _step_seed(seed, epoch, b))
-                scores = decoder(z, torch.cat([s, sn]), torch.cat([r, rn]), torch.cat([o, on]))
-                if loss == "bce":
-                    labels = torch.cat([torch.ones(s.shape[0], device=dev), torch.zeros(sn.shape[0], device=dev)])
-                    output = nn.functional.binary_cross_entropy_with_logits(scores, labels)
-                else:       # negative i * num_negatives + j belongs to positive i
-                    p, n = scores[:s.shape[0]], scores[s.shape[0]:].view(s.shape[0], num_negatives)
-                    output = torch.relu(margin + n - p[:, None]).mean()
+                if loss == "softmax":       # every positive against all entities, both sides: no negatives are drawn
+                    output = torch.cat([softmax_loss(z, decoder, s, r, o, side) for side in ("object", "subject")]).mean()
+                else:
+                    sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, _step_seed(seed, epoch, b))
+                    scores = decoder(z, torch.cat([s, sn]), torch.cat([r, rn]), torch.cat([o, on]))
+                    if loss == "bce":
+                        labels = torch.cat([torch.ones(s.shape[0], device=dev), torch.zeros(sn.shape[0], device=dev)])
+                        output = nn.functional.binary_cross_entropy_with_logits(scores, labels)
+                    else:       # negative i * num_negatives + j belongs to positive i
+                        p, n = scores[:s.shape[0]], scores[s.shape[0]:].view(s.shape[0], num_negatives)
+                        output = torch.relu(margin + n - p[:, None]).mean()
                 output = output + reg * (z.pow(2).mean() + decoder.rel.pow(2).mean())
                 output.backward()
                 optimizer.step()
