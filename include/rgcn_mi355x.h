@@ -828,6 +828,50 @@ int rgcn_lpsm_query_backward(int decoder, int side, const float* z, int ldz, con
                              const uint32_t* rel_triple, float* dz, int lddz, float* drel, int lddrel, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---- the softmax loss on DistMult rows wider than 128 (csrc/rgcn_lp_softmax_wide.hip) -------------------------------
+ * Additions; RGCN_ABI_VERSION stays.  The rgcn_lpsm_* calls above for the DistMult decoder with width 1..RGCN_XWIDE_MAX_WIDTH and a
+ * work split of their own (there is no `decoder` argument: no wide ComplEx exists).  Every convention, limit, status, the `bad` word,
+ * the void query and the contract of each call are those of rgcn_lpsm_*; the index of rgcn_lp_index_build serves this family too.
+ * NO FLOAT ATOMICS: every sum has a fixed order (below), so the same inputs give the same bits on every call.
+ * SW, the rows of the stationary table a workgroup keeps in LDS, is 64 for width <= 256 and 32 above;
+ *   slices(a, b) = min(ceil(1024 / ceil(a / SW)), ceil(ceil(b / 16) / 8)), at least 1.
+ *
+ * qrows [n_queries][ldq] = z[anchor] o rel[r]: one wave per row, lane l owns the 16-byte pieces l and l + 64 (rgcn_lpw_score's row
+ * layout); qtarget as rgcn_lpsm_query writes it. */
+int rgcn_lpsmw_query(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                     const int64_t* anchor, const int64_t* r, const int64_t* target, int64_t n_queries, float* qrows, int ldq,
+                     int64_t* qtarget, int32_t* bad, void* stream);
+
+/* lse, tlogit, loss [n_queries].  rgcn_lpw_rank's sweep (SW query rows in dynamic LDS, entity rows streamed 16 per wave in slabs of
+ * 128 columns, one device function for every logit: a chain of fp32 MFMA steps over (slab, c, j)) with rgcn_lpsm_forward's online
+ * pair and merge order: a lane's rows in sweep order, the sixteen lanes of a row group by a butterfly, the eight waves in order, the
+ * slices in order.  bytes = 8 * slices(Q, N) * SW ceil(Q / SW), in 256s. */
+size_t rgcn_lpsmw_forward_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width);
+int rgcn_lpsmw_forward(const float* qrows, int ldq, const float* z, int ldz, int width, int32_t num_nodes, const int64_t* target,
+                       int64_t n_queries, float* lse, float* tlogit, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+
+/* rgcn_lpsm_backward's dq and dz.  One sweep body for both: SW rows of one table stay in LDS; a workgroup step takes 128 rows of the
+ * other: each of the eight waves contracts 16 of them with the SW rows over all columns (the forward's chain per logit) and writes its
+ * 16 x SW weights to LDS, then each wave multiplies all 128 x SW weights by ITS eighth of the columns of the 128 rows.  An output
+ * element is one chain over the streamed rows in ascending order; then the slices of the streamed table in order.  bytes =
+ * 4 * slices(Q, N) * Q * 4 ceil(width / 4) if slices(Q, N) > 1, plus, when dz is asked for, 4 * slices(N, Q) * N * 4 ceil(width / 4)
+ * if slices(N, Q) > 1; each piece in 256s. */
+size_t rgcn_lpsmw_backward_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width, int want_dz);
+int rgcn_lpsmw_backward(const float* qrows, int ldq, const float* z, int ldz, int width, int32_t num_nodes, const int64_t* target,
+                        int64_t n_queries, const float* lse, const float* g, float* dq, int lddq, float* dz, int lddz, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* rgcn_lpsm_query_backward for DistMult on rgcn_lpw_backward's walks: dz[v] += sum over v's slots in sorted order whose parity is
+ * the anchor end (side 0: s, side 1: o) of dq o rel[r], one wave per node, rows without such a slot not touched; drel (WRITTEN, every
+ * row) = dq o z[anchor] in chunks of 256 triples dealt round robin to the 4 waves of a workgroup, the waves' rows added in wave
+ * order, then the chunks in order.  rgcn_lpw_backward's workspace, needed for drel only. */
+size_t rgcn_lpsmw_query_backward_workspace_bytes(int64_t n_triples, int32_t num_relations, int width);
+int rgcn_lpsmw_query_backward(int side, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes,
+                              int32_t num_relations, const int64_t* s, const int64_t* r, const int64_t* o, int64_t n_triples,
+                              const float* dq, int lddq, const uint32_t* node_ptr, const uint32_t* node_slot, const uint32_t* rel_ptr,
+                              const uint32_t* rel_triple, float* dz, int lddz, float* drel, int lddrel, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- summaries -> original graph on tensors: block labels, transferred embeddings (csrc/rgcn_transfer.hip) ----------
  * Additions; RGCN_ABI_VERSION stays.  Both calls are asynchronous: no allocation, no read-back, no synchronisation, everything on
  * `stream`.  Argument checks come before the device is looked at.  An id out of range is never used as an address: it sets one of

@@ -175,6 +175,14 @@ def _prototypes() -> dict:
         "rgcn_lpsm_query_backward_workspace_bytes": (sz, [i32, i64, i32, i32]),
         "rgcn_lpsm_query_backward": (i32, [i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, i32,
                                            vp, i32, vp, sz, vp]),
+        "rgcn_lpsmw_query": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp]),
+        "rgcn_lpsmw_forward_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lpsmw_forward": (i32, [vp, i32, vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, sz, vp]),
+        "rgcn_lpsmw_backward_workspace_bytes": (sz, [i64, i32, i32, i32]),
+        "rgcn_lpsmw_backward": (i32, [vp, i32, vp, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, i32, vp, sz, vp]),
+        "rgcn_lpsmw_query_backward_workspace_bytes": (sz, [i64, i32, i32]),
+        "rgcn_lpsmw_query_backward": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32,
+                                            vp, sz, vp]),
         "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
@@ -929,6 +937,17 @@ def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.T
 
 # ---- the softmax loss over all entities (rgcn_lp_softmax.hip) ------------------------------------------------
 LPSM_DISTMULT = 2      # RGCN_LPSM_DISTMULT: the `decoder` of the rgcn_lpsm_* calls beside KGE_COMPLEX
+LPSM_MAX_WIDTH = 128   # rows wider than this go to the rgcn_lpsmw_* calls (rgcn_lp_softmax_wide.hip), as lp_score(family=)
+                       # routes; at most this many columns take the rgcn_lpsm_* path
+
+
+def _lpsm_family(what: str, width: int, decoder: Optional[int] = None):
+    """``(the call's name, its leading decoder argument)``: rgcn_lpsm_* up to 128 columns, rgcn_lpsmw_* (DistMult only) above"""
+    if width <= LPSM_MAX_WIDTH:
+        return what, (() if decoder is None else (int(decoder),))
+    if decoder is not None and int(decoder) != LPSM_DISTMULT:
+        raise RgcnLibraryError(f"{what}: rows of {width} columns are served for the DistMult decoder only (rgcn_lpsmw_*)")
+    return what.replace("rgcn_lpsm_", "rgcn_lpsmw_"), ()
 
 
 def _lpsm_rows(rows: int, width: int, dev, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -952,11 +971,12 @@ def lpsm_query(decoder: int, side: int, z: torch.Tensor, rel: torch.Tensor, anch
     _lp_bad(what, bad, z.device)
     qrows = _lpsm_rows(n, width, z.device, qrows)
     qtarget = torch.empty(n, dtype=torch.int64, device=z.device)
+    what, head = _lpsm_family(what, width, decoder)
     if n:
         with torch.cuda.device(z.device):
-            check(load().rgcn_lpsm_query(int(decoder), int(side), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width, n_nodes,
-                                         n_rel, anchor.data_ptr(), r.data_ptr(), target.data_ptr(), n, qrows.data_ptr(), qrows.stride(0),
-                                         qtarget.data_ptr(), _ptr(bad), _stream(z)), what)
+            check(getattr(load(), what)(*head, *((int(side),) if head else ()), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width,
+                                        n_nodes, n_rel, anchor.data_ptr(), r.data_ptr(), target.data_ptr(), n, qrows.data_ptr(),
+                                        qrows.stride(0), qtarget.data_ptr(), _ptr(bad), _stream(z)), what)
     return qrows, qtarget
 
 
@@ -968,11 +988,12 @@ def lpsm_forward(qrows: torch.Tensor, z: torch.Tensor, target: torch.Tensor, wor
     if int(target.shape[0]) != n:
         raise RgcnLibraryError(f"{what}: {int(target.shape[0])} targets for {n} query rows")
     lse, tlogit, loss = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(3))
+    what, _ = _lpsm_family(what, width)
     if n:
         with torch.cuda.device(dev):
-            ws = _lpsm_workspace(what, lib.rgcn_lpsm_forward_workspace_bytes(n, n_nodes, width), workspace, dev)
-            check(lib.rgcn_lpsm_forward(qrows.data_ptr(), qrows.stride(0), z.data_ptr(), z.stride(0), width, n_nodes, target.data_ptr(), n,
-                                        lse.data_ptr(), tlogit.data_ptr(), loss.data_ptr(), ws.data_ptr(), int(ws.numel()), _stream(z)), what)
+            ws = _lpsm_workspace(what, getattr(lib, what + "_workspace_bytes")(n, n_nodes, width), workspace, dev)
+            check(getattr(lib, what)(qrows.data_ptr(), qrows.stride(0), z.data_ptr(), z.stride(0), width, n_nodes, target.data_ptr(), n,
+                                     lse.data_ptr(), tlogit.data_ptr(), loss.data_ptr(), ws.data_ptr(), int(ws.numel()), _stream(z)), what)
     return lse, tlogit, loss
 
 
@@ -990,12 +1011,13 @@ def lpsm_backward(qrows: torch.Tensor, z: torch.Tensor, target: torch.Tensor, ls
     dq = _lpsm_rows(n, width, dev, dq)
     if need_z:
         dz = _lpsm_rows(n_nodes, width, dev, dz) if n else torch.zeros(n_nodes, width, dtype=torch.float32, device=dev)
+    what, _ = _lpsm_family(what, width)
     if n:
         with torch.cuda.device(dev):
-            ws = _lpsm_workspace(what, lib.rgcn_lpsm_backward_workspace_bytes(n, n_nodes, width, int(need_z)), workspace, dev)
-            check(lib.rgcn_lpsm_backward(qrows.data_ptr(), qrows.stride(0), z.data_ptr(), z.stride(0), width, n_nodes, target.data_ptr(),
-                                         n, lse.data_ptr(), g.data_ptr(), dq.data_ptr(), dq.stride(0), _ptr(dz) if need_z else None,
-                                         dz.stride(0) if need_z else 0, ws.data_ptr(), int(ws.numel()), _stream(z)), what)
+            ws = _lpsm_workspace(what, getattr(lib, what + "_workspace_bytes")(n, n_nodes, width, int(need_z)), workspace, dev)
+            check(getattr(lib, what)(qrows.data_ptr(), qrows.stride(0), z.data_ptr(), z.stride(0), width, n_nodes, target.data_ptr(),
+                                     n, lse.data_ptr(), g.data_ptr(), dq.data_ptr(), dq.stride(0), _ptr(dz) if need_z else None,
+                                     dz.stride(0) if need_z else 0, ws.data_ptr(), int(ws.numel()), _stream(z)), what)
     return dq, (dz if need_z else None)
 
 
@@ -1012,15 +1034,16 @@ def lpsm_query_backward(decoder: int, side: int, z: torch.Tensor, rel: torch.Ten
         raise RgcnLibraryError(f"{what}: dq or the index was built for other sizes")
     if need_rel:
         drel = _lpsm_rows(n_rel, width, dev, drel) if n else torch.zeros(n_rel, width, dtype=torch.float32, device=dev)
+    what, head = _lpsm_family(what, width, decoder)
     if n and (dz is not None or need_rel):
         with torch.cuda.device(dev):
-            nbytes = lib.rgcn_lpsm_query_backward_workspace_bytes(int(decoder), n, n_rel, width) if need_rel else 0
+            nbytes = getattr(lib, what + "_workspace_bytes")(*head, n, n_rel, width) if need_rel else 0
             ws = _lpsm_workspace(what, nbytes, workspace, dev)
-            check(lib.rgcn_lpsm_query_backward(int(decoder), int(side), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width,
-                                               n_nodes, n_rel, s.data_ptr(), r.data_ptr(), o.data_ptr(), n, dq.data_ptr(), dq.stride(0),
-                                               _ptr(ix.node_ptr), _ptr(ix.node_slot), _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(dz),
-                                               0 if dz is None else dz.stride(0), _ptr(drel) if need_rel else None,
-                                               drel.stride(0) if need_rel else 0, ws.data_ptr(), int(ws.numel()), _stream(z)), what)
+            check(getattr(lib, what)(*head, int(side), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width,
+                                     n_nodes, n_rel, s.data_ptr(), r.data_ptr(), o.data_ptr(), n, dq.data_ptr(), dq.stride(0),
+                                     _ptr(ix.node_ptr), _ptr(ix.node_slot), _ptr(ix.rel_ptr), _ptr(ix.rel_triple), _ptr(dz),
+                                     0 if dz is None else dz.stride(0), _ptr(drel) if need_rel else None,
+                                     drel.stride(0) if need_rel else 0, ws.data_ptr(), int(ws.numel()), _stream(z)), what)
     return drel if need_rel else None
 
 

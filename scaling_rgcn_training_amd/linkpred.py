@@ -4,7 +4,7 @@ DGL ``link.py``): ``with_inverse_edges`` for the encoder's graph, ``FilterIndex`
 Hits@k.  The encoder is any model that returns ``z [N, dim]``, e.g. ``Emb_Layers(2 R, hidden, dim, N, emb)`` with
 ``activation=do_nothing``.  ``ComplEx`` and ``TransE`` are the asymmetric decoders, on the kernels of csrc/rgcn_kge.hip:
 the same index, negatives, filter and metrics serve them.  ``softmax_loss`` is the 1-N training loss over all entities, on the kernels of
-csrc/rgcn_lp_softmax.hip.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
+csrc/rgcn_lp_softmax.hip and, for a wide ``DistMult``, of csrc/rgcn_lp_softmax_wide.hip.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Tuple
@@ -206,8 +206,8 @@ class _SoftmaxLossFunction(torch.autograd.Function):
     backward.  The index is the decoders' own, built in the backward and only the halves the wanted gradients need."""
 
     @staticmethod
-    def forward(ctx, z, rel, s, r, o, bad, builds, code, side):
-        zp, rp = _padded(z.detach()), _padded(rel.detach())
+    def forward(ctx, z, rel, s, r, o, bad, builds, code, side, limit=MAX_WIDTH):
+        zp, rp = _padded(z.detach(), limit), _padded(rel.detach(), limit)
         anchor, target = (s, o) if side == 0 else (o, s)
         qrows, qtarget = _lib.lpsm_query(code, side, zp, rp, anchor, r, target, bad)
         lse, _, loss = _lib.lpsm_forward(qrows, zp, qtarget)
@@ -226,21 +226,29 @@ class _SoftmaxLossFunction(torch.autograd.Function):
             ctx.builds["node"] += int(need_z)
             ctx.builds["relation"] += int(need_rel)
             drel = _lib.lpsm_query_backward(ctx.code, ctx.side, zp, rp, s, r, o, dq, ix, dz, need_rel)
-        return dz, drel, None, None, None, None, None, None, None
+        return dz, drel, None, None, None, None, None, None, None, None
 
 
-def softmax_loss(z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor, side: str = "object") -> Tensor:
+def softmax_loss(z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor, side: str = "object", wide: bool = False) -> Tensor:
     """The 1-N ("1vsAll") loss, float32 [Q]: ``loss_i = logsumexp_n <q_i, z_n> - <q_i, z_target_i>`` over ALL N entities, unfiltered
     and with the true one included; ``q_i`` is the decoder's query row of (s_i, r_i, ?) (``side="object"``, the target is o_i) or
     (?, r_i, o_i) (``"subject"``, the target is s_i), the row ``ranks`` scores with.  No [Q, N] logits exist, forward or backward
     (csrc/rgcn_lp_softmax.hip).  Differentiable in ``z`` and ``decoder.rel`` under any upstream [Q] gradient.
-    ``DistMult`` of at most 128 columns and ``ComplEx``; ``TransE`` scores are no dot product with a query row, and the wide
-    ``DistMult`` is not served.  A triple with an id out of range gets loss 0 and no gradient and is reported by ``check()``."""
+    ``DistMult`` of at most 128 columns and ``ComplEx``; ``TransE`` scores are no dot product with a query row.  ``wide=True`` also
+    serves a ``DistMult(..., wide=True)`` of 129..512 columns, on csrc/rgcn_lp_softmax_wide.hip; every other decoder
+    runs with the flag bit for bit as without it.  A triple with an id out of range gets loss 0 and no gradient and is reported by
+    ``check()``."""
     if side not in ("object", "subject"):
         raise ValueError(f"side must be 'object' or 'subject' (got {side!r})")
+    if not isinstance(wide, bool):
+        raise ValueError(f"wide must be a bool (got {wide!r})")
+    limit = MAX_WIDTH
     if isinstance(decoder, DistMult):
         if decoder.family != "lp":
-            raise ValueError(f"softmax_loss serves DistMult up to {MAX_WIDTH} columns (got {decoder.dim}); DESIGN.md 23")
+            if not wide:
+                raise ValueError(f"softmax_loss serves DistMult up to {MAX_WIDTH} columns (got {decoder.dim}) unless wide=True is passed "
+                                 f"(up to {WIDE_MAX_WIDTH}); DESIGN.md 23, 24")
+            limit = WIDE_MAX_WIDTH
         code = _lib.LPSM_DISTMULT
     elif isinstance(decoder, ComplEx):
         code = decoder.code
@@ -254,7 +262,7 @@ def softmax_loss(z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor,
         raise ValueError(f"softmax_loss runs on the GPU only: z lives on {z.device} and there is no torch fallback")
     s, r, o = _triples(s, r, o, z.device)
     return _SoftmaxLossFunction.apply(z, decoder.rel, s, r, o, decoder._bad_word(z.device), decoder.index_builds, code,
-                                      0 if side == "object" else 1)
+                                      0 if side == "object" else 1, limit)
 
 
 def corrupt(s: Tensor, r: Tensor, o: Tensor, num_nodes: int, num_negatives: int, seed: int) -> Tuple[Tensor, Tensor, Tensor]:

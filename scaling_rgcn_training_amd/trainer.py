@@ -359,8 +359,8 @@ class Trainer:
         score vectors).  ``TransE`` scores are never positive, so BCE on them as logits can only push towards 0 and is a poor fit:
         train ``TransE`` with ``loss="margin"``; ``DistMult`` and ``ComplEx`` take either.  ``loss="softmax"`` is the 1-N regime
         (DESIGN.md 23): per batch ``linkpred.softmax_loss`` on both sides, every positive against ALL entities, the step loss the mean
-        of the ``2 B`` values plus the ``reg`` term; ``num_negatives`` is ignored and no negative is drawn.  ``DistMult`` up to 128
-        columns and ``ComplEx`` only."""
+        of the ``2 B`` values plus the ``reg`` term; ``num_negatives`` is ignored and no negative is drawn.  ``DistMult``
+        (a ``wide=True`` one of up to 512 columns included: DESIGN.md 24) and ``ComplEx`` only."""
         from .linkpred import FilterIndex, metrics, softmax_loss
         from .sampling import check_sample_seed
         for name, t in (("train_triples", train_triples), ("valid_triples", valid_triples)):
@@ -397,7 +397,8 @@ class Trainer:
                 optimizer.zero_grad()
                 z = model(data, do_nothing)
                 if loss == "softmax":       # every positive against all entities, both sides: no negatives are drawn
-                    output = torch.cat([softmax_loss(z, decoder, s, r, o, side) for side in ("object", "subject")]).mean()
+                    # (wide=True: a DistMult built with wide=True was the user's opt-in; every other decoder runs as without it)
+                    output = torch.cat([softmax_loss(z, decoder, s, r, o, side, wide=True) for side in ("object", "subject")]).mean()
                 else:
                     sn, rn, on = self._lp_negatives(s, r, o, int(z.shape[0]), num_negatives, _step_seed(seed, epoch, b))
                     scores = decoder(z, torch.cat([s, sn]), torch.cat([r, rn]), torch.cat([o, on]))

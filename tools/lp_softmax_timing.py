@@ -21,6 +21,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 from linkpred_timing import NODES, RELATIONS, wall_ms  # noqa: E402
 
 LP_RANK_TFLOPS = 86.33      # hip_raw_tflops_fp32 of the "ranks" line of profiles/linkpred_timing.txt (dim 64, 10,000 queries)
+LPW_RANK_TFLOPS = 112.0     # lpw_rank's sweep at 512 columns (profiles/linkpred_wide_timing.txt)
 
 
 def torch_loss(z, rel, s, r, o):
@@ -32,6 +33,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lp_softmax_timing.txt"))
+    ap.add_argument("--dim", type=int, nargs="+", default=[64, 128],
+                    help="widths to time; above 128 a DistMult(..., wide=True) on csrc/rgcn_lp_softmax_wide.hip (DESIGN.md 24)")
     args = ap.parse_args()
     import __graft_entry__ as g
     g.build()
@@ -42,15 +45,15 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(0)
     lines = [json.dumps({"steps": steps, "method": "host clock around calls that end in a synchronise, median after two warm-ups",
                          "device": torch.cuda.get_device_name(0), "entities": NODES, "relations": RELATIONS, "decoder": "distmult",
-                         "lp_rank_tflops_fp32_dim64": LP_RANK_TFLOPS})]
+                         "lp_rank_tflops_fp32_dim64": LP_RANK_TFLOPS, "lpw_rank_tflops_fp32_dim512": LPW_RANK_TFLOPS})]
 
     def emit(rec):
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
-    for dim in (64, 128):
+    for dim in args.dim:
         z = (torch.randn(NODES, dim, device=dev, generator=gen) * 0.3).requires_grad_(True)
-        dec = DistMult(RELATIONS, dim).to(dev)
+        dec = DistMult(RELATIONS, dim, wide=dim > 128).to(dev)
         for queries in (1024, 10000):
             s, o = (torch.randint(0, NODES, (queries,), device=dev, generator=gen) for _ in range(2))
             r = torch.randint(0, RELATIONS, (queries,), device=dev, generator=gen)
@@ -60,7 +63,7 @@ def main():
                 z.grad = dec.rel.grad = None
                 loss_fn().backward(gout)
 
-            ours = lambda: softmax_loss(z, dec, s, r, o)
+            ours = lambda: softmax_loss(z, dec, s, r, o, wide=True)
             rec = {"case": "softmax_loss", "dim": dim, "queries": queries, "hip_forward_ms": wall_ms(lambda: ours().detach(), steps),
                    "hip_forward_backward_ms": wall_ms(lambda: fb(ours), steps)}
             mine = (ours().detach(), z.grad.clone(), dec.rel.grad.clone())
