@@ -872,6 +872,37 @@ int rgcn_lpsmw_query_backward(int side, const float* z, int ldz, const float* re
                               const uint32_t* rel_triple, float* dz, int lddz, float* drel, int lddrel, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---- link prediction: the k best entities of a query (csrc/rgcn_lp_topk.hip) ---------------------------------------
+ * Additions; RGCN_ABI_VERSION stays.  For query q the candidates are all e in [0, num_nodes) that are not in
+ * filter_idx[filter_ptr[q] .. filter_ptr[q + 1]) (filter_ptr NULL: all of them); a candidate's score is the one rgcn_lp_rank /
+ * rgcn_kge_rank compare, from the same device function, bit for bit.  ids_out / scores_out [n_queries][k] hold the k best in the order
+ * of ONE 64-bit key per candidate, descending:
+ *     key = orderable(score) << 32 | (0xFFFFFFFF - e),   orderable(x) = bits(x + 0.0f) with the sign bit set when it was clear, all
+ *                                                        bits inverted when it was set
+ * that is, score descending (-0 and +0 equal) and, among equal scores, entity id ascending.  A NaN score is no candidate.  A query with
+ * fewer than k candidates ends in slots of id -1, score -inf; a query whose anchor or relation is out of range gets a whole row of
+ * them.  No [n_queries x num_nodes] matrix exists anywhere; no float atomics, and selection is by key alone, so the same inputs give
+ * the same bits and a query's row does not depend on the other queries of the call.
+ * The filter list of a query must be ASCENDING (it is searched by bisection; on a list that is not, which entries are excluded is
+ * unspecified).  filter_ptr is clamped to [0, filter_len]: nothing is read outside filter_idx[0 .. filter_len).  An entry out of range
+ * excludes nothing.
+ * 1 <= k <= 64, else RGCN_ERR_ARG.  Every other convention and refusal is rgcn_lp_rank's / rgcn_kge_rank's (NULL, WIDTH, STRIDE and
+ * alignment, ARG, PLAN: n_queries > 0xFFFF0000 or num_relations > 65536, WORKSPACE), answered before the device is looked at;
+ * n_queries == 0 launches nothing.  rgcn_kge_topk serves RGCN_KGE_COMPLEX (an odd width: RGCN_ERR_WIDTH) with rgcn_kge_rank's `side`;
+ * RGCN_KGE_TRANSE_L1 is NOT served (its sweep is not the matrix-instruction one) and is RGCN_ERR_ARG like any other value.
+ * The workspace holds the sorted k keys of every (query, entity slice): 8 * n_queries * slices * k bytes in 256s, slices as the rank
+ * sweep's grid.  The size queries answer 0 on arguments the call would refuse. */
+size_t rgcn_lp_topk_workspace_bytes(int64_t n_queries, int32_t num_nodes, int width, int k);
+int rgcn_lp_topk(const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes, int32_t num_relations,
+                 const int64_t* anchor, const int64_t* r, int64_t n_queries, int k, const int64_t* filter_ptr,
+                 const int64_t* filter_idx, int64_t filter_len, int64_t* ids_out, float* scores_out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+size_t rgcn_kge_topk_workspace_bytes(int decoder, int64_t n_queries, int32_t num_nodes, int width, int k);
+int rgcn_kge_topk(int decoder, int side, const float* z, int ldz, const float* rel, int ldr, int width, int32_t num_nodes,
+                  int32_t num_relations, const int64_t* anchor, const int64_t* r, int64_t n_queries, int k, const int64_t* filter_ptr,
+                  const int64_t* filter_idx, int64_t filter_len, int64_t* ids_out, float* scores_out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---- summaries -> original graph on tensors: block labels, transferred embeddings (csrc/rgcn_transfer.hip) ----------
  * Additions; RGCN_ABI_VERSION stays.  Both calls are asynchronous: no allocation, no read-back, no synchronisation, everything on
  * `stream`.  Argument checks come before the device is looked at.  An id out of range is never used as an address: it sets one of

@@ -17,8 +17,8 @@ Sub-modules:
   ``forward_blocks`` / ``Trainer.train_minibatch`` walk; ``block_index`` / ``BlockIndex``: the index ``RGCNConv.forward_block``
   runs a layer from, straight from a block, without graph plans
 * ``sparse_optim`` -- ``RowAdam``: Adam on the embedding rows a mini-batch step gathered, nothing else of the table is touched
-* ``linkpred`` -- link prediction: the ``DistMult`` decoder, ``corrupt`` negatives, filtered ``ranks`` / ``metrics``,
-  ``FilterIndex``, ``with_inverse_edges``; ``Trainer.train_link_prediction`` is the loop around them
+* ``linkpred`` -- link prediction: the ``DistMult`` decoder, ``corrupt`` negatives, filtered ``ranks`` / ``metrics``, ``topk``
+  predictions, ``FilterIndex``, ``with_inverse_edges``; ``Trainer.train_link_prediction`` is the loop around them
 * ``transfer`` -- summaries -> original graph on tensors: ``summary_labels`` (the fractional labels of a partition's blocks),
   ``TransferredEmbedding`` and the ``stack`` / ``concat`` / ``sum_embeddings`` tricks ``Trainer.train_original`` takes
 * ``tensor_data`` -- ``TensorDataset`` / ``TensorGraph``: the dataset ``Trainer`` reads, for a graph that has no node names
@@ -55,7 +55,7 @@ def __getattr__(name):
     if name == "RowAdam":
         from .sparse_optim import RowAdam
         return RowAdam
-    if name in ("DistMult", "corrupt", "with_inverse_edges", "FilterIndex", "ranks", "metrics"):
+    if name in ("DistMult", "corrupt", "with_inverse_edges", "FilterIndex", "ranks", "metrics", "topk"):
         from . import linkpred
         return getattr(linkpred, name)
     if name in ("TensorDataset", "TensorGraph"):

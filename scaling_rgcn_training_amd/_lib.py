@@ -183,6 +183,10 @@ def _prototypes() -> dict:
         "rgcn_lpsmw_query_backward_workspace_bytes": (sz, [i64, i32, i32]),
         "rgcn_lpsmw_query_backward": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32,
                                             vp, sz, vp]),
+        "rgcn_lp_topk_workspace_bytes": (sz, [i64, i32, i32, i32]),
+        "rgcn_lp_topk": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
+        "rgcn_kge_topk_workspace_bytes": (sz, [i32, i64, i32, i32, i32]),
+        "rgcn_kge_topk": (i32, [i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_block_labels_workspace_bytes": (sz, [i64, i64, i64, i32]),
         "rgcn_tr_block_labels": (i32, [vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, i64, vp, vp, vp, sz, vp]),
         "rgcn_tr_gather": (i32, [vp, vp, vp, vp, i32, i32, i64, vp, i64, i32, i64, vp, i64, i64, vp, vp]),
@@ -933,6 +937,41 @@ def lp_rank(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.T
                                    greater.data_ptr(), equal.data_ptr(), *shape, workspace.data_ptr(), int(workspace.numel()), _stream(z)),
                   what)
     return greater, equal
+
+
+def kge_topk(decoder: int, side: int, *args, **kw):
+    """lp_topk on rgcn_kge_topk (KGE_COMPLEX only); ``side`` as in kge_rank"""
+    return lp_topk(*args, family="kge", decoder=decoder, side=side, **kw)
+
+
+def lp_topk(z: torch.Tensor, rel: torch.Tensor, anchor: torch.Tensor, r: torch.Tensor, k: int,
+            filter_ptr: Optional[torch.Tensor] = None, filter_idx: Optional[torch.Tensor] = None,
+            workspace: Optional[torch.Tensor] = None, family: str = "lp", decoder: int = 0, side: int = 0):
+    """rgcn_lp_topk: ``(ids int64 [Q, k], scores float32 [Q, k])``, the k best candidates of the queries (anchor, r) that are not in
+    the query's ASCENDING filter list (CSR as in lp_rank; None: every entity is a candidate), best first, ties by ascending id; slots
+    past the last candidate are (-1, -inf).  csrc/rgcn_lp_topk.hip, DESIGN.md 25.  Asynchronous."""
+    lib, dev, what, head = load(), z.device, f"rgcn_{family}_topk", _kge_head(family, decoder)
+    n_nodes, n_rel, width = _lp_tables(what, z, rel)
+    n = _lp_ids(what, dev, anchor=anchor, r=r)
+    flen = 0
+    if filter_ptr is not None:
+        _lp_ids(what, dev, filter_ptr=filter_ptr)
+        _lp_ids(what, dev, filter_idx=filter_idx)
+        if int(filter_ptr.shape[0]) != n + 1:
+            raise RgcnLibraryError(f"{what}: filter_ptr holds {int(filter_ptr.shape[0])} entries for {n} queries")
+        flen = int(filter_idx.shape[0])
+    ids = torch.empty(n, int(k), dtype=torch.int64, device=dev)
+    scores = torch.empty(n, int(k), dtype=torch.float32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            if workspace is None:
+                workspace = torch.empty(getattr(lib, what + "_workspace_bytes")(*head, n, n_nodes, width, int(k)), dtype=torch.uint8,
+                                        device=dev)
+            check(getattr(lib, what)(*head, *((int(side),) if head else ()), z.data_ptr(), z.stride(0), rel.data_ptr(), rel.stride(0), width,
+                                     n_nodes, n_rel, anchor.data_ptr(), r.data_ptr(), n, int(k), _ptr(filter_ptr),
+                                     _ptr(filter_idx) if flen else None, flen, ids.data_ptr(), scores.data_ptr(), workspace.data_ptr(),
+                                     int(workspace.numel()), _stream(z)), what)
+    return ids, scores
 
 
 # ---- the softmax loss over all entities (rgcn_lp_softmax.hip; DESIGN.md 23) ------------------------------------------------

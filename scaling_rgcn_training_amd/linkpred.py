@@ -3,7 +3,7 @@ the kernels of csrc/rgcn_linkpred.hip, with the plumbing both frameworks' exampl
 DGL ``link.py``): ``with_inverse_edges`` for the encoder's graph, ``FilterIndex`` for the known triples, ``metrics`` for MRR and
 Hits@k.  The encoder is any model that returns ``z [N, dim]``, e.g. ``Emb_Layers(2 R, hidden, dim, N, emb)`` with
 ``activation=do_nothing``.  ``ComplEx`` and ``TransE`` are the asymmetric decoders, on the kernels of csrc/rgcn_kge.hip:
-the same index, negatives, filter and metrics serve them.  ``softmax_loss`` is the 1-N training loss over all entities, on the kernels of
+the same index, negatives, filter and metrics serve them.  ``topk`` answers a query with its ``k`` best entities on the kernels of csrc/rgcn_lp_topk.hip.  ``softmax_loss`` is the 1-N training loss over all entities, on the kernels of
 csrc/rgcn_lp_softmax.hip and, for a wide ``DistMult``, of csrc/rgcn_lp_softmax_wide.hip.  The hot paths have no torch fallback: tensors that are not on the GPU are refused."""
 from __future__ import annotations
 
@@ -371,6 +371,42 @@ def ranks(z: Tensor, decoder: nn.Module, s: Tensor, r: Tensor, o: Tensor, side: 
     limit = WIDE_MAX_WIDTH if decoder.family == "lpw" else MAX_WIDTH
     return _lib.lp_rank(_padded(z.detach(), limit), _padded(decoder.rel.detach(), limit), anchor, r, target, fptr, fidx,
                         family=decoder.family)
+
+
+def topk(z: Tensor, decoder: nn.Module, anchor: Tensor, r: Tensor, k: int, side: str = "object",
+         filter: Optional[FilterIndex] = None) -> Tuple[Tensor, Tensor]:
+    """``(ids int64 [Q, k], scores float32 [Q, k])``: the ``k`` (1..64) best objects of (anchor, r, ?) (``side="object"``) or subjects
+    of (?, r, anchor) (``"subject"``) among all N entities but, with ``filter``, those that complete the query to a known triple.  The
+    scores are ``ranks``'s, bit for bit; the order is score descending, equal scores by ascending id; a NaN score is never selected.
+    A query with fewer than ``k`` candidates ends in slots of id -1 and score -inf, a query with an id out of range is a whole row of
+    them.  No [Q, N] scores exist anywhere; a query's row does not depend on the other queries of the call.  ``DistMult`` of at most
+    128 columns and ``ComplEx`` (csrc/rgcn_lp_topk.hip)."""
+    if side not in ("object", "subject"):
+        raise ValueError(f"side must be 'object' or 'subject' (got {side!r})")
+    if isinstance(decoder, TransE):
+        raise ValueError("topk does not serve TransE: its candidates are swept on the vector ALU, not by the selection kernel (DESIGN.md 25)")
+    if not isinstance(decoder, (DistMult, ComplEx)):
+        raise ValueError("topk scores with a DistMult or ComplEx decoder")
+    if isinstance(decoder, DistMult) and decoder.family != "lp":
+        raise ValueError(f"topk serves DistMult rows of at most {MAX_WIDTH} columns (got {decoder.dim}; DESIGN.md 25)")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 64:
+        raise ValueError(f"k must be an int in 1..64 (got {k!r})")
+    if filter is not None and not isinstance(filter, FilterIndex):
+        raise ValueError("filter must be a FilterIndex or None")
+    if not torch.is_tensor(z) or z.dim() != 2 or z.shape[1] != decoder.dim or z.dtype != torch.float32:
+        raise ValueError(f"z must be float32 [N, {decoder.dim}]")
+    anchor, r = _ids("anchor", anchor, z.device), _ids("r", r, z.device)
+    if anchor.shape != r.shape:
+        raise ValueError(f"anchor and r must have one length (got {tuple(anchor.shape)}, {tuple(r.shape)})")
+    fptr = fidx = None
+    if filter is not None:
+        if filter.num_nodes != z.shape[0] or filter.num_relations != decoder.num_relations:
+            raise ValueError("the filter was built for another number of nodes or relations")
+        fptr, fidx = filter.lists(anchor, r, anchor, side)      # (lists keys on the anchor's end only)
+    zp, rp = _padded(z.detach()), _padded(decoder.rel.detach())
+    if isinstance(decoder, ComplEx):
+        return _lib.kge_topk(decoder.code, 0 if side == "object" else 1, zp, rp, anchor, r, k, fptr, fidx)
+    return _lib.lp_topk(zp, rp, anchor, r, k, fptr, fidx)
 
 
 def metrics(greater: Tensor, equal: Tensor, ks: Sequence[int] = (1, 3, 10), ties: str = "mean") -> Dict[str, float]:
